@@ -19,6 +19,7 @@ Extra objects on the JSON line:
                this same build of the kernels (null / absent otherwise).
   cpu_baseline the PyTorch-CPU restatement of the reference graph (oracle/torch_port.py; kind "port": TensorFlow 1.5 is not
                installable) on all host cores for a bounded sample at the same batch, rank 0 at N=1 only.
+  dump_outputs with --dump-outputs DIR: where the last timed iteration's costs, variables and u vectors went (dump_outputs()).
 """
 import argparse
 import ctypes as C
@@ -349,6 +350,30 @@ def cpu_baseline_mnist(cores, B=64, alpha=0.5, iters=5):
                                              "logging-only evals (model.py:374-398), mean %.2fs" % l}}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(m, out_dir):
+    """--dump-outputs: what the timed iterations hand their caller, as it stands after the last one -- the two logged costs
+    (d_loss.npy, g_loss.npy), every trainable variable (param.<name>.npy) and the spectral-norm u vectors (sn_u.<name>.npy),
+    float32, '/' in the variable names written as '.'.  The bench's inputs are seeded (pool, weights, device RNG), so two builds
+    run with the same arguments can be compared array by array."""
+    ctx = m.ctx
+    arrays = {"d_loss": ctx.download(m.loss_d).reshape(-1)[:1], "g_loss": ctx.download(m.loss_g).reshape(-1)[:1]}
+    for k, v in sorted(m.get_params().items()):
+        arrays["param." + k.replace("/", ".")] = v
+    for k, v in sorted(m.get_state().items()):
+        arrays["sn_u." + k.replace("/", ".")] = v.reshape(-1)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v)
+    return len(arrays), total
+
+
 def launcher_command(args, argv, env):
     """The command that starts the ranks of ``--gpus N`` when this process is not one of them already (no WORLD_SIZE in the
     environment): one process per GPU under torch.distributed.run on this node, rendezvous on 127.0.0.1.  None when this
@@ -397,7 +422,11 @@ def main():
     ap.add_argument("--lr", type=float, default=2e-4, help="Adam learning rate (reference: 2e-4, gan_resnet.py:--lr)")
     ap.add_argument("--master-port", type=int, default=0, help="rendezvous port of the ranks --gpus N starts (default: a free one)")
     ap.add_argument("--dry-run", action="store_true", help="print the launcher command --gpus N would start, and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the losses, variables and spectral-norm u vectors of the last one to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     default_wl = args.batch == 64 and args.dtype == "bf16" and args.algorithm == "rcgan"
 
     # --gpus N outside a launcher: start the N ranks as CHILD processes (this process has made no GPU call yet and never
@@ -464,6 +493,9 @@ def main():
         dt = float(t.item())
     d_loss, g_loss = m.losses()
     ok = np.isfinite(d_loss) and np.isfinite(g_loss)
+    dumped = None
+    if args.dump_outputs and rank == 0:      # before the profiling iterations below, which train on
+        dumped = dump_outputs(m, args.dump_outputs)
 
     # replicated state must stay bit-identical across ranks (same kernels on the same all-reduced gradients): every rank hashes its
     # parameters after the timed iterations, rank 0 reports whether all hashes agree
@@ -504,6 +536,8 @@ def main():
                           "iteration_tflops_algorithmic": round(60.858 * args.batch * world / 1e3, 3),
                           "sustained_tflops": round(60.858 * args.batch * world / 1e3 / (dt / args.steps), 2),
                           "losses_finite": bool(ok), "d_loss": round(d_loss, 4), "g_loss": round(g_loss, 4)}}
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped[0], "bytes": dumped[1]}
         if comm is not None:
             if weights_identical is not None:
                 out["config"]["rank_weights_bit_identical"] = bool(weights_identical)

@@ -326,3 +326,37 @@ def test_precision_study_bookkeeping():
     assert per_arm["bf16"]["n_seeds"] == 4 and per_arm["f32"]["n_seeds"] == 4
     d = paired["f32_minus_bf16"]
     assert d["n_pairs"] == 4 and abs(d["mean"] - 0.13) < 1e-9 and d["se"] > 0 and abs(d["t"] - d["mean"] / d["se"]) < 1e-9
+
+
+def test_bench_dump_outputs_writes_every_array_of_the_step(tmp_path):
+    """bench.py --dump-outputs: the two costs, every variable and every spectral-norm u vector as DIR/<name>.npy in float32, '/' in
+    the names written as '.'; a dump over the 64 MB cap is refused before anything is written; --steps 0 is refused."""
+    import importlib.util
+    import subprocess
+    import sys
+    from types import SimpleNamespace
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rs = np.random.RandomState(5)
+    params = {"Generator/G.Input/W": rs.randn(4, 6), "Discriminator/D.Output/b": rs.randn(1).astype(np.float32)}
+    state = {"Discriminator/D.Output/W/spectral_norm/u": rs.randn(1, 3).astype(np.float32)}
+    loss = {"d": np.float32([1.25]), "g": np.float32([-0.5])}
+    m = SimpleNamespace(loss_d="d", loss_g="g", ctx=SimpleNamespace(download=lambda t: loss[t]),
+                        get_params=lambda: params, get_state=lambda: state)
+    n, nbytes = bench.dump_outputs(m, str(tmp_path / "out"))
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(["d_loss.npy", "g_loss.npy", "param.Generator.G.Input.W.npy", "param.Discriminator.D.Output.b.npy",
+                            "sn_u.Discriminator.D.Output.W.spectral_norm.u.npy"]) and n == 5
+    got = {f[:-4]: np.load(str(tmp_path / "out" / f)) for f in files}
+    assert all(v.dtype == np.float32 for v in got.values()) and nbytes == sum(v.nbytes for v in got.values())
+    assert got["d_loss"].tolist() == [1.25] and got["g_loss"].tolist() == [-0.5]
+    assert np.array_equal(got["param.Generator.G.Input.W"], params["Generator/G.Input/W"].astype(np.float32))
+    assert np.array_equal(got["sn_u.Discriminator.D.Output.W.spectral_norm.u"], state["Discriminator/D.Output/W/spectral_norm/u"].reshape(-1))
+    params["Generator/G.Input/W"] = np.zeros((17, 1 << 20), np.float32)
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(m, str(tmp_path / "big"))
+    assert not os.path.exists(tmp_path / "big")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps" in r.stderr
