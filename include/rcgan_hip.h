@@ -563,6 +563,20 @@ int rcgan_bn_apply_segments(rcgan_ctx* ctx, int nseg, int n_per_seg, int rows_pe
  * host_scale * (*dev_scale if dev_scale != NULL); the loss VALUES they accumulate stay unscaled.  dev_scale is DEVICE memory read at
  * execution time, so a captured step follows a scale that changes between replays.  Default: 1, NULL. */
 int rcgan_set_grad_scale(rcgan_ctx* ctx, float host_scale, const float* dev_scale);
+
+/* ---- fp32 matmul precision (the counterpart of torch.set_float32_matmul_precision) -------------------------------------------
+ * How the gather GEMM (conv_direct.hip: the fp32 convolutions, their data and filter gradients and the dense layers with fp32
+ * activations) multiplies fp32 operands:
+ *   RCGAN_F32_PRECISION_HIGHEST  v_mfma_f32_32x32x2_f32: exact fp32 products (default)
+ *   RCGAN_F32_PRECISION_HIGH     every operand split into hi + lo bf16 (hi = bf16(x), lo = bf16(x - hi), nearest even) and
+ *                                a*b ~= a_lo*b_hi + a_hi*b_lo + a_hi*b_hi on v_mfma_f32_32x32x16_bf16, accumulated in fp32: about
+ *                                16 significand bits per operand, error ~2^-16 * sum|a*b| on top of fp32 accumulation
+ * The setting is read when a launch is ENQUEUED: a captured graph keeps the mode it was captured under.  Operands with 16-bit
+ * activations and every other kernel (column sums, tiny / skinny dense layers, batch norm, spectral norm, Adam) are not affected.
+ * Any other value: RCGAN_EINVALID_ARG. */
+#define RCGAN_F32_PRECISION_HIGHEST 0
+#define RCGAN_F32_PRECISION_HIGH 1
+int rcgan_set_f32_matmul_precision(rcgan_ctx* ctx, int precision);
 /* Dynamic loss scaling.  ls_state: DEVICE float[4] = {scale, applied steps since the last change, non-finite flag, skipped steps}.
  *   rcgan_grad_finite_check : raises the flag if g[0,count) holds an inf / nan (after the all-reduce: every rank sees the same sum);
  *   rcgan_adam_tf_dyn       : rcgan_adam_tf_host that (a) does nothing when the flag is raised (the step is skipped), (b) divides the

@@ -16,6 +16,8 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 CONV_IN_UPSAMPLE2X, CONV_IN_RELU, CONV_ACCUMULATE, CONV_FORCE_DIRECT, CONV_OUT_MEANPOOL2, CONV_RESID_UPSAMPLE2X = 1, 2, 4, 8, 16, 32
 LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_NEG_MEAN, LOSS_CE_ONES, LOSS_CE_ZEROS = 0, 1, 2, 3, 4
 QUERY_TR_READ = 0
+F32_PRECISION_HIGHEST, F32_PRECISION_HIGH = 0, 1     # rcgan_set_f32_matmul_precision
+F32_PRECISIONS = {"highest": F32_PRECISION_HIGHEST, "high": F32_PRECISION_HIGH}
 
 RCGAN_EHIP, RCGAN_ERCCL = -4, -5
 EUNSUPPORTED_SHAPE = -2
@@ -232,6 +234,7 @@ SIGNATURES = {
     "rcgan_comm_load_error": (C.c_char_p, []),
     "rcgan_set2_f32": (I, [P, P, F, F]),
     "rcgan_set_grad_scale": (I, [P, F, P]),
+    "rcgan_set_f32_matmul_precision": (I, [P, I]),
     "rcgan_grad_finite_check": (I, [P, SZ, P, P]),
     "rcgan_adam_tf_dyn": (I, [P, SZ, P, P, P, P, F, P, F, F, F, F, F, P]),
     "rcgan_loss_scale_update": (I, [P, P, P, P, F, F, F]),

@@ -17,7 +17,7 @@ import torch
 from . import _lib as L
 from . import ops as O
 from .ops_cifar import NO_OPS, Conv2D, Linear, cond_batchnorm, embed_y, spectral_normed_weight
-from .runtime import DT, Context, ParamGroup
+from .runtime import DT, Context, ParamGroup, check_f32_matmul_precision
 from .variables import Graph, scoped, variable_scope
 
 Z_DIM = 128
@@ -392,9 +392,11 @@ class CifarRCGAN:
                  confuse_init=False, confuse_init_diag=0.2, confuse_multiplier=1.0, confuse_lr_decay=False,
                  device=0, use_graphs=True, device_rng=True, arena_bytes=None, world_size=1, rank=0,
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
-                 grad_bucket_dtype=None, stub_model=None):
+                 grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest"):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # "high": the fp32 gather GEMMs on split-bf16 matrix cores (rcgan_set_f32_matmul_precision), on every context of the engine
+        self.f32_matmul_precision = check_f32_matmul_precision(f32_matmul_precision, dtype)
         self.alg, self.alpha, self.B, self.lr = algorithm, alpha, int(batch_size), lr
         self.perm, self.perm_mult, self.perm_type = perm_classifier, perm_multiplier, perm_type
         self.confuse_multiplier, self.confuse_lr_decay = confuse_multiplier, confuse_lr_decay
@@ -409,6 +411,7 @@ class CifarRCGAN:
             arena_bytes = int(2.5e6 * 4 * self.B * (4 if dtype == "f32" else 2)) + (1 << 30)
         self.ctx = Context(device, dtype, arena_bytes=arena_bytes)
         ctx = self.ctx
+        ctx.set_f32_matmul_precision(self.f32_matmul_precision)
         # Static loss scaling for fp16 activations (5 exponent bits: activation gradients of ~1e-5 and below would go
         # subnormal): every loss term -- hence every activation and filter gradient -- is multiplied by a power of two,
         # the fp32 filter gradients are divided by it inside the Adam kernel (grad_scale).  1 for bf16 / fp32.
@@ -556,6 +559,7 @@ class CifarRCGAN:
             self.ctx2 = Context(device, dtype, arena_bytes=int(2.5e6 * self.B * (4 if dtype == "f32" else 2)) + (256 << 20), ws_bytes=256 << 20)
             ctx.also_close = [self.ctx2]
             ctx.check(self.ctx2.lib.rcgan_set_grad_scale(self.ctx2.h, 1.0, None))
+            self.ctx2.set_f32_matmul_precision(self.f32_matmul_precision)
             self.graph2 = Graph(self.ctx2, [ParamGroup.alias(self.ctx2, self.PG)], {})
             self.graph2.persist = self.graph.persist        # the generator's prepared filters (refresh_persistent on the step stream)
             self.rng_state_gf = torch.zeros(2, dtype=torch.int64, device=ctx.device)

@@ -331,6 +331,7 @@ int rcgan_create(rcgan_ctx** out, int device, void* stream) {
   c->narrow_ws = nullptr; c->narrow_ws_bytes = 0; c->splitr_ws = nullptr; c->splitr_ws_bytes = 0;
   c->gscale_host = 1.f;
   c->gscale_dev = nullptr;
+  c->f32_precision = RCGAN_F32_PRECISION_HIGHEST;
   c->zero_page = nullptr;
   if (hipMalloc(&c->zero_page, RC_ZERO_PAGE_BYTES) != hipSuccess || hipMemset(c->zero_page, 0, RC_ZERO_PAGE_BYTES) != hipSuccess) {
     delete c;
@@ -505,6 +506,13 @@ int rcgan_graph_destroy(rcgan_ctx* ctx, int id) {
   RC_REQUIRE(ctx, id >= 0 && id < (int)ctx->graphs.size() && ctx->graphs[id], "graph id %d", id);
   (void)hipGraphExecDestroy(ctx->graphs[id]);
   ctx->graphs[id] = nullptr;
+  return RCGAN_OK;
+}
+
+int rcgan_set_f32_matmul_precision(rcgan_ctx* ctx, int precision) {
+  if (!ctx) return RCGAN_EINVALID_ARG;
+  RC_REQUIRE(ctx, precision == RCGAN_F32_PRECISION_HIGHEST || precision == RCGAN_F32_PRECISION_HIGH, "fp32 matmul precision %d", precision);
+  ctx->f32_precision = precision;
   return RCGAN_OK;
 }
 

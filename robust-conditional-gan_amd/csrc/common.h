@@ -34,6 +34,9 @@ struct rcgan_ctx {
   // gscale_host * (gscale_dev ? *gscale_dev : 1); the loss VALUES they accumulate stay unscaled
   float gscale_host;
   const float* gscale_dev;
+  // fp32 matmul precision of the gather GEMM (rcgan_set_f32_matmul_precision): RCGAN_F32_PRECISION_HIGHEST = fp32 MFMA,
+  // RCGAN_F32_PRECISION_HIGH = split-bf16 MFMA; read when a launch is enqueued
+  int f32_precision;
   // data-parallel gradient exchange (comm.hip): an RCCL communicator (or the single-process test double), its own stream for
   // buckets exchanged beside the rest of the backward pass, fork / join events (capturable)
   void* comm;          // ncclComm_t

@@ -4,7 +4,8 @@
 // fetch expressed as functors.  It serves every shape the 16-bit MFMA path does not take: fp32 mode (MNIST config 2 and
 // the fp32 parity runs), the MNIST 5x5 stride-2 convs and transposed convs, and all dense layers.  Same math as
 // tf.nn.conv2d / conv2d_backprop_input / conv2d_backprop_filter with SAME padding (reference call sites:
-// mnist/ops.py:62,78; cifar10/common/ops/conv2d.py:181-187).
+// mnist/ops.py:62,78; cifar10/common/ops/conv2d.py:181-187).  Opt-in ("high" fp32 matmul precision, rcgan_set_f32_matmul_precision): the
+// same skeleton on split-bf16 operands and v_mfma_f32_32x32x16_bf16 (gemm_gather_kernel<..., SPLIT = true>).
 #include <algorithm>
 
 #include "common.h"
@@ -593,7 +594,27 @@ template <class Op> __device__ __forceinline__ auto b_init(const Op& op, long j0
 
 #define GG_XBUF 2304   /* floats per operand buffer: max(64 x 36 K-major, 32 x 68 N-major) */
 
-template <class Op, int KS>
+// Split-bf16 MFMA ("high" fp32 matmul precision, rcgan_set_f32_matmul_precision): every fp32 operand element x is stored as
+// hi = bf16(x), lo = bf16(x - hi) (round to nearest even; x - hi is exact in fp32) and a K-step of 32 runs as two 16-wide halves
+// of three v_mfma_f32_32x32x16_bf16 each, lo*hi + hi*lo + hi*hi into the fp32 accumulator (small terms first).  The lo*lo term
+// (~2^-16 relative) is dropped.  The K-slot a lane feeds to element e of half h is 16*(lane>>5) + 8h + e for both operands.
+// LDS images, in the bytes of the fp32 buffer (dwords of two bf16, the lower K-slot in the low half):
+//   K-major: row r at dword 36 r: 16 dwords of hi (slots 0..31), then 16 of lo, 4 pad.  Read with ds_read_b128.
+//   N-major: K-slot pair p (slots 2p, 2p+1) at dword 68 p + row, hi in dwords [0, 1088), lo in [1088, 2176).  The fetch takes
+//            the slot pairs (2p, 2p+1) instead of (p, p+16), so a thread packs its own pairs; read with ds_read_b32.
+typedef __bf16 gg_bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 gg_bf16x2 __attribute__((ext_vector_type(2)));
+typedef float gg_f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned gg_u32x4 __attribute__((ext_vector_type(4)));
+#define GG_NMAJ_LO 1088   /* dwords: 16 slot pairs x 68 */
+// hi / lo dwords of the element pair (a, b): a in the low half
+__device__ __forceinline__ void split_pair(float a, float b, unsigned& hi, unsigned& lo) {
+  hi = __builtin_bit_cast(unsigned, __builtin_convertvector((gg_f32x2){a, b}, gg_bf16x2));      // v_cvt_pk_bf16_f32
+  const float ra = a - __uint_as_float(hi << 16), rb = b - __uint_as_float(hi & 0xffff0000u);
+  lo = __builtin_bit_cast(unsigned, __builtin_convertvector((gg_f32x2){ra, rb}, gg_bf16x2));
+}
+
+template <class Op, int KS, bool SPLIT = false>
 __global__ __launch_bounds__(256 * KS) void gemm_gather_kernel(Op op_in, typename Op::Aux aux) {
   extern __shared__ __attribute__((aligned(16))) float gg_smem[];
   Op op = op_in;
@@ -621,18 +642,42 @@ __global__ __launch_bounds__(256 * KS) void gemm_gather_kernel(Op op_in, typenam
   auto fetch = [&](long r0) {
     if constexpr (Op::A_KMAJOR) {
       op.a8(ast, r0 + (tid & 3) * 8, r_end, ra);
+    } else if constexpr (SPLIT) {               // N-major, split: the K-slot pair (2p, 2p + 1) instead of (p, p + 16)
+      op.a4(ast, r0 + 2 * (tid >> 4), r_end, ra);
+      op.a4(ast, r0 + 2 * (tid >> 4) + 1, r_end, ra + 4);
     } else {
       op.a4(ast, r0 + (tid >> 4), r_end, ra);
       op.a4(ast, r0 + (tid >> 4) + 16, r_end, ra + 4);
     }
     if constexpr (Op::B_KMAJOR) {
       op.b8(bst, r0 + (tid & 3) * 8, r_end, rb);
+    } else if constexpr (SPLIT) {
+      op.b4(r0 + 2 * (tid >> 4), r_end, bst, rb);
+      op.b4(r0 + 2 * (tid >> 4) + 1, r_end, bst, rb + 4);
     } else {
       op.b4(r0 + (tid >> 4), r_end, bst, rb);
       op.b4(r0 + (tid >> 4) + 16, r_end, bst, rb + 4);
     }
   };
   auto put = [&](float* xb, bool kmajor, const float* f) {
+    if constexpr (SPLIT) {
+      unsigned* const u = (unsigned*)xb;
+      unsigned hi[4], lo[4];
+      if (kmajor) {              // f: slots 8 (tid & 3) .. +7 of row tid >> 2
+#pragma unroll
+        for (int d = 0; d < 4; ++d) split_pair(f[2 * d], f[2 * d + 1], hi[d], lo[d]);
+        unsigned* p = u + (tid >> 2) * 36 + (tid & 3) * 4;
+        *(gg_u32x4*)p = (gg_u32x4){hi[0], hi[1], hi[2], hi[3]};
+        *(gg_u32x4*)(p + 16) = (gg_u32x4){lo[0], lo[1], lo[2], lo[3]};
+      } else {                   // f: rows 4 (tid & 15) .. +3 at slot 2p (f[0..3]) and 2p + 1 (f[4..7]), p = tid >> 4
+#pragma unroll
+        for (int q = 0; q < 4; ++q) split_pair(f[q], f[4 + q], hi[q], lo[q]);
+        unsigned* p = u + (tid >> 4) * 68 + (tid & 15) * 4;
+        *(gg_u32x4*)p = (gg_u32x4){hi[0], hi[1], hi[2], hi[3]};
+        *(gg_u32x4*)(p + GG_NMAJ_LO) = (gg_u32x4){lo[0], lo[1], lo[2], lo[3]};
+      }
+      return;
+    }
     if (kmajor) {
       float* p = xb + (tid >> 2) * 36 + (tid & 3) * 8;
       *(float4*)p = make_float4(f[0], f[1], f[2], f[3]);
@@ -679,8 +724,44 @@ __global__ __launch_bounds__(256 * KS) void gemm_gather_kernel(Op op_in, typenam
   // a wavefront whose 32 x 32 block lies wholly past M or N (the 10 label columns of a 138- / 74- / 1034-wide operand fill a sixth of their
   // tile) stages operands and keeps the barriers but leaves the matrix pipe and the LDS reads to the others
   const bool block_live = i0 + wr * 32 < op.M && j0 + wc * 32 < op.N;
+  // split: hi / lo operand of half h of the K-step for this lane (row w32 + l31, slots 16 hh + 8 h .. +7)
+  auto get_split = [&](const float* xb, bool kmajor, int w32, int h, gg_u32x4& hi, gg_u32x4& lo) {
+    const unsigned* u = (const unsigned*)xb;
+    if (kmajor) {
+      const unsigned* p = u + (w32 + l31) * 36 + 8 * hh + 4 * h;
+      hi = *(const gg_u32x4*)p;
+      lo = *(const gg_u32x4*)(p + 16);
+    } else {
+      const unsigned* p = u + (8 * hh + 4 * h) * 68 + w32 + l31;
+      hi = (gg_u32x4){p[0], p[68], p[136], p[204]};
+      lo = (gg_u32x4){p[GG_NMAJ_LO], p[GG_NMAJ_LO + 68], p[GG_NMAJ_LO + 136], p[GG_NMAJ_LO + 204]};
+    }
+  };
   auto mfma_step = [&](int buf) {
     if (!block_live) return;
+    if constexpr (SPLIT) {
+      gg_u32x4 ahi[2], alo[2], bhi[2], blo[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        get_split(lds + buf * GG_XBUF, Op::A_KMAJOR, wr * 32, h, ahi[h], alo[h]);
+        get_split(lds + (2 + buf) * GG_XBUF, Op::B_KMAJOR, wc * 32, h, bhi[h], blo[h]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const gg_bf16x8 ah = __builtin_bit_cast(gg_bf16x8, ahi[h]), al = __builtin_bit_cast(gg_bf16x8, alo[h]);
+        const gg_bf16x8 bh = __builtin_bit_cast(gg_bf16x8, bhi[h]), bl = __builtin_bit_cast(gg_bf16x8, blo[h]);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, acc, 0, 0, 0);
+      }
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
+      return;
+    }
     float av[16], bv[16];
     get(lds + buf * GG_XBUF, Op::A_KMAJOR, wr * 32, av);
     get(lds + (2 + buf) * GG_XBUF, Op::B_KMAJOR, wc * 32, bv);
@@ -946,12 +1027,12 @@ static int gg_env_int(const char* name, int dflt) {
   return (e && *e) ? atoi(e) : dflt;
 }
 
-template <class Op, int KS>
-static int launch_gemm_ks(rcgan_ctx* ctx, Op& op, dim3 grid, const typename Op::Aux& aux) {
+template <class Op, int KS, bool SPLIT>
+static int launch_gemm_kernel(rcgan_ctx* ctx, Op& op, dim3 grid, const typename Op::Aux& aux) {
   static bool attr_set = false;
   const size_t lds = (size_t)KS * 4 * GG_XBUF * sizeof(float);
   if (!attr_set) {
-    RC_HIP(ctx, hipFuncSetAttribute((const void*)gemm_gather_kernel<Op, KS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RC_HIP(ctx, hipFuncSetAttribute((const void*)gemm_gather_kernel<Op, KS, SPLIT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     attr_set = true;
   }
   {
@@ -959,10 +1040,19 @@ static int launch_gemm_ks(rcgan_ctx* ctx, Op& op, dim3 grid, const typename Op::
     // parity classes of a stride-2 data gradient -- over every class's share
     const double fl = 2.0 * (double)op.M * (double)op.N * (double)op.R * (has_select<Op>::value ? (double)grid.z : 1.0);
     ProfScope ps(ctx, RCGAN_PROF_GATHER_F32, fl);
-    hipLaunchKernelGGL((gemm_gather_kernel<Op, KS>), grid, dim3(256 * KS), lds, ctx->stream, op, aux);
+    hipLaunchKernelGGL((gemm_gather_kernel<Op, KS, SPLIT>), grid, dim3(256 * KS), lds, ctx->stream, op, aux);
   }
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
+}
+// the context's fp32 matmul precision, read when the launch is enqueued (a captured graph keeps the mode of its capture); it applies
+// to fp32 x fp32 operands only -- the 16-bit activation routes keep their kernels
+template <class Op, int KS>
+static int launch_gemm_ks(rcgan_ctx* ctx, Op& op, dim3 grid, const typename Op::Aux& aux) {
+  if constexpr (std::is_same<typename Op::AT, float>::value && std::is_same<typename Op::BT, float>::value) {
+    if (ctx->f32_precision == RCGAN_F32_PRECISION_HIGH) return launch_gemm_kernel<Op, KS, true>(ctx, op, grid, aux);
+  }
+  return launch_gemm_kernel<Op, KS, false>(ctx, op, grid, aux);
 }
 
 template <class Op>

@@ -14,7 +14,7 @@ import torch
 from . import _lib as L
 from . import ops as O
 from .ops_mnist import batch_norm, conv2d, conv_cond_concat, deconv2d, linear, lrelu
-from .runtime import DT, Context, ParamGroup
+from .runtime import DT, Context, ParamGroup, check_f32_matmul_precision
 from .variables import Graph, variable_scope
 
 Y_DIM, Z_DIM, GF_DIM, DF_DIM, GFC_DIM, DFC_DIM = 10, 100, 64, 64, 1024, 1024
@@ -95,7 +95,9 @@ class MnistRCGAN:
                  disc_type="projection", loss_fn="hinge", estimate_confuse=False, confuse_multiplier=10.0,
                  perm_regularizer=True, perm_multiplier=10.0, spectral_norm=True, max_norm=True,
                  concat_y=False, concat_y_layers=(1,), device=0, use_graphs=True, world_size=1, rank=0, variables=None,
-                 confusion_matrix=None):
+                 confusion_matrix=None, f32_matmul_precision="highest"):
+        # "high": the fp32 gather GEMMs on split-bf16 matrix cores (rcgan_set_f32_matmul_precision)
+        self.f32_matmul_precision = check_f32_matmul_precision(f32_matmul_precision, dtype)
         if loss_fn not in ("hinge", "ce"):
             raise ValueError('Unknown self.config.loss_fn: {}!'.format(loss_fn))          # model.py:147
         if algorithm not in ("biased", "unbiased", "rcgan", "ambient"):
@@ -109,6 +111,7 @@ class MnistRCGAN:
         self.world, self.rank, self.use_graphs = world_size, rank, use_graphs
         B = self.B
         self.ctx = ctx = Context(device, dtype, arena_bytes=(1 << 29) + B * (24 << 20) // 8, ws_bytes=1 << 29)
+        ctx.set_f32_matmul_precision(self.f32_matmul_precision)
         if variables is None:
             variables = create_variables(seed, disc_type, self.est, perm_regularizer, spectral_norm, self.layers)
         gs, ds, cs, S, U = variables

@@ -107,6 +107,16 @@ class Arena:
         return self.base + off
 
 
+def check_f32_matmul_precision(precision, dtype):
+    """The ``f32_matmul_precision`` argument of the models: "highest" (fp32 matrix cores, the default) or "high" (split-bf16
+    matrix cores, fp32 activations only).  Raises ValueError; needs no GPU."""
+    if precision not in L.F32_PRECISIONS:
+        raise ValueError("Unknown f32_matmul_precision %r: one of %s" % (precision, ", ".join(sorted(L.F32_PRECISIONS))))
+    if precision != "highest" and dtype != "f32":
+        raise ValueError("f32_matmul_precision=%r needs dtype='f32' (got %r)" % (precision, dtype))
+    return precision
+
+
 class Context:
     """One per process / GPU.  Wraps rcgan_ctx, the stream, the arena and the workspace."""
 
@@ -212,6 +222,12 @@ class Context:
 
     def sync(self):
         self.check(self.lib.rcgan_stream_sync(self.h))
+
+    def set_f32_matmul_precision(self, precision):
+        """"highest" or "high" (rcgan_set_f32_matmul_precision): read when a launch is enqueued, so a graph captured afterwards
+        keeps it."""
+        self.check(self.lib.rcgan_set_f32_matmul_precision(self.h, L.F32_PRECISIONS[precision]))
+        self.f32_matmul_precision = precision
 
     def zeros(self, shape, dtype=None):
         t = self.empty(shape, dtype)

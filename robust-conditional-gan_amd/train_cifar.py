@@ -52,6 +52,8 @@ def define_flags():
     f.DEFINE_string("log_level", 'info', "logging level [info, debug]")
     # this build's additions (absent flags keep the reference behaviour)
     f.DEFINE_string("dtype", 'bf16', "activation dtype [bf16, f16 (static loss scale 1024), f32]")
+    f.DEFINE_string("f32_matmul_precision", 'highest', "fp32 GEMMs with --dtype f32 [highest: fp32 matrix cores, high: split-bf16 "
+                    "matrix cores]")
     f.DEFINE_boolean("synthetic", False, "train on the SURVEY 8(d) synthetic data instead of ../data/cifar10")
     f.DEFINE_string("synthetic_kind", 'uniform', "with --synthetic: [uniform] SURVEY 8(d) label-free noise images, [templates] "
                     "class-pattern images (data.template_images) scored by eval_cifar.TemplateClassifier instead of the CIFAR ResNet")
@@ -119,7 +121,7 @@ def main(argv=None):
                    perm_classifier=FLAGS.perm_classifier, perm_multiplier=FLAGS.perm_multiplier, perm_type=FLAGS.perm_type,
                    confuse_init=FLAGS.confuse_init, confuse_init_diag=FLAGS.confuse_init_diag,
                    confuse_multiplier=FLAGS.confuse_multiplier, confuse_lr_decay=FLAGS.confuse_lr_decay,
-                   device=local, world_size=world, rank=rank)
+                   device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     if FLAGS.synthetic:

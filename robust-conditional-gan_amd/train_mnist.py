@@ -73,6 +73,8 @@ def define_flags():
     f.DEFINE_float("recover_learning_rate", 5.e+2, "recover_labels learning rate")
     # this build's additions (absent flags keep the reference behaviour)
     f.DEFINE_string("dtype", 'f32', "activation dtype [f32, bf16]")
+    f.DEFINE_string("f32_matmul_precision", 'highest', "fp32 GEMMs with --dtype f32 [highest: fp32 matrix cores, high: split-bf16 "
+                    "matrix cores]")
     f.DEFINE_boolean("synthetic", False, "train on SURVEY 8(d) synthetic digits instead of <data_dir>/mnist")
     f.DEFINE_integer("synthetic_size", 7000, "number of synthetic samples")
     f.DEFINE_string("synthetic_kind", 'uniform', "with --synthetic: [uniform] label-free noise digits, [templates] class-pattern digits "
@@ -150,7 +152,7 @@ def main(argv=None):
                    estimate_confuse=FLAGS.estimate_confuse, confuse_multiplier=FLAGS.confuse_multiplier,
                    perm_regularizer=FLAGS.perm_regularizer, perm_multiplier=FLAGS.perm_multiplier,
                    spectral_norm=FLAGS.spectral_norm, max_norm=FLAGS.max_norm, concat_y=FLAGS.concat_y, concat_y_layers=layers,
-                   device=local, world_size=world, rank=rank, confusion_matrix=data["C"])
+                   device=local, world_size=world, rank=rank, confusion_matrix=data["C"], f32_matmul_precision=FLAGS.f32_matmul_precision)
     sh = lambda a: shard_rows(a, rank, world)
     model_dir = os.path.join(ckpt_root, "{}_{}_{}_{}".format("mnist", B, 28, 28))          # model.py:836-840
     saver = Saver(max_to_keep=5)
@@ -245,7 +247,7 @@ def main(argv=None):
                          estimate_confuse=FLAGS.estimate_confuse, confuse_multiplier=FLAGS.confuse_multiplier,
                          perm_regularizer=FLAGS.perm_regularizer, perm_multiplier=FLAGS.perm_multiplier,
                          spectral_norm=FLAGS.spectral_norm, max_norm=FLAGS.max_norm, concat_y=FLAGS.concat_y, concat_y_layers=layers,
-                         device=local, use_graphs=False, confusion_matrix=data["C"])
+                         device=local, use_graphs=False, confusion_matrix=data["C"], f32_matmul_precision=FLAGS.f32_matmul_precision)
         rec.load_state_dict(final_state)
         recover_path = os.path.join(ckpt_root, 'recover_bs{}_epoch{}_lr{:.5g}'.format(R, FLAGS.recover_epoch, FLAGS.recover_learning_rate),
                                     datetime.now().strftime("%Y%m%d-%H%M%S"))
