@@ -20,7 +20,7 @@ F32_PRECISION_HIGHEST, F32_PRECISION_HIGH = 0, 1     # rcgan_set_f32_matmul_prec
 F32_PRECISIONS = {"highest": F32_PRECISION_HIGHEST, "high": F32_PRECISION_HIGH}
 
 RCGAN_EHIP, RCGAN_ERCCL = -4, -5
-EUNSUPPORTED_SHAPE = -2
+EINVALID_ARG, EUNSUPPORTED_SHAPE = -1, -2
 ERRORS = {-1: "RCGAN_EINVALID_ARG", -2: "RCGAN_EUNSUPPORTED_SHAPE", -3: "RCGAN_EWORKSPACE_TOO_SMALL",
           -4: "RCGAN_EHIP", -5: "RCGAN_ERCCL"}
 
@@ -89,6 +89,9 @@ class SnItem(C.Structure):
 class SnBwdItem(C.Structure):
     _fields_ = [("w", C.c_void_p), ("dwbar", C.c_void_p), ("dw", C.c_void_p), ("save", C.c_void_p),
                 ("k", C.c_int), ("c", C.c_int), ("accumulate", C.c_int)]
+
+
+SN_MAX_RANGES = 48     # rcgan_sn_bwd_adam: at most this many {lo, hi} ranges of the slab outside the items (csrc/sn.hip)
 
 
 class SnAdam(C.Structure):

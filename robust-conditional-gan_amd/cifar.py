@@ -492,6 +492,9 @@ class CifarRCGAN:
         # RCGAN_SN_ADAM=0 restores the separate launch.
         self.fused_tail = (not self.dp_active and not self.dynamic_ls and not self.graph_adam
                            and os.environ.get("RCGAN_SN_ADAM", "1") == "1")
+        # whether the last launch of a critic step applies the update, per captured step: False / True = d_step's "d" / "d_fakes" step
+        # (its fakes_ready), "d5" = critic_steps.  Written by the body that runs or is captured for that step: a replayed graph keeps its
+        # capture-time flag, and a forward-only _d_body (eval_d_cost) writes none.
         self._tail_fused = {}
         B = self.B
         f32, i32, act = L.F32, "i32", ctx.act_dtype
@@ -738,7 +741,8 @@ class CifarRCGAN:
 
     def _d_body(self, fakes_ready=False):
         """Forward + backward of disc_cost (gan_resnet.py:557-697) on this rank's shard.  fakes_ready: the generator
-        forward of this step was evaluated by prepare_critic_fakes; its images are in the fake rows of self.x_all."""
+        forward of this step was evaluated by prepare_critic_fakes; its images are in the fake rows of self.x_all.
+        Returns True when the step's last launch applies the optimiser update (rcgan_sn_bwd_adam)."""
         ctx, g, B, inp = self.ctx, self.graph, self.B, self.inp
         self._refresh_generator_filters()       # no-op unless the generator changed behind d_step/g_step's back
         ctx.new_step()
@@ -821,9 +825,14 @@ class CifarRCGAN:
             logits = perm_classifier(real, self.perm_type)                               # :692
             O.bce_onehot_term(ctx, logits, inp["labels"], 1.0, self.loss_d)                          # :693-695
         ctx.backward()
-        self._tail_fused[bool(fakes_ready)] = bool(ctx.sn_adam and ctx.sn_adam.get("done"))
+        fused = bool(ctx.sn_adam and ctx.sn_adam.get("done"))
         ctx.sn_adam = None
         self._dp_finish([self.PD])
+        return fused
+
+    def _d_step_body(self, fakes_ready):
+        """_d_body as d_step's step: records whether that step's last launch applies the update (self._tail_fused)."""
+        self._tail_fused[fakes_ready] = self._d_body(fakes_ready)
 
     # ---------------------------------------------------------------------------------- G step
     def _g_body(self):
@@ -1067,12 +1076,11 @@ class CifarRCGAN:
             else:
                 with torch.cuda.stream(ctx.stream):
                     ctx.view(self.x_all.rows(self.B, 2 * self.B)).copy_(ctx.view(self.fakes_all.rows(k * self.B, (k + 1) * self.B)), non_blocking=True)
-            self._run("d_fakes", lambda: self._d_body(True))
-            fused = self._tail_fused.get(True, False)
+            key, fakes_ready = "d_fakes", True
         else:
-            self._run("d", self._d_body)
-            fused = self._tail_fused.get(False, False)
-        if fused:
+            key, fakes_ready = "d", False
+        self._run(key, lambda: self._d_step_body(fakes_ready))
+        if self._tail_fused.get(fakes_ready, False):
             # the step's last launch applied the update (rcgan_sn_bwd_adam): host-side bookkeeping only
             lr = steps[0][1]
             self.PD.t += 1
@@ -1116,15 +1124,17 @@ class CifarRCGAN:
         self._join_gf()
 
         def body():
+            fused = True
             for k in range(N_CRITIC):
                 saved = {n: self.inp[n] for n in self._d_slot_views[k]}
                 self.inp.update(self._d_slot_views[k])
                 try:
-                    self._d_body(True)
+                    fused = self._d_body(True) and fused
                 finally:
                     self.inp.update(saved)
+            self._tail_fused["d5"] = fused
         self._run("d5", body)
-        assert self._tail_fused.get(True, False), "critic_steps: the step's last launch did not apply the update"
+        assert self._tail_fused.get("d5", False), "critic_steps: a step's last launch did not apply the update"
         self._fakes_left = 0                    # (the device's slice counter has walked all N_CRITIC slices and is back at 0)
         self.PD.t += N_CRITIC
         self.PD._dev_hyper = (float(lr), self.PD.t)

@@ -485,6 +485,12 @@ int rcgan_sn_bwd_adam(rcgan_ctx* ctx, const rcgan_sn_bwd_item* items, int n_item
     const size_t sz = (size_t)items[i].k * items[i].c;
     RC_REQUIRE(ctx, items[i].w >= opt->w && items[i].w + sz <= opt->w + opt->count, "item %d: w outside the slab", i);
     RC_REQUIRE(ctx, items[i].dw - opt->g == items[i].w - opt->w, "item %d: dw and w at different slab offsets", i);
+    // c % 4 == 0: sn_bwd_p2_kernel reads and writes the item's rows, its save buffer and its rows of m / v as float4
+    auto a16 = [](const void* p) { return ((size_t)p & 15) == 0; };
+    RC_REQUIRE(ctx, items[i].c % 4 != 0 || ((items[i].w - opt->w) % 4 == 0 && a16(items[i].w) && a16(items[i].dwbar) && a16(items[i].dw) &&
+                                            a16(items[i].save) && a16(opt->m) && a16(opt->v)),
+               "item %d ([%d,%d]): c %% 4 == 0 needs a slab offset that is a multiple of 4 floats and 16-byte aligned w, dwbar, dw, save, m, v",
+               i, items[i].k, items[i].c);
     iv.push_back({(size_t)(items[i].w - opt->w), (size_t)(items[i].w - opt->w) + sz});
   }
   for (int r = 0; r < opt->n_ranges; ++r) {

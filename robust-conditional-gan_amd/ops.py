@@ -276,11 +276,8 @@ def spectral_norm_batch(ctx, entries):
             bi[j] = L.SnBwdItem(w.param.ptr, w.dwbar.ptr, w.param.grad.ptr, save.ptr, k, c, 1)
             done.add(i)
         fa = getattr(ctx, "sn_adam", None)
+        ranges = None
         if fa is not None and not fa.get("done") and len(todo) == len(weights) and all(w.param.group is fa["group"] for _, w, _ in todo):
-            # (round 6) a single-rank step whose optimiser group is exactly this call's weights + the parameters between them: the
-            # second launch also applies TF-Adam -- to the rows it has just produced, and through rider workgroups to the rest of
-            # the slab (rcgan_sn_bwd_adam).  This closure is the LAST gradient work of the step (recorded first, it runs last), so
-            # every other gradient of the group is final here.
             grp = fa["group"]
             cover = sorted((grp.offsets[w.param.name], grp.offsets[w.param.name] + w.param.size) for _, w, _ in todo)
             ranges, at = [], 0
@@ -290,6 +287,13 @@ def spectral_norm_batch(ctx, entries):
                 at = hi
             if at < grp.count:
                 ranges += [at, grp.count]
+            if len(ranges) // 2 > L.SN_MAX_RANGES or grp.count >= 1 << 32:
+                ranges = None       # beyond what one fused call takes: dW alone here, the caller's optimiser launch afterwards
+        if ranges is not None:
+            # (round 6) a single-rank step whose optimiser group is exactly this call's weights + the parameters between them: the
+            # second launch also applies TF-Adam -- to the rows it has just produced, and through rider workgroups to the rest of
+            # the slab (rcgan_sn_bwd_adam).  This closure is the LAST gradient work of the step (recorded first, it runs last), so
+            # every other gradient of the group is final here.
             ra = (C.c_size_t * max(len(ranges), 1))(*ranges)
             opt = L.SnAdam(grp.value.data_ptr(), grp.grad.data_ptr(), grp.m.data_ptr(), grp.v.data_ptr(), grp.count, grp.hyper.data_ptr(),
                            fa["beta1"], fa["beta2"], fa.get("eps", 1e-8), fa.get("clip", 0.0), fa["grad_scale"], len(ranges) // 2, ra)

@@ -574,3 +574,111 @@ def test_critic_steps_as_one_graph_equal_single_steps(alg, perm, dtype, monkeypa
         assert np.array_equal(pa[k], pb[k]), k
     for k in sa:
         assert np.array_equal(sa[k], sb[k]), k
+
+
+def _slabs(m, *which):
+    """The critic's optimiser slabs as float64 (synchronises)."""
+    m.ctx.sync()
+    return {k: getattr(m.PD, k).detach().cpu().numpy().astype(np.float64) for k in which}
+
+
+def _assert_ulp(got, ref, scale, n, what):
+    """|got - ref| <= n fp32 ulp of ``scale`` (per element: the largest magnitude the update's arithmetic handles)."""
+    tol = n * np.spacing(np.abs(scale).astype(np.float32)).astype(np.float64)
+    bad = np.abs(got - ref) > tol
+    assert not bad.any(), "%s: %d elements beyond %d ulp, e.g. %r vs %r" % (what, int(bad.sum()), n, float(got[bad][0]), float(ref[bad][0]))
+
+
+@pytest.mark.parametrize("dtype,use_graphs", [("bf16", True), ("bf16", False), ("f32", True), ("f32", False)])
+def test_eval_d_cost_between_critic_steps_leaves_one_update_per_step(dtype, use_graphs, monkeypatch):
+    """d_step, d_step, eval_d_cost, d_step (the second and third d_step replay the captured step when graphs are on).  The forward-only
+    eval_d_cost runs the critic's body without the optimiser; the step replayed after it must still be ONE Adam update: the critic's
+    step count (host and device) is 3, the last step's m / v are one float64 TF-Adam update of the gradient it left in the slab (beta1
+    0, beta2 0.9), and its w moved by one step of those m / v at the step's decayed lr.  The separate optimiser launch
+    (RCGAN_SN_ADAM=0) passes the same checks and agrees as in test_optimiser_inside_the_spectral_norm_backward."""
+    from oracle import nn
+    from rcgan_amd.cifar import lr_decay
+    rs = np.random.RandomState(31)
+    B = 4
+    raws = [_batches(rs, B)[1] for _ in range(4)]
+    its = (0, 7000, None, 14000)           # None: eval_d_cost
+    finals = []
+    for fused in ("1", "0"):
+        monkeypatch.setenv("RCGAN_SN_ADAM", fused)
+        m, _, _ = _make("rcgan", False, B, dtype, use_graphs=use_graphs)
+        try:
+            assert m.fused_tail == (fused == "1")
+            for raw, it in zip(raws, its):
+                m.set_inputs(labels_all=_labels_all("rcgan", raw), **raw)
+                if it is None:
+                    assert np.isfinite(m.eval_d_cost())
+                    continue
+                if it == its[-1]:
+                    before = _slabs(m, "value", "m", "v")
+                m.d_step(iteration=it)
+            after = _slabs(m, "value", "m", "v", "grad")
+            assert m.PD.t == 3
+            if fused == "1":
+                assert float(m.PD.hyper.cpu()[1]) == 3.0
+            gi = after["grad"] * (1.0 / (m.world * m.loss_scale))
+            lr = m.lr * lr_decay(its[-1])
+            _, mm, v = nn.adam_tf(before["value"], gi, before["m"], before["v"], 3, lr, 0.0, 0.9)
+            _assert_ulp(after["m"], mm, np.maximum.reduce([np.abs(mm), np.abs(before["m"]), np.abs(gi)]), 4, "m (RCGAN_SN_ADAM=%s)" % fused)
+            _assert_ulp(after["v"], v, np.maximum.reduce([v, before["v"], gi * gi]), 4, "v (RCGAN_SN_ADAM=%s)" % fused)
+            # w: ONE step made of the m and v just checked (in fp32, m + (g - m)(1 - beta1) keeps only the high bits of a small g next
+            # to a large old m -- allowed for above; the step inherits it), to 8 ulp of the largest of old value, new value and step:
+            # the step carries the roundings of alpha, the product, the square root and the quotient.  A second update is a whole step.
+            w = before["value"] - after["m"] * (lr * np.sqrt(1.0 - 0.9 ** 3)) / (np.sqrt(after["v"]) + 1e-8)
+            _assert_ulp(after["value"], w, np.maximum.reduce([np.abs(w), np.abs(before["value"]), np.abs(before["value"] - w)]), 8,
+                        "w (RCGAN_SN_ADAM=%s)" % fused)
+            finals.append(after["value"])
+        finally:
+            m.ctx.close()
+    fa, fb = finals
+    assert np.isfinite(fa).all() and float(np.abs(fa - fb).max()) <= 2 * 2e-4 * 3 + 1e-6
+
+
+def test_eval_d_cost_in_the_trainer_s_order(monkeypatch):
+    """The trainer's order: prepare_critic_fakes + critic_steps, g_step, eval_d_cost, and the next iteration's critic_steps -- as one
+    captured graph of the N_CRITIC steps (RCGAN_CRITIC_GRAPH=1) and as N_CRITIC d_step calls on prepared fakes (=0).  Both leave the
+    critic's step count at 2 * N_CRITIC on the host and the device, and the same weights bit for bit (an extra update in either
+    would show)."""
+    import rcgan_amd  # noqa: F401
+    from rcgan_amd.cifar import CifarRCGAN, N_CRITIC
+    rs = np.random.RandomState(29)
+    B = 4
+    its = []
+    for _ in range(2):
+        ds = []
+        for _ in range(N_CRITIC):
+            raw = _batches(rs, B)[1]
+            d = {k: raw[k] for k in ("images", "labels", "labels_random", "labels_biased", "inv_weights")}
+            d["labels_all"] = _labels_all("rcgan", raw)
+            ds.append(d)
+        its.append((ds, dict(labels_random_G=rs.randint(10, size=2 * B), labels_biased_G=rs.randint(10, size=2 * B))))
+    outs = []
+    for one_graph in ("1", "0"):
+        monkeypatch.setenv("RCGAN_CRITIC_GRAPH", one_graph)
+        m = CifarRCGAN(algorithm="rcgan", alpha=0.6, batch_size=B, dtype="bf16", seed=5, use_graphs=True, device_rng=True,
+                       arena_bytes=2 << 30)
+        try:
+            for it, (ds, g) in enumerate(its):
+                if it > 0:
+                    m.feed_host("g", **g)
+                    m.g_step(iteration=it * 9000)
+                    m.feed_host("d", **its[it - 1][0][-1])
+                    assert np.isfinite(m.eval_d_cost())
+                m.feed_host("gf", labels_random_all=np.concatenate([d["labels_random"] for d in ds]))
+                m.prepare_critic_fakes()
+                assert m._critic_graph_ok() == (one_graph == "1")
+                m.critic_steps(ds, iteration=it * 9000)
+            assert ("d5" in m._graphs) == (one_graph == "1")
+            assert m.PD.t == 2 * N_CRITIC
+            m.ctx.sync()
+            assert float(m.PD.hyper.cpu()[1]) == 2 * N_CRITIC
+            outs.append(m.get_params())
+        finally:
+            m.ctx.close()
+    pa, pb = outs
+    for k in pa:
+        assert np.array_equal(pa[k], pb[k]), k
