@@ -1324,6 +1324,13 @@ struct FragRow { int item; int ctn, ss; bf16_t* fwd; bf16_t* bwd; };
 struct PrepBatch { PrepItem it[48]; PhasePrepBatch::It ph[8]; FragRow fr[12]; int start[72]; int n, rows, frag_row0, nfrag, gemm_row, inputs_row; SmallGemmArgs gemm; StepInputsArgs inputs; };
 
 static_assert(sizeof(PrepBatch) <= 4096, "kernel arguments are limited to 4 KiB");
+// rows of one launch at most: the items, the riding phase filters, the fragment rows and the two riders (label embeddings, step inputs)
+constexpr int PREP_MAX_ROWS = (int)(sizeof(PrepBatch::it) / sizeof(PrepItem) + sizeof(PrepBatch::ph) / sizeof(PhasePrepBatch::It) +
+                                    sizeof(PrepBatch::fr) / sizeof(FragRow)) + 2;
+// first step of conv_prepare_batch_kernel's binary row search: it reaches rows [0, 2 * PREP_ROW_STEP)
+constexpr int PREP_ROW_STEP = 64;
+static_assert(PREP_MAX_ROWS <= 2 * PREP_ROW_STEP, "the row search must reach every row a launch can hold");
+static_assert(PREP_MAX_ROWS + 1 <= (int)(sizeof(PrepBatch::start) / sizeof(int)), "start[] holds rows + 1 entries");
 
 // rows [R][K] -> fragment-major [block of 16*ctn rows][slice][step ss][tile ctn][lane 64][8] (rf_fragments_kernel's layout): the element index of (row, k)
 __device__ __forceinline__ long frag_index(int row, int k, int ctn, int ss, int nsl) {
@@ -1427,9 +1434,9 @@ __global__ __launch_bounds__(256) void conv_prepare_batch_kernel(PrepBatch b) {
   __shared__ __attribute__((aligned(16))) float lds_u[SG_AS_FLOATS + SG_RED_FLOATS];
   static_assert(sizeof(bf16_t) * 64 * 66 <= sizeof(float) * (SG_AS_FLOATS + SG_RED_FLOATS), "transpose tile fits");
   bf16_t (*tile)[66] = (bf16_t (*)[66])lds_u;
-  int row = 0;                                   // largest r with start[r] <= blockIdx.x (six dependent scalar loads, not 57)
+  int row = 0;                                   // largest r with start[r] <= blockIdx.x (seven dependent scalar loads, not 69)
 #pragma unroll
-  for (int step = 32; step > 0; step >>= 1) {
+  for (int step = PREP_ROW_STEP; step > 0; step >>= 1) {
     const int r = row + step;
     if (r < b.rows && (int)blockIdx.x >= b.start[r]) row = r;
   }
