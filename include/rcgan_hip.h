@@ -157,7 +157,8 @@ typedef struct rcgan_prepare_item {
 int rcgan_conv_prepare_batch(rcgan_ctx* ctx, const rcgan_prepare_item* items, int n_items);
 /* The same launch with the projection head's label embeddings riding in it as extra workgroups:
  * E[l][j] = (sum_k table[l][k] * w_e[k][j]) / sigma_e + b_e[j]  (embedding.py:29-51 + D.Embedding_y, gan_resnet.py:414-421).
- * E depends on parameters only; computed here it leaves the step's dependency chain (rcgan_head_desc::E_pre).  e may be NULL. */
+ * E depends on parameters only; computed here it leaves the step's dependency chain (rcgan_head_desc::E_pre).  e may be NULL.
+ * v <= 16 (the rider's LDS); a model of more classes computes E inside rcgan_proj_head_fwd_bwd instead. */
 typedef struct rcgan_embed_desc {
   int v, e_dim, d;
   const float *table, *w_e, *sigma_e /* device scalar or NULL */, *b_e /* or NULL */;
@@ -208,7 +209,7 @@ int rcgan_conv2d_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, co
  * (normalization.py:27-59, gan_resnet.py:350-352) applied to the convolution's staged input instead of being written out and read back:
  * for a forward-only pass (the critic steps' generator forwards) the normalised tensor never exists.  x: the batch norm's INPUT;
  * mean / rstd [segments][cin] from rcgan_bn_fwd_segments(..., y = NULL) (statistics only) or rcgan_bn_stats; gamma / beta [n_labels][cin];
- * labels [n] or NULL.  Same values as rcgan_bn_apply_* followed by rcgan_conv2d_fwd (the affine is evaluated in the same fp32
+ * labels [n] or NULL (any n_labels up to 1024: each workgroup stages only its image's [2][cin] affine).  Same values as rcgan_bn_apply_* followed by rcgan_conv2d_fwd (the affine is evaluated in the same fp32
  * sequence and rounded to 16 bits at the same point).  rcgan_conv_bn_in_ok: the small-output image-end layers (G.Output: 256 -> 3) and
  * (round 5) the 3x3 / upsample-3x3 layers the halo-patch kernels take (conv_mfma8h.hip: 16- / 32-wide (low-resolution) images, enough
  * 256-pixel tiles to fill the chip -- G.Block.2.Conv2, G.Block.3.Conv1 / Conv2 at the bench batches); d->flags may carry
@@ -288,8 +289,11 @@ size_t rcgan_linear_workspace_bytes(int m, int k, int n);
 /* Batch statistics over rows of x[rows][c]: mean, biased var -> rstd = rsqrt(var+eps).
  * moving_mean / moving_var (may be NULL) get the TF fused-batch-norm update
  * m -= (m - batch)*(1-decay) with the UNBIASED variance (mnist/ops.py:38-44).
- * ws: rcgan_bn_workspace_bytes(rows, c). */
+ * ws: rcgan_bn_workspace_bytes(rows, c) for up to 16 labels; rcgan_bn_workspace_bytes_labels(rows, c, n_labels) grows with the
+ * label count (the per-label tables of the non-power-of-two apply paths) and equals the former for n_labels <= 16.
+ * Label bounds of the conditional calls below: 1 <= n_labels <= 1024, every label in [0, n_labels). */
 size_t rcgan_bn_workspace_bytes(int rows, int c);
+size_t rcgan_bn_workspace_bytes_labels(int rows, int c, int n_labels);
 int rcgan_bn_stats(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, float eps,
                    float* mean, float* rstd, float* moving_mean, float* moving_var, float decay,
                    void* ws, size_t ws_bytes);
@@ -308,7 +312,10 @@ int rcgan_bn_fwd_segments(rcgan_ctx* ctx, int nseg, int n_per_seg, int rows_per_
                           const void* x, const int32_t* labels, const float* gamma, const float* beta, float eps, int act,
                           float* mean, float* rstd, void* y, void* ws, size_t ws_bytes);
 /* Backward of stats+apply (gradient flows through the batch statistics).  dgamma/dbeta: [n_labels][c]
- * (= or += by accumulate); dx = or += by accumulate_dx.  y is the forward output (activation mask). */
+ * (= or += by accumulate); dx = or += by accumulate_dx.  y is the forward output (activation mask).
+ * n_labels <= 16: per-label accumulators in registers / LDS (the fused, tree and generic paths).  17 .. 1024: per-sample partials
+ * in ws, then a deterministic fp64 reduction per (label, channel) in sample order; a label absent from the batch gets 0 (left
+ * untouched under accumulate).  ws: (n*2*c + 4*c) floats on that route (within rcgan_bn_workspace_bytes for n <= 8192). */
 int rcgan_bn_bwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype,
                  const void* x, const void* y, const void* dy, const int32_t* labels,
                  const float* gamma, const float* mean, const float* rstd, int act,
@@ -409,7 +416,7 @@ int rcgan_rng_fill(rcgan_ctx* ctx, size_t count, int dtype, int kind, float lo, 
 int rcgan_act_meanhw_fwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int act, const void* x, float* feat);
 int rcgan_act_meanhw_bwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int act, const void* x,
                          const float* dfeat, void* dx);
-/* rows gathered from a [v][d] table / scatter-added back (tf.nn.embedding_lookup, embedding.py:51). */
+/* rows gathered from a [v][d] table / scatter-added back (tf.nn.embedding_lookup, embedding.py:51).  No bound on v (idx in [0, v)). */
 int rcgan_gather_rows(rcgan_ctx* ctx, int n, int d, const float* table, const int32_t* idx, float* out);
 int rcgan_scatter_add_rows(rcgan_ctx* ctx, int n, int d, int v, const float* src, const int32_t* idx,
                            float* table_grad, int accumulate);
@@ -419,7 +426,8 @@ int rcgan_proj_logit_fwd(rcgan_ctx* ctx, int n, int d, const float* feat, const 
 int rcgan_proj_logit_bwd(rcgan_ctx* ctx, int n, int d, const float* feat, const float* emb, const float* dlogit,
                          float* dfeat, float* dpsi, float* demb, int acc_feat);
 /* logits[n][v] = psi[n] + <feat[n,:], E[v,:]> for every label v (rcgan-u: gan_resnet.py:654-660, 737-740;
- * the reference re-runs the projection for all 10 labels -- features are computed once here) + adjoint. */
+ * the reference re-runs the projection for all 10 labels -- features are computed once here) + adjoint.  No bound on v: a wavefront
+ * per logit, a thread per output of the adjoint (v <= 1024 in the models). */
 int rcgan_proj_logit_all_fwd(rcgan_ctx* ctx, int n, int d, int v, const float* feat, const float* psi,
                              const float* E, float* logits);
 int rcgan_proj_logit_all_bwd(rcgan_ctx* ctx, int n, int d, int v, const float* feat, const float* E,
@@ -429,7 +437,8 @@ int rcgan_proj_logit_all_bwd(rcgan_ctx* ctx, int n, int d, int v, const float* f
  *   CE_ONES / CE_ZEROS: mean sigmoid_ce(x, 1|0) (mnist/model.py:139-145)
  * x: [rows][cols]; optional row weights wts[rows][cols] turn the inner mean into
  * mean_rows( sum_cols( term * wts ) )  (unbiased :647, rcgan-u :684,759; mnist/model.py:201-204);
- * dwts (may be NULL) receives weight * dL/dwts (needed for the learned confusion matrix). */
+ * dwts (may be NULL) receives weight * dL/dwts (needed for the learned confusion matrix).  One workgroup: any rows x cols
+ * (the [B, K] weight rows of the K-class models included). */
 #define RCGAN_LOSS_HINGE_REAL 0
 #define RCGAN_LOSS_HINGE_FAKE 1
 #define RCGAN_LOSS_NEG_MEAN 2
@@ -485,7 +494,11 @@ int rcgan_conv2d_rf(rcgan_ctx* ctx, const rcgan_conv_desc* d, int backward, cons
  * gradients in one launch.  Rows [0, rows_a) form part a, rows [rows_a, n) part b (real | fake of the critic step, :604-606);
  * each part has its loss kind and EITHER int32 labels [rows] (one-hot weights) OR a weight matrix [rows, v] (confusion-matrix
  * rows :682-684, C^-1 rows :647) with optional d/d(weights).  ws: (v*d + n*(v+1) + (v+1)*d + 256) floats of scratch.  loss_acc += weight * (mean over the part's rows);
- * dfeat is written, the five parameter gradients are accumulated (+=); any output may be null. */
+ * dfeat is written, the five parameter gradients are accumulated (+=); any output may be null.
+ * Bounds: n <= 1024, d <= 256, 1 <= v <= 1024.  v <= 16: label embeddings in LDS, parameter gradients may ride (E_pre, defer_ws).
+ * v > 16: a route with nothing sized by v in LDS or registers (a thread per output of E, dE and the parameter gradients; the
+ * weight-row logits 64 labels at a time): defer_ws is ignored (the gradients are complete on return), E_pre is honoured,
+ * ws: (v*d + n*(v+1) + (v+1)*d + n + n*d) floats. */
 typedef struct {
   int n, d, v, e_dim;
   int rows_a, kind_a, kind_b;
@@ -513,6 +526,7 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
                             float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
                             float* db_e, void* ws, size_t ws_bytes);
 int rcgan_head_flush(rcgan_ctx* ctx);
+/* (bce_onehot: one workgroup, any rows x cols, labels in [0, cols).) */
 int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x, const int32_t* labels,
                              float weight, float* loss_acc, float* dx);
 /* recover_labels objective (mnist/model.py:533-537): gen [r*ydim, pix] = one generated image per (real sample r, label y),
@@ -521,7 +535,8 @@ int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x,
  * Writes loss [1], dgen (same shape as gen, or NULL) and dyrec [r, ydim] (or NULL).  ws: r*ydim floats. */
 int rcgan_recover_mse_fwd_bwd(rcgan_ctx* ctx, int r, int ydim, int pix, int dtype, const void* gen, const void* actual,
                               const float* yrec, float* loss, void* dgen, float* dyrec, void* ws, size_t ws_bytes);
-/* C = softmax(logits) row-wise and its adjoint (gan_resnet.py:522, mnist/model.py:106). */
+/* C = softmax(logits) row-wise and its adjoint (gan_resnet.py:522, mnist/model.py:106).  A thread per row: any cols (the
+ * K x K confusion matrix of rcgan-u, K <= 1024). */
 int rcgan_softmax_rows_fwd(rcgan_ctx* ctx, int rows, int cols, const float* logits, float* p);
 int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, const float* dp, float* dlogits,
                            int accumulate);

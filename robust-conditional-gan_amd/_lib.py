@@ -91,6 +91,10 @@ class SnBwdItem(C.Structure):
                 ("k", C.c_int), ("c", C.c_int), ("accumulate", C.c_int)]
 
 
+# class counts of the conditional models (include/rcgan_hip.h): the narrow routes (per-label accumulators in registers / LDS, label
+# embeddings riding in other launches) take up to LABELS_NARROW classes, the wide ones up to MAX_CLASSES
+LABELS_NARROW = 16
+MAX_CLASSES = 1024
 SN_MAX_RANGES = 48     # rcgan_sn_bwd_adam: at most this many {lo, hi} ranges of the slab outside the items (csrc/sn.hip)
 
 
@@ -160,6 +164,7 @@ SIGNATURES = {
     "rcgan_linear_bwd_weight": (I, [P, I, I, I, I, P, P, P, P, I, P, SZ]),
     "rcgan_linear_workspace_bytes": (SZ, [I, I, I]),
     "rcgan_bn_workspace_bytes": (SZ, [I, I]),
+    "rcgan_bn_workspace_bytes_labels": (SZ, [I, I, I]),
     "rcgan_bn_stats": (I, [P, I, I, I, P, F, P, P, P, P, F, P, SZ]),
     "rcgan_bn_apply_fwd": (I, [P, I, I, I, I, I, P, P, P, P, P, P, I, P, P, SZ]),
     "rcgan_bn_fwd_segments": (I, [P, I, I, I, I, I, I, P, P, P, P, F, I, P, P, P, P, SZ]),

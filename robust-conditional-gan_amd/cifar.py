@@ -23,7 +23,7 @@ from .variables import Graph, scoped, variable_scope
 Z_DIM = 128
 DIM_G = 128
 DIM_D = 128
-VOCAB_SIZE = 10
+VOCAB_SIZE = 10                 # the reference's class count (CIFAR-10); a model of K classes: CifarRCGAN(n_classes=K)
 EMBEDDING_DIM = 300
 IMG_SIZE = 32
 IMG_DIM = 3
@@ -45,7 +45,8 @@ POOL_IN_TRUNK = os.environ.get("RCGAN_POOL_IN_TRUNK", "1") == "1"
 # variable creation (reference initialisers, reference creation order -- SURVEY.md Appendix A)
 # ------------------------------------------------------------------------------------------------------
 class _Init:
-    def __init__(self, seed):
+    def __init__(self, seed, n_classes=VOCAB_SIZE):
+        self.K = int(n_classes)
         # rs: numpy's stream -- the reference draws its filters / matrices / embedding table from np.random in graph-construction
         # order (conv2d.py:83-88, linear.py:54-61, embedding.py:29-34), reproduced here bit for bit from np.random.seed(seed)
         # (tests/golden/ref_cifar_*.npz).  rs_tf: what TensorFlow's own generators initialise (the spectral-norm u vectors, sn.py:36;
@@ -90,8 +91,8 @@ class _Init:
     def condbn(self, dst, name, c):           # normalization.py:49-52 (constant initialisers: no draw)
         if dst is None:
             return
-        dst.append((name + "/CondBatchNorm/offset", (VOCAB_SIZE, c), np.zeros((VOCAB_SIZE, c), "float32")))
-        dst.append((name + "/CondBatchNorm/scale", (VOCAB_SIZE, c), np.ones((VOCAB_SIZE, c), "float32")))
+        dst.append((name + "/CondBatchNorm/offset", (self.K, c), np.zeros((self.K, c), "float32")))
+        dst.append((name + "/CondBatchNorm/scale", (self.K, c), np.ones((self.K, c), "float32")))
 
     # ---- one CALL of each model function of gan_resnet.py: dst = the list the variables go to, or None for a reuse=True call
     def generator(self, dst):                 # Generator, gan_resnet.py:356-371
@@ -121,34 +122,43 @@ class _Init:
 
     def projection(self, dst):                # Discriminator_projection, gan_resnet.py:414-421
         d = "Discriminator/"
-        table = self.rs.uniform(-0.08, 0.08, size=(VOCAB_SIZE, EMBEDDING_DIM)).astype("float32")     # embedding.py:29-34
+        table = self.rs.uniform(-0.08, 0.08, size=(self.K, EMBEDDING_DIM)).astype("float32")     # embedding.py:29-34
         if dst is not None:
-            dst.append((d + "Embedding.Label/embedding_map", (VOCAB_SIZE, EMBEDDING_DIM), table))
+            dst.append((d + "Embedding.Label/embedding_map", (self.K, EMBEDDING_DIM), table))
         self.linear(dst, d + "D.Embedding_y", EMBEDDING_DIM, DIM_D, True)
 
     def perm(self, dst, perm_type):           # perm_classifier, gan_resnet.py:458-483
         d = "Discriminator/"
         if perm_type == "linear":
-            self.linear(dst, d + "D.d_perm_classifier_h1", OUTPUT_DIM, VOCAB_SIZE, True)
+            self.linear(dst, d + "D.d_perm_classifier_h1", OUTPUT_DIM, self.K, True)
         elif perm_type == "2layer":
             self.linear(dst, d + "D.d_perm_classifier_h1", OUTPUT_DIM, 128, True)
-            self.linear(dst, d + "D.d_perm_classifier_h2", 128, VOCAB_SIZE, True)
+            self.linear(dst, d + "D.d_perm_classifier_h2", 128, self.K, True)
         else:
             raise ValueError('Unknown perm_type {}'.format(perm_type))
 
 
-def confusion_logits_initial(confuse_init, confuse_init_diag, rs):
-    """gan_resnet.py:499-520."""
+def check_n_classes(n_classes):
+    """The class counts the kernels take (include/rcgan_hip.h): 2 .. 1024."""
+    k = int(n_classes)
+    if k != n_classes or not 2 <= k <= L.MAX_CLASSES:
+        raise ValueError("n_classes must be an integer in [2, %d], got %r" % (L.MAX_CLASSES, n_classes))
+    return k
+
+
+def confusion_logits_initial(confuse_init, confuse_init_diag, rs, n_classes=VOCAB_SIZE):
+    """gan_resnet.py:499-520 with VOCAB_SIZE = n_classes (the reference's special case of 10 classes kept for K = 10 only)."""
+    K = n_classes
     if not confuse_init:
-        lim = np.sqrt(6.0 / (2 * VOCAB_SIZE))      # TF default get_variable initialiser: glorot_uniform
-        return rs.uniform(-lim, lim, size=(VOCAB_SIZE, VOCAB_SIZE)).astype("float32")
-    if confuse_init_diag > 0.99 and VOCAB_SIZE == 10.:
+        lim = np.sqrt(6.0 / (2 * K))      # TF default get_variable initialiser: glorot_uniform
+        return rs.uniform(-lim, lim, size=(K, K)).astype("float32")
+    if confuse_init_diag > 0.99 and K == 10.:
         aa = 7.0
     else:
-        aa = np.log(VOCAB_SIZE * confuse_init_diag / (1. - confuse_init_diag))
+        aa = np.log(K * confuse_init_diag / (1. - confuse_init_diag))
     aa = min(7.0, aa)
-    m = (0 - aa / VOCAB_SIZE) * np.ones([VOCAB_SIZE, VOCAB_SIZE], dtype=np.float32)
-    np.fill_diagonal(m, (aa - (aa / VOCAB_SIZE)))
+    m = (0 - aa / K) * np.ones([K, K], dtype=np.float32)
+    np.fill_diagonal(m, (aa - (aa / K)))
     return m
 
 
@@ -156,27 +166,29 @@ N_TOWERS = 2      # len(DEVICES): two towers even on one device (gan_resnet.py:1
 
 
 def create_variables(seed=0, algorithm="rcgan", perm_classifier=False, perm_type="linear",
-                     confuse_init=False, confuse_init_diag=0.2):
+                     confuse_init=False, confuse_init_diag=0.2, n_classes=VOCAB_SIZE):
     """-> (G specs, D specs, C specs, U dict); specs are (name, shape, initial value).
     The numpy-initialised values equal the reference's under ``np.random.seed(seed)`` bit for bit (pinned by
     tests/golden/ref_cifar_*.npz, which scripts/make_golden_reference.py produces by running the reference's own main()).  That needs
     the reference's graph-construction ORDER including the calls that create nothing: every Conv2D / Linear / embed_y call draws
     its initial values before asking for the variable, so the second tower's Generator (reuse=True, gan_resnet.py:541-546), the
     ten extra projections of 'unbiased' (:615-622) and the second Discriminator + projection of 'rcgan-u' (:654-657) consume the
-    stream in front of the variables created after them."""
+    stream in front of the variables created after them.  n_classes: the label tables, embedding map, perm-classifier outputs and
+    confusion matrix are sized by it (VOCAB_SIZE of the reference, gan_resnet.py:170)."""
     if algorithm not in ALGORITHMS:
         raise ValueError("Unknown algorithm %s" % algorithm)
-    it = _Init(seed)
+    K = check_n_classes(n_classes)
+    it = _Init(seed, K)
     if algorithm == "rcgan-u":
-        it.Cm.append(("confusion_logits", (VOCAB_SIZE, VOCAB_SIZE),
-                      confusion_logits_initial(confuse_init, confuse_init_diag, it.rs_tf)))
+        it.Cm.append(("confusion_logits", (K, K),
+                      confusion_logits_initial(confuse_init, confuse_init_diag, it.rs_tf, K)))
     it.generator(it.G)                        # tower 0 creates (gan_resnet.py:541-546) ...
     for _ in range(N_TOWERS - 1):
         it.generator(None)                    # ... the other towers reuse
     it.discriminator(it.D)                    # tower 0 of the critic cost (:584-586)
     it.projection(it.D)
     if algorithm == "unbiased":
-        for _ in range(VOCAB_SIZE):
+        for _ in range(K):
             it.projection(None)               # :615-622
     elif algorithm == "rcgan-u":
         it.discriminator(None)                # :654-657
@@ -186,9 +198,10 @@ def create_variables(seed=0, algorithm="rcgan", perm_classifier=False, perm_type
     return it.G, it.D, it.Cm, it.U
 
 
-def C_ALPHA(alpha):
-    """gan_resnet.py:106."""
-    return ((1 - alpha) / 9.0) * np.ones((10, 10)) + (alpha - (1 - alpha) / 9.0) * np.eye(10)
+def C_ALPHA(alpha, n_classes=VOCAB_SIZE):
+    """gan_resnet.py:106: symmetric label noise, alpha on the diagonal and (1 - alpha) / (K - 1) off it."""
+    K = n_classes
+    return ((1 - alpha) / float(K - 1)) * np.ones((K, K)) + (alpha - (1 - alpha) / float(K - 1)) * np.eye(K)
 
 
 FEED_COPY_KERNEL = os.environ.get("RCGAN_FEED_COPY_KERNEL", "1") == "1"
@@ -208,6 +221,11 @@ def lr_decay(iteration):
 # ------------------------------------------------------------------------------------------------------
 def _ctx():
     return Graph.current.ctx
+
+
+def _n_classes():
+    """The class count of the model whose graph is being built (CifarRCGAN sets Graph.n_classes)."""
+    return getattr(Graph.current, "n_classes", VOCAB_SIZE)
 
 
 SHORTCUT_BEFORE_UPSAMPLE = os.environ.get("RCGAN_SHORTCUT_LOW", "1") == "1"
@@ -232,11 +250,11 @@ def G_ResidualBlock(inputs, input_dim, output_dim, filter_size, name, labels, se
     with variable_scope(name + '.N1'):
         # (_defer_apply: in forward-only passes the affine + ReLU go into the consuming convolution's staged input where its kernel can
         # -- ops.BnPending: the halo-patch kernels and G.Output's; elsewhere, and under the tape, the norm is applied as before)
-        out = cond_batchnorm(name + '.N1', [0, 1, 2], inputs, labels=labels, n_labels=10, _act=L.ACT_RELU, _segments=segments, _defer_apply=True)
+        out = cond_batchnorm(name + '.N1', [0, 1, 2], inputs, labels=labels, n_labels=_n_classes(), _act=L.ACT_RELU, _segments=segments, _defer_apply=True)
     # (_bn_next: a batch norm follows -- on the big grids its statistics come out of this convolution's epilogue, ops.conv2d)
     out = UpsampleConv(out, output_dim, filter_size, name + '.Conv1', _bn_next=True)
     with variable_scope(name + '.N2'):
-        out = cond_batchnorm(name + '.N2', [0, 1, 2], out, labels=labels, n_labels=10, _act=L.ACT_RELU, _segments=segments, _defer_apply=True)
+        out = cond_batchnorm(name + '.N2', [0, 1, 2], out, labels=labels, n_labels=_n_classes(), _act=L.ACT_RELU, _segments=segments, _defer_apply=True)
     if low:
         return Conv2D(out, output_dim, output_dim, filter_size, 1, name + '.Conv2', _residual=shortcut, _residual_up=True, _bn_next=True)
     return Conv2D(out, output_dim, output_dim, filter_size, 1, name + '.Conv2', _accumulate_into=shortcut)
@@ -258,7 +276,7 @@ def Generator(n_samples, labels, noise, out=None, segments=1):
         with variable_scope('G.OutputNorm'):
             # (forward-only passes -- the critic steps' generator forwards, sampling: the affine + ReLU are applied inside G.Output's
             # launch, the normalised tensor is never written: ops.BnPending)
-            output = cond_batchnorm('G.OutputNorm', [0, 1, 2], output, labels=labels, n_labels=10, _act=L.ACT_RELU, _segments=segments,
+            output = cond_batchnorm('G.OutputNorm', [0, 1, 2], output, labels=labels, n_labels=_n_classes(), _act=L.ACT_RELU, _segments=segments,
                                     _defer_apply=True)
         output = Conv2D(output, DIM_G * 2, IMG_DIM, 3, 1, 'G.Output', he_init=False)
         output = O.act(ctx, output, L.ACT_TANH, out=out.reshape(output.shape) if out is not None else None)
@@ -336,7 +354,7 @@ def Discriminator(inputs, labels, update_collection=None, _head=True):
 def Discriminator_projection(labels, update_collection=None):
     """gan_resnet.py:414-421."""
     with variable_scope("Discriminator"):
-        e = embed_y(labels, VOCAB_SIZE, EMBEDDING_DIM)
+        e = embed_y(labels, _n_classes(), EMBEDDING_DIM)
         return Linear(e, EMBEDDING_DIM, DIM_D, 'D.Embedding_y', spectral_normed=True,
                       update_collection=update_collection, biases=True)
 
@@ -373,10 +391,10 @@ def perm_classifier(x, perm_type='linear'):
     with variable_scope("Discriminator"):
         x = O.cast(ctx, O.reshape(ctx, x, (-1, OUTPUT_DIM)), L.F32)
         if perm_type == 'linear':
-            return Linear(x, OUTPUT_DIM, VOCAB_SIZE, 'D.d_perm_classifier_h1', spectral_normed=True, biases=True)
+            return Linear(x, OUTPUT_DIM, _n_classes(), 'D.d_perm_classifier_h1', spectral_normed=True, biases=True)
         elif perm_type == '2layer':
             h = Linear(x, OUTPUT_DIM, 128, 'D.d_perm_classifier_h1', spectral_normed=True, biases=True)
-            return Linear(h, 128, VOCAB_SIZE, 'D.d_perm_classifier_h2', spectral_normed=True, biases=True)
+            return Linear(h, 128, _n_classes(), 'D.d_perm_classifier_h2', spectral_normed=True, biases=True)
         raise ValueError('Unknown perm_type {}'.format(perm_type))
 
 
@@ -392,9 +410,11 @@ class CifarRCGAN:
                  confuse_init=False, confuse_init_diag=0.2, confuse_multiplier=1.0, confuse_lr_decay=False,
                  device=0, use_graphs=True, device_rng=True, arena_bytes=None, world_size=1, rank=0,
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
-                 grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest"):
+                 grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # class count K (2 .. 1024): checked before any context exists; K > 16 takes the kernels' wide routes
+        self.K = check_n_classes(n_classes)
         # "high": the fp32 gather GEMMs on split-bf16 matrix cores (rcgan_set_f32_matmul_precision), on every context of the engine
         self.f32_matmul_precision = check_f32_matmul_precision(f32_matmul_precision, dtype)
         self.alg, self.alpha, self.B, self.lr = algorithm, alpha, int(batch_size), lr
@@ -430,7 +450,7 @@ class CifarRCGAN:
             self.ls_state = None
             ctx.check(ctx.lib.rcgan_set_grad_scale(ctx.h, self.loss_scale, None))
         if variables is None:
-            variables = create_variables(seed, algorithm, perm_classifier, perm_type, confuse_init, confuse_init_diag)
+            variables = create_variables(seed, algorithm, perm_classifier, perm_type, confuse_init, confuse_init_diag, self.K)
         gs, ds, cs, U = variables
         self.PG, self.PD = ParamGroup(ctx, gs), ParamGroup(ctx, ds, sn_scratch=True)
         self.PC = ParamGroup(ctx, cs) if cs else None
@@ -441,6 +461,7 @@ class CifarRCGAN:
             ctx.view(t).copy_(torch.from_numpy(np.ascontiguousarray(v.reshape(-1))))
             self.state[k] = t
         self.graph = Graph(ctx, self.groups, self.state)
+        self.graph.n_classes = self.K
         # Data parallel (world_size > 1; gan_resnet.py:529-546,697,786): the gradient slabs are all-reduced INSIDE the C ABI
         # (rcgan_allreduce_sum*, RCCL over xGMI) and inside the step's captured graph; the optimiser launch is part of the same graph.
         #   comm: None -> RCCL (one process per GPU, dp.init_comm);  "stub" -> the single-process test double (every rank holds what
@@ -504,7 +525,7 @@ class CifarRCGAN:
         # G-step batch over with ONE copy (set_feed); the named views below alias the slabs (set_inputs still works).
         self.feed_layout = {
             "d": [("images", (B, OUTPUT_DIM), i32), ("labels", (B,), i32), ("labels_random", (B,), i32), ("labels_biased", (B,), i32),
-                  ("inv_weights", (B, VOCAB_SIZE), f32), ("labels_all", (2 * B,), i32)],
+                  ("inv_weights", (B, self.K), f32), ("labels_all", (2 * B,), i32)],
             "g": [("labels_random_G", (2 * B,), i32), ("labels_biased_G", (2 * B,), i32)],
             # generator labels of the N_CRITIC critic steps of one iteration (prepare_critic_fakes)
             "gf": [("labels_random_all", (N_CRITIC * B,), i32)]}
@@ -532,9 +553,9 @@ class CifarRCGAN:
         self.critic_graph = os.environ.get("RCGAN_CRITIC_GRAPH", "1") == "1"
         self.inp.update(noise=P((B, OUTPUT_DIM), f32), z=P((B, Z_DIM), act), z_G=P((2 * B, Z_DIM), act),
                         z_all=P((N_CRITIC * B, Z_DIM), act),
-                        arange=P((VOCAB_SIZE,), i32), C_const=P((VOCAB_SIZE, VOCAB_SIZE), f32))
-        ctx.view(self.inp["arange"]).copy_(torch.arange(VOCAB_SIZE, dtype=torch.int32))
-        ctx.view(self.inp["C_const"]).copy_(torch.from_numpy(C_ALPHA(alpha).astype(np.float32)))
+                        arange=P((self.K,), i32), C_const=P((self.K, self.K), f32))
+        ctx.view(self.inp["arange"]).copy_(torch.arange(self.K, dtype=torch.int32))
+        ctx.view(self.inp["C_const"]).copy_(torch.from_numpy(C_ALPHA(alpha, self.K).astype(np.float32)))
         # the critic steps' generator forwards evaluated as one batch (prepare_critic_fakes): fakes of all N_CRITIC steps,
         # and the discriminator input [real ; fake] of a step at a fixed address the fake rows are copied into
         self.fakes_all = P((N_CRITIC * B, OUTPUT_DIM), act)
@@ -573,7 +594,7 @@ class CifarRCGAN:
         self._slice_mirror = 0
         self.seed = seed
         self._graphs = {}
-        # inspection hook: a persistent fp32 [2B, 10] buffer the fused projection head also writes its logits to (logit of the
+        # inspection hook: a persistent fp32 [2B, K] buffer the fused projection head also writes its logits to (logit of the
         # sample's label, or of every label where the loss weights all of them); None in production.  Set before the first step.
         self.head_logits = None
         self.iteration = 0
@@ -692,7 +713,9 @@ class CifarRCGAN:
         # the head computes them in a launch of its own, in the middle of the step's dependency chain)
         g, embed = self.graph, None
         g.head_E = None
-        if self.fused_head and self.PD in which and head_update is not False and os.environ.get("RCGAN_HEAD_EMBED_RIDE", "1") == "1":
+        # (up to LABELS_NARROW classes: the rider's LDS holds E; a model of more classes computes E inside the head's launches)
+        if self.fused_head and self.PD in which and head_update is not False and self.K <= L.LABELS_NARROW and \
+                os.environ.get("RCGAN_HEAD_EMBED_RIDE", "1") == "1":
             _, _, table, w_e, b_e = _head_weights(head_update)
             E = self.ctx.empty((table.shape[0], w_e.param.shape[-1]), L.F32)
             embed = (table, w_e, b_e, E)
@@ -1268,6 +1291,10 @@ class CifarRCGAN:
         return out
 
     def load_state_dict(self, sd):
+        # a checkpoint of another class count would fail deep inside a table copy: name both counts instead
+        key = "Discriminator/Embedding.Label/embedding_map"
+        if key in sd and np.asarray(sd[key]).shape[0] != self.K:
+            raise ValueError("checkpoint has %d classes, this model has %d (n_classes)" % (np.asarray(sd[key]).shape[0], self.K))
         self._fakes_left = 0
         if self.overlap_gf:
             self.ctx2.sync()                 # (host-side writes to the parameters follow)
@@ -1303,11 +1330,11 @@ class CifarRCGAN:
         ctx.sync()
 
     def confusion_matrix_value(self):
-        """The confusion matrix the losses use, as a host array [10,10]: softmax of the learned logits (rcgan-u) or the
+        """The confusion matrix the losses use, as a host array [K, K]: softmax of the learned logits (rcgan-u) or the
         fixed one-coin matrix (gan_resnet.py:499-524)."""
         ctx = self.ctx
         if self.PC is None:
-            return ctx.download(self.inp["C_const"]).reshape(VOCAB_SIZE, VOCAB_SIZE)
+            return ctx.download(self.inp["C_const"]).reshape(self.K, self.K)
         logits = self.PC.get("confusion_logits").astype(np.float64)
         e = np.exp(logits - logits.max(axis=1, keepdims=True))
         return (e / e.sum(axis=1, keepdims=True)).astype(np.float32)

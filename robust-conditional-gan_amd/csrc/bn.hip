@@ -1047,6 +1047,164 @@ int bn_tile_stats_finish_launch(rcgan_ctx* ctx, const float* part, int c, int ns
   return RCGAN_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Conditional backward for MORE than MAX_LABELS classes (CIFAR-100: 100 or 20, 1000-class sets; up to BN_MAX_LABELS_WIDE).  The
+// narrow paths keep per-label accumulators in registers or LDS; here nothing scales with the class count:
+//   1. bn_sample_partial_kernel: one row group per sample -> partial[s][0][c] = sum dy', partial[s][1][c] = sum dy' * xhat
+//   2. bn_bwd_class_kernel: workgroup row l < K walks the samples in index order and adds, in fp64, the partials of those whose
+//      label is l -> dgamma[l] / dbeta[l] (an absent class gets exactly 0, or is left untouched under `accumulate`); row K
+//      forms s1 = sum_s gamma[l_s] * partial[s][0], s2 likewise (fp64, sample order) and the dx constants PQ / s12.
+//   3. the existing apply kernels (gamma[label] read per row, no K-sized table).
+// No atomics: every sum has a fixed order, so results are bit-reproducible (graph replay).
+// ------------------------------------------------------------------------------------------------
+#define BN_MAX_LABELS_WIDE 1024
+
+// block = 32 channel chunks (256 channels) x 8 row lanes; grid = (ceil(chunks / 32), n).  beta (optional): ReLU / leaky-ReLU
+// mask recomputed from x with the forward's arithmetic (as bn_fused_reduce_kernel), y is then not read.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_sample_partial_kernel(int rows_per_sample, int c, const T* x, const T* y, const T* dy,
+                                                                const int32_t* labels, const float* gamma, const float* beta,
+                                                                const float* mean, const float* rstd, int act, float* partial) {
+  __shared__ float red[2][8][256];
+  const int chunk = blockIdx.x * 32 + (threadIdx.x & 31);
+  const int rl = threadIdx.x >> 5;
+  const bool on = chunk * 8 < c;
+  const long rb = (long)blockIdx.y * rows_per_sample, re = rb + rows_per_sample;
+  float s1[8], s2[8], mu[8], rs[8], ainv[8], ac0[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { s1[j] = 0.f; s2[j] = 0.f; }
+  if (on) {
+    ld8(mean + chunk * 8, mu); ld8(rstd + chunk * 8, rs);
+    if (beta) {
+      const long lo = (long)labels[blockIdx.y] * c + chunk * 8;
+      float gm8[8], bt8[8];
+      ld8(gamma + lo, gm8); ld8(beta + lo, bt8);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { ainv[j] = rs[j] * gm8[j]; ac0[j] = bn_c0(mu[j], ainv[j], bt8[j]); }
+    }
+#pragma unroll 2
+    for (long r = rb + rl; r < re; r += 8) {
+      const long off = r * c + chunk * 8;
+      float xv[8], gv[8];
+      ld8(x + off, xv);
+      ld8(dy + off, gv);
+      if (beta) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gv[j] *= act_grad(act, bn_stored<T>(bn_pre(xv[j], ainv[j], ac0[j])));
+      } else if (act != RCGAN_ACT_NONE) {
+        float yv[8];
+        ld8(y + off, yv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) gv[j] *= act_grad(act, yv[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { s1[j] += gv[j]; s2[j] += gv[j] * (xv[j] - mu[j]) * rs[j]; }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    red[0][rl][(threadIdx.x & 31) * 8 + j] = s1[j];
+    red[1][rl][(threadIdx.x & 31) * 8 + j] = s2[j];
+  }
+  __syncthreads();
+  const int col = blockIdx.x * 256 + threadIdx.x;
+  if (col < c) {
+    float a = 0.f, b = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) { a += red[0][q][threadIdx.x]; b += red[1][q][threadIdx.x]; }
+    partial[((long)blockIdx.y * 2 + 0) * c + col] = a;
+    partial[((long)blockIdx.y * 2 + 1) * c + col] = b;
+  }
+}
+
+// grid (ceil(c / 256), K + 1) x 256 threads: a thread per channel; the labels pass through LDS 256 at a time
+__global__ __launch_bounds__(256) void bn_bwd_class_kernel(int n, int c, int n_labels, long rows, const int32_t* labels, const float* gamma,
+                                                           const float* partial, const float* mean, const float* rstd, float* dgamma,
+                                                           float* dbeta, int accumulate, float* s12, float* PQ) {
+  __shared__ int lab_s[256];
+  const int t = threadIdx.x, ch = blockIdx.x * 256 + t, l = blockIdx.y;
+  const bool totals = l == n_labels;
+  double d1 = 0.0, d2 = 0.0;
+  int cnt = 0;
+  for (int s0 = 0; s0 < n; s0 += 256) {
+    __syncthreads();
+    if (s0 + t < n) lab_s[t] = labels[s0 + t];
+    __syncthreads();
+    const int m = min(256, n - s0);
+    if (ch >= c) continue;
+    for (int k = 0; k < m; ++k) {
+      const int ls = lab_s[k];
+      if (ls < 0 || ls >= n_labels || (!totals && ls != l)) continue;
+      const float* pp = partial + (long)(s0 + k) * 2 * c + ch;
+      if (totals) {
+        const double gm = (double)gamma[(long)ls * c + ch];
+        d1 += gm * (double)pp[0]; d2 += gm * (double)pp[c];
+      } else {
+        d1 += (double)pp[0]; d2 += (double)pp[c];
+        ++cnt;
+      }
+    }
+  }
+  if (ch >= c) return;
+  if (!totals) {
+    if (cnt == 0 && accumulate) return;       // absent class: untouched
+    const long o = (long)l * c + ch;
+    float og = (float)d2, ob = (float)d1;
+    if (accumulate) { og += dgamma[o]; ob += dbeta[o]; }
+    dgamma[o] = og; dbeta[o] = ob;
+    return;
+  }
+  s12[ch] = (float)d1;
+  s12[c + ch] = (float)d2;
+  // dx = A*g + P*x + Q, A = rstd*gamma[label] (read per row by the apply kernel), P = -rstd^2*s2/M, Q = -P*mean - rstd*s1/M
+  const float invM = 1.f / (float)rows;
+  const float r = rstd[ch];
+  const float p = -r * r * (float)d2 * invM;
+  PQ[ch] = p;
+  PQ[c + ch] = -p * mean[ch] - r * (float)d1 * invM;
+}
+
+// workspace: partial [n][2][c] | s12 [2][c] | PQ [2][c] floats
+static int bn_bwd_wide(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x, const void* y,
+                       const void* dy, const int32_t* labels, const float* gamma, const float* beta_m, const float* mean, const float* rstd,
+                       int act, void* dx, int accumulate_dx, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes) {
+  RC_REQUIRE(ctx, n >= 1 && rows_per_sample >= 1 && c >= 1, "bad shape n %d rows %d c %d", n, rows_per_sample, c);
+  RC_REQUIRE(ctx, dgamma && dbeta, "the conditional backward needs dgamma and dbeta");
+  const long rows = (long)n * rows_per_sample;
+  const size_t need = ((size_t)n * 2 * c + 4 * (size_t)c) * sizeof(float);
+  if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
+  float* partial = (float*)ws;
+  float* s12 = partial + (size_t)n * 2 * c;
+  float* PQ = s12 + 2 * (size_t)c;
+  const bool fused = bn_fused_ok(c);
+  if (c % 8 == 0) {
+    const float* bm = fused ? beta_m : nullptr;        // the mask from x wherever the apply below also takes it
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_sample_partial_kernel<T>, dim3(cdiv(c / 8, 32), n), dim3(256), 0, ctx->stream,
+                                                     rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, bm, mean,
+                                                     rstd, act, partial));
+  } else {
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_partial_kernel<T, 1>), dim3(cdiv(c, 64), n), dim3(256), 0, ctx->stream, rows, c,
+                                                     (long)rows_per_sample, (const T*)x, (const T*)y, (const T*)dy, mean, rstd, act, partial));
+  }
+  RC_LAUNCH_CHECK(ctx);
+  hipLaunchKernelGGL(bn_bwd_class_kernel, dim3(cdiv(c, 256), n_labels + 1), dim3(256), 0, ctx->stream, n, c, n_labels, rows, labels, gamma,
+                     (const float*)partial, mean, rstd, dgamma, dbeta, accumulate, s12, PQ);
+  RC_LAUNCH_CHECK(ctx);
+  if (fused) {
+    const long nchunks = rows * c / 8;
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<T>, dim3(apply_grid_fused(nchunks, c)), dim3(256), 0, ctx->stream,
+                                                     nchunks, rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, rstd,
+                                                     (const float*)PQ, act, (T*)dx, accumulate_dx, beta_m, mean));
+  } else {
+    const long total = rows * c;
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_grid2(total)), dim3(256), 0, ctx->stream, total, rows,
+                                                     rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, mean,
+                                                     rstd, (const float*)s12, act, (T*)dx, accumulate_dx));
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
 extern "C" {
 
 size_t rcgan_bn_workspace_bytes(int rows, int c) {
@@ -1056,6 +1214,12 @@ size_t rcgan_bn_workspace_bytes(int rows, int c) {
   if (ng < 4096) ng = 4096;   // per-sample grouping (n <= 4096 samples)
   ng *= 2;
   return (size_t)(ng * 2 * (long)c + 4 * (long)c + 2 * MAX_LABELS * (long)c) * sizeof(float) + 256;
+}
+
+size_t rcgan_bn_workspace_bytes_labels(int rows, int c, int n_labels) {
+  // the rule above with the per-label staging of the table paths ([2][n_labels][c]) sized for n_labels instead of MAX_LABELS
+  const size_t base = rcgan_bn_workspace_bytes(rows, c);
+  return n_labels > MAX_LABELS ? base + (size_t)2 * (n_labels - MAX_LABELS) * c * sizeof(float) : base;
 }
 
 int rcgan_bn_stats(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, float eps, float* mean, float* rstd,
@@ -1212,8 +1376,11 @@ int rcgan_bn_bwd2(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_label
                   int act, void* dx, int accumulate_dx, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes) {
   // with beta, ReLU / leaky ReLU masks are recomputed from x on the fused paths (two instead of three tensor reads per pass)
   const float* beta_m = (beta && (act == RCGAN_ACT_RELU || act == RCGAN_ACT_LRELU)) ? beta : nullptr;
-  RC_REQUIRE(ctx, n_labels >= 1 && n_labels <= MAX_LABELS, "n_labels %d", n_labels);
+  RC_REQUIRE(ctx, n_labels >= 1 && n_labels <= BN_MAX_LABELS_WIDE, "n_labels %d (1 .. %d)", n_labels, BN_MAX_LABELS_WIDE);
   RC_REQUIRE(ctx, labels != nullptr || n_labels == 1, "labels required for n_labels > 1");
+  if (n_labels > MAX_LABELS)
+    return bn_bwd_wide(ctx, n, rows_per_sample, c, n_labels, dtype, x, y, dy, labels, gamma, beta_m, mean, rstd, act, dx, accumulate_dx,
+                       dgamma, dbeta, accumulate, ws, ws_bytes);
   long rows = (long)n * rows_per_sample;
   long rpg;
   int ng;

@@ -390,6 +390,173 @@ __global__ __launch_bounds__(256) void head_wgrad_kernel(HeadArgs a, const float
   head_wgrad_body(a, dEg, blockIdx.x, hs);
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// The head for v > HEAD_MAX_V labels (CIFAR-100, 1000-class sets; up to HEAD_MAX_V_WIDE): the same values without anything
+// sized by v in LDS or registers, and without riders (its launches follow one another on the stream):
+//   embed : E[l][j] = (table[l] @ W_e)[j] / sigma_e + b_e[j]      a thread per element, k in order
+//   logit : a wavefront per sample.  One-hot part: the single logit of E[label].  Weight-row part: every label, 64 at a time
+//           (lane = label), then dfeat += sum_l dlogit[l] E[l] in label order from the 64 values in LDS.  Per-sample loss rows.
+//   dE    : dE[l][j] = sum_s dlogit[s][l] feat[s][j] (row v: the psi column -> dw_out), a thread per element, s in order;
+//           one more workgroup adds db_out and the loss (sample order)
+//   wgrad : dW_e += table^T dE,  dtable += dE W_e^T / sigma_e,  dw_out, db_e    a thread per element
+// Every sum has a fixed order: bit-identical on replay.
+// ---------------------------------------------------------------------------------------------------------
+#define HEAD_MAX_V_WIDE 1024
+
+__global__ __launch_bounds__(256) void head_wide_embed_kernel(int v, int e, int d, const float* table, const float* w_e, const float* sigma,
+                                                              const float* b, float* E) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)v * d) return;
+  const int l = (int)(i / d), j = (int)(i - (long)l * d);
+  const float* tl = table + (long)l * e;
+  float acc = 0.f;
+  for (int k = 0; k < e; ++k) acc += tl[k] * w_e[(long)k * d + j];
+  E[i] = acc * (sigma ? 1.f / sigma[0] : 1.f) + (b ? b[j] : 0.f);
+}
+
+__global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const float* E, float* dlg, float* lossrow) {
+  __shared__ float fs[4][HEAD_MAX_D];           // the wavefront's features
+  __shared__ float gl[4][64];                   // dlogit of the current 64 labels
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int n = a.n, d = a.d, v = a.v, vp = v + 1;
+  const int s = blockIdx.x * 4 + wave;
+  const bool on = s < n;
+  const int p = (on && s >= a.part[0].rows) ? 1 : 0;
+  const HeadPart& P = a.part[p];
+  const int sr = p ? s - a.part[0].rows : s;
+  const float inv_rows = 1.f / (float)P.rows;
+  const float gw = a.weight * grad_scale_of(a.gs_host, a.gs_dev);
+  const float inv_so = a.sigma_out ? 1.f / a.sigma_out[0] : 1.f;
+  const float bo = a.b_out ? a.b_out[0] : 0.f;
+  float f[HEAD_MAX_D / 64], wo[HEAD_MAX_D / 64], df[HEAD_MAX_D / 64];
+  float ps = 0.f;
+#pragma unroll
+  for (int q = 0; q < HEAD_MAX_D / 64; ++q) {
+    const int j = lane + q * 64;
+    f[q] = (on && j < d) ? a.feat[(long)s * d + j] : 0.f;
+    wo[q] = j < d ? a.w_out[j] * inv_so : 0.f;
+    fs[wave][j] = f[q];
+    ps += f[q] * wo[q];
+    df[q] = 0.f;
+  }
+  ps = wave_sum(ps) + bo;
+  float lacc = 0.f, dsl = 0.f;                  // this lane's share of the sample's loss and of sum_l dlogit[l]
+  const bool onehot = on && P.labels != nullptr, rowsw = on && P.wts != nullptr;
+  if (onehot) {
+    const int lab = P.labels[sr];
+    const bool ok = lab >= 0 && lab < v;
+    float dot = 0.f;
+#pragma unroll
+    for (int q = 0; q < HEAD_MAX_D / 64; ++q) { const int j = lane + q * 64; dot += (ok && j < d) ? f[q] * E[(long)lab * d + j] : 0.f; }
+    const float x = wave_sum(dot) + ps;
+    float tt, dd;
+    loss_term(P.kind, x, &tt, &dd);
+    const float g = ok ? gw * dd * inv_rows : 0.f;
+    if (ok) {
+#pragma unroll
+      for (int q = 0; q < HEAD_MAX_D / 64; ++q) { const int j = lane + q * 64; df[q] += j < d ? g * E[(long)lab * d + j] : 0.f; }
+    }
+    if (lane == 0 && ok) { lacc = tt * inv_rows; dsl = g; }
+    for (int l = lane; l < v; l += 64) {
+      dlg[(long)s * vp + l] = l == lab ? g : 0.f;
+      if (a.logits) a.logits[(long)s * v + l] = l == lab ? x : 0.f;
+    }
+  }
+  __syncthreads();                              // fs
+  for (int c0 = 0; c0 < v; c0 += 64) {         // (workgroup-uniform trip count)
+    const int l = c0 + lane;
+    float g = 0.f;
+    if (rowsw && l < v) {
+      const float* El = E + (long)l * d;
+      float dot = 0.f;
+#pragma unroll 8
+      for (int j = 0; j < d; ++j) dot += fs[wave][j] * El[j];
+      const float x = dot + ps;
+      float tt, dd;
+      loss_term(P.kind, x, &tt, &dd);
+      const float wf = P.wts[(long)sr * v + l] * inv_rows;
+      lacc += tt * wf;
+      g = gw * dd * wf;
+      dsl += g;
+      if (P.dwts) P.dwts[(long)sr * v + l] = gw * tt * inv_rows;
+      if (a.logits) a.logits[(long)s * v + l] = x;
+      dlg[(long)s * vp + l] = g;
+    }
+    gl[wave][lane] = g;
+    __syncthreads();
+    if (rowsw) {
+      const int m = min(64, v - c0);
+      for (int k = 0; k < m; ++k) {
+        const float gk = gl[wave][k];
+        const float* Ek = E + (long)(c0 + k) * d;
+#pragma unroll
+        for (int q = 0; q < HEAD_MAX_D / 64; ++q) { const int j = lane + q * 64; df[q] += j < d ? gk * Ek[j] : 0.f; }
+      }
+    }
+    __syncthreads();
+  }
+  if (!on) return;
+  const float dsum = wave_sum(dsl);
+  lacc = wave_sum(lacc);
+#pragma unroll
+  for (int q = 0; q < HEAD_MAX_D / 64; ++q) df[q] += dsum * wo[q];
+  if (a.dfeat) {
+#pragma unroll
+    for (int q = 0; q < HEAD_MAX_D / 64; ++q) { const int j = lane + q * 64; if (j < d) a.dfeat[(long)s * d + j] = df[q]; }
+  }
+  if (lane == 0) { dlg[(long)s * vp + v] = dsum; lossrow[s] = lacc; }
+}
+
+// dE [(v+1)][d] over cdiv((v+1)*d, 256) workgroups (0 when no parameter gradient is wanted) and one last workgroup for db_out / the loss
+__global__ __launch_bounds__(256) void head_wide_de_kernel(int n, int d, int v, const float* dlg, const float* feat, float* dE, float* db_out,
+                                                           const float* lossrow, float* loss_acc, float weight) {
+  const int vp = v + 1;
+  if (blockIdx.x == gridDim.x - 1) {
+    if (threadIdx.x == 0) {
+      float sb = 0.f, sl = 0.f;
+      for (int s = 0; s < n; ++s) { sb += dlg[(long)s * vp + v]; sl += lossrow[s]; }
+      if (db_out) db_out[0] += sb;
+      if (loss_acc) *loss_acc += weight * sl;
+    }
+    return;
+  }
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)vp * d) return;
+  const int l = (int)(i / d), j = (int)(i - (long)l * d);
+  float acc = 0.f;
+  for (int s = 0; s < n; ++s) acc += dlg[(long)s * vp + l] * feat[(long)s * d + j];
+  dE[i] = acc;
+}
+
+// items: [0, ed*d) dW_e[k][j];  [ed*d, ed*d + v*ed) dtable[l][k];  then d items for dw_out[j] and db_e[j]
+__global__ __launch_bounds__(256) void head_wide_wgrad_kernel(HeadArgs a, const float* dE) {
+  const int d = a.d, v = a.v, ed = a.e_dim;
+  const long n_w = (long)ed * d, n_t = (long)v * ed, total = n_w + n_t + d;
+  const float inv_se = a.sigma_e ? 1.f / a.sigma_e[0] : 1.f;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    if (i < n_w) {
+      if (!a.dw_e) continue;
+      const int k = (int)(i / d), j = (int)(i - (long)k * d);
+      float acc = 0.f;
+      for (int l = 0; l < v; ++l) acc += a.table[(long)l * ed + k] * dE[(long)l * d + j];
+      a.dw_e[i] += acc;
+    } else if (i < n_w + n_t) {
+      if (!a.dtable) continue;
+      const long o = i - n_w;
+      const int l = (int)(o / ed), k = (int)(o - (long)l * ed);
+      const float* wk = a.w_e + (long)k * d;
+      const float* dl = dE + (long)l * d;
+      float dot = 0.f;
+      for (int j = 0; j < d; ++j) dot += wk[j] * dl[j];
+      a.dtable[o] += dot * inv_se;
+    } else {
+      const int j = (int)(i - n_w - n_t);
+      if (a.dw_out) a.dw_out[j] += dE[(long)v * d + j];
+      if (a.db_e) { float tot = 0.f; for (int l = 0; l < v; ++l) tot += dE[(long)l * d + j]; a.db_e[j] += tot; }
+    }
+  }
+}
+
 static inline int g1(long total) {
   long b = (total + 255) / 256;
   if (b > 4096) b = 4096;
@@ -533,12 +700,58 @@ bool head_take_wgrad(rcgan_ctx* ctx, HeadWgradRider* out) {
   return true;
 }
 
+// v > HEAD_MAX_V: the unridden launches above; defer_ws is ignored (the parameter gradients are complete when the call returns).
+// ws: E [v][d] | dlogit [n][v+1] | dE [v+1][d] | loss rows [n] | (pooling inside the head) dfeat [n][d] floats
+static int head_wide(rcgan_ctx* ctx, HeadArgs& a, const rcgan_head_desc* hd, void* ws, size_t ws_bytes) {
+  const int vp = a.v + 1;
+  const bool pool_grad = a.x && a.dx;
+  const size_t need = ((size_t)a.v * a.d + (size_t)a.n * vp + (size_t)vp * a.d + a.n + (pool_grad ? (size_t)a.n * a.d : 0)) * sizeof(float);
+  if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
+  float* Eg = (float*)ws;
+  float* dlg = Eg + (size_t)a.v * a.d;
+  float* dEg = dlg + (size_t)a.n * vp;
+  float* lossrow = dEg + (size_t)vp * a.d;
+  if (ctx->head_stage) {            // an earlier head's deferred launches were never carried: they go first
+    int rc = rcgan_head_flush(ctx);
+    if (rc) return rc;
+  }
+  if (a.x) {                        // pool first (the features are this call's output), scatter the gradient back last
+    int rc = rcgan_act_meanhw_fwd(ctx, a.n, a.hw, a.d, hd->x_dtype, a.act, a.x, a.feat_out);
+    if (rc) return rc;
+    if (pool_grad && !a.dfeat) a.dfeat = lossrow + a.n;
+  }
+  if (hd->E_pre) {
+    Eg = (float*)hd->E_pre;
+  } else {
+    hipLaunchKernelGGL(head_wide_embed_kernel, dim3(cdiv((long)a.v * a.d, 256)), dim3(256), 0, ctx->stream, a.v, a.e_dim, a.d, a.table, a.w_e,
+                       a.sigma_e, a.b_e, Eg);
+    RC_LAUNCH_CHECK(ctx);
+  }
+  hipLaunchKernelGGL(head_wide_logit_kernel, dim3(cdiv(a.n, 4)), dim3(256), 0, ctx->stream, a, (const float*)Eg, dlg, lossrow);
+  RC_LAUNCH_CHECK(ctx);
+  const bool want_params = a.dw_out || a.db_out || a.dtable || a.dw_e || a.db_e;
+  const int nde = want_params ? (int)cdiv((long)vp * a.d, 256) : 0;
+  hipLaunchKernelGGL(head_wide_de_kernel, dim3(nde + 1), dim3(256), 0, ctx->stream, a.n, a.d, a.v, (const float*)dlg, (const float*)a.feat, dEg,
+                     a.db_out, (const float*)lossrow, a.loss_acc, a.weight);
+  RC_LAUNCH_CHECK(ctx);
+  if (want_params && (a.dw_out || a.dtable || a.dw_e || a.db_e)) {
+    hipLaunchKernelGGL(head_wide_wgrad_kernel, dim3(g1((long)a.e_dim * a.d + (long)a.v * a.e_dim + a.d)), dim3(256), 0, ctx->stream, a,
+                       (const float*)dEg);
+    RC_LAUNCH_CHECK(ctx);
+  }
+  if (pool_grad) {
+    int rc = rcgan_act_meanhw_bwd(ctx, a.n, a.hw, a.d, hd->x_dtype, a.act, a.x, a.dfeat, a.dx);
+    if (rc) return rc;
+  }
+  return RCGAN_OK;
+}
+
 int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const float* feat, const float* w_out, const float* sigma_out,
                             const float* b_out, const float* table, const float* w_e, const float* sigma_e, const float* b_e,
                             float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
                             float* db_e, void* ws, size_t ws_bytes) {
   RC_REQUIRE(ctx, hd && feat && w_out && table && w_e, "null argument");
-  RC_REQUIRE(ctx, hd->n >= 1 && hd->n <= HEAD_MAX_N && hd->d >= 1 && hd->d <= HEAD_MAX_D && hd->v >= 1 && hd->v <= HEAD_MAX_V && hd->e_dim >= 1,
+  RC_REQUIRE(ctx, hd->n >= 1 && hd->n <= HEAD_MAX_N && hd->d >= 1 && hd->d <= HEAD_MAX_D && hd->v >= 1 && hd->v <= HEAD_MAX_V_WIDE && hd->e_dim >= 1,
              "head shape n %d d %d v %d e %d", hd->n, hd->d, hd->v, hd->e_dim);
   RC_REQUIRE(ctx, hd->rows_a >= 1 && hd->rows_a <= hd->n, "rows_a %d of %d", hd->rows_a, hd->n);
   HeadArgs a;
@@ -559,6 +772,7 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
     RC_REQUIRE(ctx, hd->x_dtype == RCGAN_F32 || hd->x_dtype == RCGAN_H16, "bad x dtype");
     a.feat_out = (float*)feat;      // the features become an OUTPUT (read by the parameter-gradient kernels)
   }
+  if (a.v > HEAD_MAX_V) return head_wide(ctx, a, hd, ws, ws_bytes);
   const int vp = a.v + 1;
   const size_t need = ((size_t)a.v * a.d + (size_t)a.n * vp + (size_t)vp * a.d + 256) * sizeof(float);
   if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);

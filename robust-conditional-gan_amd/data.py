@@ -10,9 +10,10 @@ import pickle
 import numpy as np
 
 
-def C_ALPHA(alpha):
-    """One-coin confusion matrix (gan_resnet.py:106)."""
-    return ((1 - alpha) / 9.0) * np.ones((10, 10)) + (alpha - (1 - alpha) / 9.0) * np.eye(10)
+def C_ALPHA(alpha, n_classes=10):
+    """One-coin confusion matrix (gan_resnet.py:106): alpha on the diagonal, (1 - alpha) / (K - 1) off it."""
+    K = n_classes
+    return ((1 - alpha) / float(K - 1)) * np.ones((K, K)) + (alpha - (1 - alpha) / float(K - 1)) * np.eye(K)
 
 
 def unpickle(file):
@@ -21,14 +22,17 @@ def unpickle(file):
     return d[b'data'], d[b'labels']
 
 
-def corrupt_labels(labels, C, rng=np.random):
+def corrupt_labels(labels, C, rng=np.random, n_classes=None):
     """cifar10.py:29-41: the noisy channel applied to the real labels, the uniformly random generator labels,
     their channel-corrupted version and the C^-1 rows for the unbiased loss.  Draw order is the reference's:
-    randint(10, 50000) first, then per sample multinomial(C[label]) and multinomial(C[random])."""
+    randint(K, 50000) first, then per sample multinomial(C[label]) and multinomial(C[random]).  K = n_classes, or C's size."""
+    K = int(n_classes) if n_classes is not None else len(C)
+    if np.shape(C) != (K, K):
+        raise ValueError("C has shape %s, expected (%d, %d)" % (np.shape(C), K, K))
     labels = np.array(labels)
-    labels_random = rng.randint(10, size=50000)
+    labels_random = rng.randint(K, size=50000)
     labels_biased = np.zeros((50000,))
-    labels_inv_weights = np.zeros((50000, 10))
+    labels_inv_weights = np.zeros((50000, K))
     C_inv = np.linalg.inv(C)
     for i in range(len(labels)):
         labels[i] = np.flatnonzero(rng.multinomial(1, C[labels[i], :]))[0]
@@ -38,7 +42,7 @@ def corrupt_labels(labels, C, rng=np.random):
 
 
 def cifar_generator(images, labels, batch_size, C, rng=np.random):
-    """cifar10.py:19-45 on in-memory arrays: fixed order, no shuffling, tail dropped."""
+    """cifar10.py:19-45 on in-memory arrays: fixed order, no shuffling, tail dropped.  The class count is C's size."""
     labels, labels_random, labels_biased, labels_inv_weights = corrupt_labels(labels, C, rng)
 
     def get_epoch():
@@ -62,14 +66,33 @@ def load(batch_size, data_dir, C, rng=np.random):
     return cifar_generator(tx, ty, batch_size, C, rng), cifar_generator(vx, vy, batch_size, C, rng)
 
 
-def class_templates():
-    """Ten fixed low-frequency colour patterns [10,3,32,32] (sums of three separable cosines per channel, frequencies 0..2):
+def unpickle100(file, coarse=False):
+    """A cifar-100-python pickle ("train" / "test"): images [n,3072] and the 100 fine labels, or the 20 coarse ones."""
+    with open(file, 'rb') as fo:
+        d = pickle.load(fo, encoding='bytes')
+    return d[b'data'], d[b'coarse_labels' if coarse else b'fine_labels']
+
+
+def load100(batch_size, data_dir, C, rng=np.random, coarse=False):
+    """``load`` for CIFAR-100 (data_dir = the cifar-100-python directory): 100 fine classes, or 20 coarse ones with coarse=True.
+    C is the [K, K] confusion matrix of that class count."""
+    K = 20 if coarse else 100
+    if np.shape(C) != (K, K):
+        raise ValueError("CIFAR-100 with %s labels has %d classes; C has shape %s" % ("coarse" if coarse else "fine", K, np.shape(C)))
+    tx, ty = unpickle100(os.path.join(data_dir, 'train'), coarse)
+    vx, vy = unpickle100(os.path.join(data_dir, 'test'), coarse)
+    return cifar_generator(np.asarray(tx), np.asarray(ty), batch_size, C, rng), cifar_generator(np.asarray(vx), np.asarray(vy), batch_size, C, rng)
+
+
+def class_templates(n_classes=10):
+    """Fixed low-frequency colour patterns [K,3,32,32] (sums of three separable cosines per channel, frequencies 0..2):
     the class-carrying part of the "templates" synthetic images.  Not reference data -- a stand-in for CIFAR-10 (no dataset and
-    no network here) on which a generated image's class can be read off exactly (eval_cifar.TemplateClassifier)."""
+    no network here) on which a generated image's class can be read off exactly (eval_cifar.TemplateClassifier).  The first ten
+    patterns are the same for every K (one stream, drawn class after class)."""
     trs = np.random.RandomState(4242)
     yy, xx = np.mgrid[0:32, 0:32] / 32.0
-    tmpl = np.zeros((10, 3, 32, 32))
-    for c in range(10):
+    tmpl = np.zeros((n_classes, 3, 32, 32))
+    for c in range(n_classes):
         for ch in range(3):
             for _ in range(3):
                 fx, fy = trs.randint(0, 3, size=2)
@@ -78,7 +101,7 @@ def class_templates():
     return tmpl
 
 
-def template_images(rs, labels):
+def template_images(rs, labels, n_classes=10):
     """uint8-valued CHW rows [n,3072]: tanh(0.6 template[label] + 0.6 low-pass noise) mapped to 0..255 -- natural-image-like
     second-order statistics that carry the label (per-image noise sigma ~ 1.4 pixels, as strong as the class pattern)."""
     n = len(labels)
@@ -87,21 +110,21 @@ def template_images(rs, labels):
         noise = (np.roll(noise, 1, 2) + 2 * noise + np.roll(noise, -1, 2)) / 4
         noise = (np.roll(noise, 1, 3) + 2 * noise + np.roll(noise, -1, 3)) / 4
     noise /= noise.std()
-    img = np.tanh(0.6 * class_templates()[np.asarray(labels)] + 0.6 * noise)
+    img = np.tanh(0.6 * class_templates(n_classes)[np.asarray(labels)] + 0.6 * noise)
     return np.clip(np.floor((img * 0.5 + 0.5) * 256.0), 0, 255).astype(np.int64).reshape(n, 3072)
 
 
-def synthetic_cifar(n=50000, seed=1234, kind="uniform"):
-    """Synthetic stand-ins for the CIFAR-10 arrays.  kind "uniform" (SURVEY 8(d)): uint8 images U{0..255} [n,3072] (CHW) and
-    clean labels U{0..9} -- timing / plumbing only, the images carry no label.  kind "templates": ``template_images`` of the
+def synthetic_cifar(n=50000, seed=1234, kind="uniform", n_classes=10):
+    """Synthetic stand-ins for the CIFAR arrays.  kind "uniform" (SURVEY 8(d)): uint8 images U{0..255} [n,3072] (CHW) and
+    clean labels U{0..K-1} -- timing / plumbing only, the images carry no label.  kind "templates": ``template_images`` of the
     clean labels -- a learnable conditional distribution for end-to-end training runs."""
     rs = np.random.RandomState(seed)
     if kind == "uniform":
-        return rs.randint(0, 256, size=(n, 3072), dtype=np.uint8), rs.randint(10, size=n)
+        return rs.randint(0, 256, size=(n, 3072), dtype=np.uint8), rs.randint(n_classes, size=n)
     if kind != "templates":
         raise ValueError("unknown synthetic kind %r" % (kind,))
-    labels = rs.randint(10, size=n)
-    images = np.concatenate([template_images(rs, labels[i:i + 5000]) for i in range(0, n, 5000)]).astype(np.uint8)
+    labels = rs.randint(n_classes, size=n)
+    images = np.concatenate([template_images(rs, labels[i:i + 5000], n_classes) for i in range(0, n, 5000)]).astype(np.uint8)
     return images, labels
 
 

@@ -1205,7 +1205,7 @@ def proj_head(ctx, feat, w_out, b_out, table, w_e, b_e, parts, weight, loss_acc,
         assert feat.grad is None, "the projection head is its features' only consumer"
         dfeat, _ = grad_of(ctx, feat)
     pg = lambda t: _p(t) if (rec and t is not None) else None
-    if rec and HEAD_RIDERS and (w_out.req or w_e.req or table.req):
+    if rec and HEAD_RIDERS and v <= L.LABELS_NARROW and (w_out.req or w_e.req or table.req):
         # deferred parameter gradients (rcgan_head_desc::defer_ws): dlogit and dE in the step arena until the launches that carry them
         nbytes = (n * (v + 1) + (v + 1) * d) * 4
         hd.defer_ws, hd.defer_ws_bytes = ctx.arena.alloc(nbytes), nbytes

@@ -17,11 +17,13 @@ from . import data as D
 from .host import Flags, Plot, Saver, latest_checkpoint, load_checkpoint, record_setting, save_images
 
 DATA_DIR = '../data/cifar10/cifar-10-batches-py/'
+DATA_DIR_100 = '../data/cifar100/cifar-100-python/'
+DATASETS = ("cifar", "cifar100")
 
 
 def define_flags():
     f = Flags()
-    f.DEFINE_string("dataset", 'cifar', "Dataset")
+    f.DEFINE_string("dataset", 'cifar', "Dataset [cifar, cifar100]")
     f.DEFINE_string("algorithm", 'rcgan', "Algorithm [rcgan, rcgan-u, biased, unbiased]")
     f.DEFINE_float("alpha", 0.8, "1 - noise level")
     f.DEFINE_string("run", '0', "run name")
@@ -58,10 +60,28 @@ def define_flags():
     f.DEFINE_string("synthetic_kind", 'uniform', "with --synthetic: [uniform] SURVEY 8(d) label-free noise images, [templates] "
                     "class-pattern images (data.template_images) scored by eval_cifar.TemplateClassifier instead of the CIFAR ResNet")
     f.DEFINE_integer("seed", 0, "variable-initialisation seed")
-    f.DEFINE_string("data_dir", DATA_DIR, "CIFAR-10 python batches")
+    f.DEFINE_string("data_dir", DATA_DIR, "CIFAR-10 python batches (--dataset cifar100: the cifar-100-python directory, default %s)"
+                    % DATA_DIR_100)
+    f.DEFINE_boolean("coarse_labels", False, "--dataset cifar100: train on the 20 coarse labels instead of the 100 fine ones")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
+
+
+def dataset_setup(FLAGS):
+    """-> (class count, data directory) of --dataset: cifar = CIFAR-10 (10), cifar100 = CIFAR-100 (100 fine or 20 coarse)."""
+    if FLAGS.dataset not in DATASETS:
+        raise ValueError("unknown --dataset %r (one of %s)" % (FLAGS.dataset, ", ".join(DATASETS)))
+    if FLAGS.dataset == "cifar":
+        if FLAGS.coarse_labels:
+            raise ValueError("--coarse_labels needs --dataset cifar100")
+        return 10, FLAGS.data_dir
+    return (20 if FLAGS.coarse_labels else 100), (DATA_DIR_100 if FLAGS.data_dir == DATA_DIR else FLAGS.data_dir)
+
+
+def grid_labels(n_classes):
+    """The fixed 100-sample grid's labels, sorted: ten per class for CIFAR-10 (gan_resnet.py:823), one per class for 100."""
+    return np.sort(np.arange(100) % n_classes).astype('int32')
 
 
 def main(argv=None):
@@ -69,13 +89,13 @@ def main(argv=None):
     FLAGS = define_flags().parse(argv)
     if FLAGS.log_file is None:
         raise ValueError('flag log_file is required')                         # gan_resnet.py:81-82
-    if FLAGS.dataset != "cifar":
-        raise ValueError("only --dataset cifar is wired in this entry point")
+    N_CLASSES, DATA = dataset_setup(FLAGS)
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
     logging.info('alpha = {}'.format(ALPHA))
-    C_ALPHA = D.C_ALPHA(ALPHA)
+    C_ALPHA = D.C_ALPHA(ALPHA, N_CLASSES)
+    logging.info('dataset = {} ({} classes)'.format(FLAGS.dataset, N_CLASSES))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -121,16 +141,19 @@ def main(argv=None):
                    perm_classifier=FLAGS.perm_classifier, perm_multiplier=FLAGS.perm_multiplier, perm_type=FLAGS.perm_type,
                    confuse_init=FLAGS.confuse_init, confuse_init_diag=FLAGS.confuse_init_diag,
                    confuse_multiplier=FLAGS.confuse_multiplier, confuse_lr_decay=FLAGS.confuse_lr_decay,
-                   device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision)
+                   device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision,
+                   n_classes=N_CLASSES)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     if FLAGS.synthetic:
-        tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind)
-        vx, vy = D.synthetic_cifar(10000, 1235, FLAGS.synthetic_kind)
+        tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
+        vx, vy = D.synthetic_cifar(10000, 1235, FLAGS.synthetic_kind, N_CLASSES)
         train_gen = D.cifar_generator(tx, ty, BATCH_SIZE, C_ALPHA)
         dev_gen = D.cifar_generator(vx, vy, BATCH_SIZE, C_ALPHA)
+    elif FLAGS.dataset == "cifar100":
+        train_gen, dev_gen = D.load100(BATCH_SIZE, DATA, C_ALPHA, coarse=FLAGS.coarse_labels)
     else:
-        train_gen, dev_gen = D.load(BATCH_SIZE, FLAGS.data_dir, C_ALPHA)
+        train_gen, dev_gen = D.load(BATCH_SIZE, DATA, C_ALPHA)
     gen = D.inf_train_gen(train_gen)
     gen_G = D.inf_train_gen_G(train_gen, 2)
     from .dp import shard_rows
@@ -144,7 +167,7 @@ def main(argv=None):
             m.load_state_dict(load_checkpoint(ckpt))
     plot = Plot()
     fixed_noise = np.random.normal(size=(100, Z_DIM)).astype('float32')       # gan_resnet.py:822
-    fixed_labels = np.array([k for k in range(10) for _ in range(10)], dtype='int32')
+    fixed_labels = grid_labels(N_CLASSES)
 
     def d_feed(batch):
         images, labels, rnd, bia, inv = batch
@@ -155,6 +178,10 @@ def main(argv=None):
     # generated-label accuracy (gan_resnet.py:424-455, 847-861): 1000 samples, 100 per class, ONE classifier batch
     label_100_list = [label for label in range(10) for _ in range(10)]
     GEN_ACC_FREQ = FLAGS.generated_label_accuracy_freq
+    if N_CLASSES != 10 and GEN_ACC_FREQ > 0:
+        # the label classifier (and the templates' reader) know the ten CIFAR-10 classes only
+        logging.info('generated label accuracy: skipped, its classifier is CIFAR-10-only ({} classes here)'.format(N_CLASSES))
+        GEN_ACC_FREQ = 0
     acc_state = {"clf": None, "max": 0.0}
 
     def save_samples(n):
@@ -179,7 +206,7 @@ def main(argv=None):
         from .inception_score import get_inception_score, samples_as_the_reference_feeds_them
         # the reference draws these labels and latents with TensorFlow's generators (gan_resnet.py:836-838): they must not advance
         # the global numpy stream the data and label-noise draws come from -- a private stream
-        all_samples = [m.sample(is_rs.randint(10, size=100).astype('int32'), is_rs.normal(size=(100, Z_DIM)).astype('float32'))
+        all_samples = [m.sample(is_rs.randint(N_CLASSES, size=100).astype('int32'), is_rs.normal(size=(100, Z_DIM)).astype('float32'))
                        for _ in range(int(n / 100))]
         return get_inception_score(samples_as_the_reference_feeds_them(np.concatenate(all_samples, axis=0)), inception_fn)
 
