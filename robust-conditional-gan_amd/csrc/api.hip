@@ -591,7 +591,7 @@ int rcgan_conv_fused_pool_ok(const rcgan_conv_desc* d) { return d && mfma_pool_o
 
 size_t rcgan_conv_prepared_bytes(const rcgan_conv_desc* d) {
   size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-  if (mfma_eligible(d)) return 2 * elems * sizeof(bf16_t) + (mfma_phase_filters(d) ? 32 * (size_t)d->cin * d->cout * sizeof(bf16_t) : 0) + 256;
+  if (mfma_eligible(d)) return (mfma_phase_filters(d) ? mfma_prepared_sum_end(d) : mfma_prepared_sum_fwd(d)) * sizeof(bf16_t) + 256;
   if (img_side(d)) return img_extra_offset(d) + img_extra_bytes(d);
   return elems * sizeof(float) + 256;
 }
@@ -603,9 +603,9 @@ int rcgan_conv_prepare(rcgan_ctx* ctx, const rcgan_conv_desc* d, const float* w,
   size_t elems = (size_t)T * d->cin * d->cout;
   if (mfma_eligible(d)) {
     bf16_t* wt = (bf16_t*)prepared;
-    rc = mfma_prepare_launch(ctx, w, sigma, wt, wt + elems, T, d->cin, d->cout);
+    rc = mfma_prepare_launch(ctx, w, sigma, wt, wt + mfma_prepared_rot(d), T, d->cin, d->cout);
     if (rc || !mfma_phase_filters(d)) return rc;
-    bf16_t* wph = wt + 2 * elems;
+    bf16_t* wph = wt + mfma_prepared_sum_fwd(d);
     const int kind = (d->flags & RCGAN_CONV_OUT_MEANPOOL2) ? 1 : 0;
     return conv_prepare_phase_launch(ctx, 1, &w, &sigma, &wph, &d->cin, &d->cout, &kind);
   }
@@ -696,23 +696,90 @@ size_t rcgan_conv_workspace_bytes(const rcgan_conv_desc* d) {
   return ws;
 }
 
-static void fill_mfma_args(const rcgan_conv_desc* d, MfmaConvArgs& a) {
-  int oh, ow, pt, pl;
-  same_pad(d->h, d->kh, 1, &oh, &pt);
-  same_pad(d->w, d->kw, 1, &ow, &pl);
-  a.N = d->n; a.H = d->h; a.W = d->w; a.KH = d->kh; a.KW = d->kw; a.PT = pt; a.PL = pl;
-  a.M = (long)d->n * d->h * d->w;
-  a.lw = ilog2_exact(d->w); a.lh = ilog2_exact(d->h);
-  if (a.lw < 0 || a.lh < 0) { a.lw = -1; a.lh = -1; }
-  a.stamps = nullptr;
-  a.wph = nullptr; a.phase = 0;
-  a.resid_up = 0;
-  a.stats = nullptr;
-}
-
 // RCGAN_CONV_RESID_UPSAMPLE2X: the matrix-core epilogue reads the half-resolution residual in place (power-of-two output grid)
 int rcgan_conv_resid_up_ok(const rcgan_conv_desc* d) {
   return d && mfma_eligible(d) && !(d->flags & RCGAN_CONV_OUT_MEANPOOL2) && d->stride == 1 && ilog2_exact(d->w) >= 1 && ilog2_exact(d->h) >= 1 ? 1 : 0;
+}
+
+// ---- posing a matrix-core launch ----------------------------------------------------------------------------------------------
+// THE translation of a descriptor into the MfmaConvArgs that mfma_conv_route routes and mfma_conv_launch issues: which of the six forms
+// (plain / phase / gather, forward or data gradient) the layer runs in, which filter layout of the prepared buffer (conv_mfma.h:
+// mfma_prepared_*) the kernel reads, and the guards in front of every launch.  The entry points add the fields their fused form owns
+// (stats, bn_*, resid, mask); the routing queries pose with ctx == nullptr and null tensors and ask the routing about the same struct.
+enum ConvDir { CONV_FWD, CONV_DGRAD };
+
+// Queries have no zero page and no prepared buffer, and the routing only asks whether they are THERE (mfma_conv_route: a.zero != nullptr;
+// mfma_conv8_phase_form: a.wph != nullptr) -- nothing is read through this stand-in.
+static const bf16_t pose_query_stand_in[8] = {0};
+
+// in / out: x / y (forward), dy / dx (data gradient).  has_resid: a residual tensor will be added by the epilogue.
+static int mfma_conv_pose(rcgan_ctx* ctx, const rcgan_conv_desc* d, ConvDir dir, const void* in, const void* prepared, const float* bias,
+                          bool has_resid, void* out, MfmaConvArgs* posed) {
+  auto fail = [&](int code, const char* what) { if (ctx) ctx->err = std::string("mfma_conv_pose: ") + what; return code; };
+  *posed = MfmaConvArgs{};      // (value-initialised whatever follows: a routing question never reads an indeterminate field)
+  MfmaConvArgs& a = *posed;
+  const bool query = ctx == nullptr;
+  const bool pool = d->flags & RCGAN_CONV_OUT_MEANPOOL2, up = d->flags & RCGAN_CONV_IN_UPSAMPLE2X;
+  if (pool && !(rcgan_conv_fused_pool_ok(d) && !has_resid))
+    return fail(RCGAN_EINVALID_ARG, "fused mean pool not available for this convolution (rcgan_conv_fused_pool_ok)");
+  if (!mfma_eligible(d)) return fail(RCGAN_EUNSUPPORTED_SHAPE, "not a matrix-core convolution");
+  if ((long)d->n * d->h * d->w * (d->cin > d->cout ? d->cin : d->cout) >= (1L << 31))
+    return fail(RCGAN_EUNSUPPORTED_SHAPE, "tensor exceeds the 32-bit element offsets of the MFMA kernels");
+  int oh, ow;
+  same_pad(d->h, d->kh, 1, &oh, &a.PT);
+  same_pad(d->w, d->kw, 1, &ow, &a.PL);
+  a.N = d->n; a.H = d->h; a.W = d->w; a.KH = d->kh; a.KW = d->kw;
+  a.M = (long)d->n * d->h * d->w;
+  const long m_low = (long)d->n * (d->h / 2) * (d->w / 2);      // the gather forms run over the low-resolution grid
+  a.lw = ilog2_exact(d->w); a.lh = ilog2_exact(d->h);
+  if (a.lw < 0 || a.lh < 0) { a.lw = -1; a.lh = -1; }
+  a.in = (const bf16_t*)in; a.bias = bias; a.out = (bf16_t*)out;
+  a.zero = query ? pose_query_stand_in : (const bf16_t*)ctx->zero_page;
+  a.accumulate = (d->flags & RCGAN_CONV_ACCUMULATE) ? 1 : 0;
+  auto filters = [&](size_t at) { return query ? pose_query_stand_in : (const bf16_t*)prepared + at; };
+  if (dir == CONV_FWD) {
+    a.wt = filters(0);
+    a.Cin = d->cin; a.Cout = d->cout;
+    a.relu_in = (d->flags & RCGAN_CONV_IN_RELU) ? 1 : 0;
+    if (pool) {
+      // ConvMeanPool as one 4x4 stride-2 convolution over x (16 taps, summed filters x 1/4): y over the pooled grid
+      a.M = m_low;
+      a.wph = filters(mfma_prepared_sum_fwd(d));        // gather layout [Cout][16 * Cin]
+      a.phase = MFMA_FORM_GATHER;
+    } else {
+      // an upsample-3x3 takes its summed filters [4][Cout][4 * Cin] along and stays MFMA_FORM_PLAIN: the routing runs it sub-pixel where
+      // whole tiles fall into one phase (mfma_conv8_phase_form, launch_conv_mfma), else over floor(row / 2) sources with wt
+      a.up = up ? 1 : 0;
+      if (up && mfma_phase_filters(d)) a.wph = filters(mfma_prepared_sum_fwd(d));
+      a.resid_up = (has_resid && (d->flags & RCGAN_CONV_RESID_UPSAMPLE2X)) ? 1 : 0;
+      if (a.resid_up && !rcgan_conv_resid_up_ok(d))
+        return fail(RCGAN_EINVALID_ARG, "half-resolution residual not available for this convolution (rcgan_conv_resid_up_ok)");
+    }
+  } else {
+    a.Cin = d->cout; a.Cout = d->cin;          // reduction over cout, output channels = cin
+    if (pool) {
+      // dy lives on the pooled grid: dx (full resolution) in the sub-pixel form -- pixel (2i + ph, 2j + pw) gathers the 2x2 pooled
+      // pixels around it with the transposed summed filters of its phase
+      a.wt = filters(0);                                    // (not a usable fallback: mfma_conv_route never leaves the phase form)
+      a.up = 1;                                             // source grid = the pooled one (h/2 x w/2)
+      a.wph = filters(mfma_prepared_sum_bwd(d));            // phase layout [4][Cin][4 * Cout]
+      a.phase = MFMA_FORM_PHASE;
+    } else if (up && mfma_phase_dgrad_ok(d)) {
+      // sub-pixel form: dx over the low-resolution grid straight from dy (16 taps at stride 2, transposed summed filters), the
+      // ReLU mask and the accumulation in the epilogue -- no full-resolution scratch, no 2x2 sum pass
+      a.wt = filters(mfma_prepared_rot(d));
+      a.M = m_low;
+      a.wph = filters(mfma_prepared_sum_bwd(d));            // gather layout [Cin][16 * Cout]
+      a.phase = MFMA_FORM_GATHER;
+    } else {
+      // rotated filters, mirrored padding.  Behind an upsample this is dx on the FULL-resolution grid: the caller sends it to scratch,
+      // and the 2x2 sum pass behind it owns the ReLU mask and the accumulation
+      a.wt = filters(mfma_prepared_rot(d));
+      a.PT = d->kh - 1 - a.PT; a.PL = d->kw - 1 - a.PL;
+      if (up) a.accumulate = 0;
+    }
+  }
+  return RCGAN_OK;
 }
 
 int rcgan_conv2d_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* prepared, const float* bias, void* y) {
@@ -720,28 +787,15 @@ int rcgan_conv2d_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, co
 }
 
 // ---- batch-norm statistics out of the producing convolution's epilogue (conv_mfma8.hip) -------------------------------------
-// the forward launch rcgan_conv2d_fwd_residual would issue for this descriptor on the matrix-core path
-static void stats_conv_args(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* prepared, const float* bias,
-                            const void* residual, void* y, MfmaConvArgs& a) {
-  fill_mfma_args(d, a);
-  a.in = (const bf16_t*)x; a.wt = (const bf16_t*)prepared; a.bias = bias; a.mask = nullptr; a.out = (bf16_t*)y;
-  if (mfma_phase_filters(d) && (d->flags & RCGAN_CONV_IN_UPSAMPLE2X)) a.wph = (const bf16_t*)prepared + 2 * (size_t)d->kh * d->kw * d->cin * d->cout;
-  a.resid = (const bf16_t*)residual;
-  a.resid_up = (residual != nullptr && (d->flags & RCGAN_CONV_RESID_UPSAMPLE2X)) ? 1 : 0;
-  a.zero = (const bf16_t*)(ctx ? ctx->zero_page : (void*)16);
-  a.Cin = d->cin; a.Cout = d->cout;
-  a.up = (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) ? 1 : 0;
-  a.relu_in = 0; a.accumulate = 0;
-}
-
 int rcgan_conv_stats_ok(const rcgan_conv_desc* d) {
   if (!d || !mfma_eligible(d) || d->stride != 1 || d->cout != 256) return 0;
   if (d->flags & (RCGAN_CONV_OUT_MEANPOOL2 | RCGAN_CONV_ACCUMULATE | RCGAN_CONV_IN_RELU | RCGAN_CONV_FORCE_DIRECT)) return 0;
-  if (((long)d->n * d->h * d->w) % 256 != 0 || (long)d->n * d->h * d->w * (d->cin > d->cout ? d->cin : d->cout) >= (1L << 31)) return 0;
+  if (((long)d->n * d->h * d->w) % 256 != 0) return 0;
   if ((d->flags & RCGAN_CONV_RESID_UPSAMPLE2X) && !rcgan_conv_resid_up_ok(d)) return 0;
+  // (asked with stats == nullptr although the launch sets it: the routing reads !a.stats only to choose between the halo-patch and the
+  // tile-per-tap 256 x 256 kernel, and mfma_conv_is_p8 says yes to both)
   MfmaConvArgs a;
-  int dummy = 0;
-  stats_conv_args(nullptr, d, nullptr, &dummy, nullptr, nullptr, nullptr, a);
+  if (mfma_conv_pose(nullptr, d, CONV_FWD, nullptr, nullptr, nullptr, false, nullptr, &a)) return 0;
   // (an upsample-3x3 layer must take its sub-pixel form or not be upsampled at all: the finisher knows these two tile orders)
   if (a.up && !(mfma_phase_filters(d) && mfma_conv8_phase_form(a))) return 0;
   return mfma_conv_is_p8(a) ? 1 : 0;
@@ -758,7 +812,9 @@ int rcgan_conv2d_fwd_stats(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void*
   RC_REQUIRE(ctx, tile_sums != nullptr, "null tile_sums");
   RC_REQUIRE(ctx, rcgan_conv_stats_ok(d), "this convolution does not produce tile statistics (rcgan_conv_stats_ok)");
   MfmaConvArgs a;
-  stats_conv_args(ctx, d, x, prepared, bias, residual, y, a);
+  rc = mfma_conv_pose(ctx, d, CONV_FWD, x, prepared, bias, residual != nullptr, y, &a);
+  if (rc) return rc;
+  a.resid = (const bf16_t*)residual;
   a.stats = tile_sums;
   return mfma_conv_launch(ctx, a);
 }
@@ -781,35 +837,16 @@ int rcgan_bn_stats_from_tiles(rcgan_ctx* ctx, const rcgan_conv_desc* d, int nseg
   return bn_tile_stats_finish_launch(ctx, tile_sums, d->cout, nseg, (int)((long)(d->n / nseg) * px / 256), 1, 0, count, eps, mean, rstd);
 }
 
-// the MfmaConvArgs of an ordinary forward launch (no pool fold), as rcgan_conv2d_fwd_residual builds them
-static void mfma_fwd_args(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* prepared, const float* bias, const void* residual,
-                          void* y, MfmaConvArgs& a) {
-  fill_mfma_args(d, a);
-  a.in = (const bf16_t*)x; a.wt = (const bf16_t*)prepared; a.bias = bias; a.mask = nullptr; a.out = (bf16_t*)y;
-  if (mfma_phase_filters(d) && (d->flags & RCGAN_CONV_IN_UPSAMPLE2X)) a.wph = (const bf16_t*)prepared + 2 * (size_t)d->kh * d->kw * d->cin * d->cout;
-  a.resid = (const bf16_t*)residual;
-  a.resid_up = (residual != nullptr && (d->flags & RCGAN_CONV_RESID_UPSAMPLE2X)) ? 1 : 0;
-  a.zero = ctx ? (const bf16_t*)ctx->zero_page : (const bf16_t*)prepared;      // (routing queries without a context: any non-null value)
-  a.Cin = d->cin; a.Cout = d->cout;
-  a.up = (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) ? 1 : 0;
-  a.relu_in = (d->flags & RCGAN_CONV_IN_RELU) ? 1 : 0;
-  a.accumulate = (d->flags & RCGAN_CONV_ACCUMULATE) ? 1 : 0;
-}
-
 // the convolutions that can apply the batch norm in front of them to their staged input: the small-output image-end layers (G.Output)
 // and (round 5) whatever the routing hands to a halo-patch kernel -- plain 3x3 / upsample-3x3 layers on 16- / 32-wide (low-resolution)
 // images with enough tiles to fill the chip (G.Block.2.Conv2, G.Block.3.Conv1 / Conv2 at the bench batches)
 static int mfma_bn_in_route(const rcgan_conv_desc* d) {
   if (!d || d->dtype != RCGAN_H16 || !mfma_eligible(d) || (d->flags & (RCGAN_CONV_OUT_MEANPOOL2 | RCGAN_CONV_IN_RELU | RCGAN_CONV_ACCUMULATE | RCGAN_CONV_FORCE_DIRECT)))
     return 0;
-  if ((long)d->n * d->h * d->w * (d->cin > d->cout ? d->cin : d->cout) >= (1L << 31)) return 0;
   static const int on = [] { const char* e = getenv("RCGAN_BN_INTO_PATCH"); return e ? atoi(e) : 1; }();
   if (!on) return 0;
   MfmaConvArgs a;
-  // (the summed sub-pixel filters exist whenever mfma_phase_filters(d): a non-null stand-in is enough for the routing question -- nothing
-  // is read through it)
-  static const bf16_t stand_in[8] = {0};
-  mfma_fwd_args(nullptr, d, nullptr, stand_in, nullptr, nullptr, nullptr, a);
+  if (mfma_conv_pose(nullptr, d, CONV_FWD, nullptr, nullptr, nullptr, false, nullptr, &a)) return 0;
   return mfma_conv_bn_route(a);
 }
 
@@ -838,12 +875,12 @@ int rcgan_conv2d_fwd_bn_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, const
   if (!rcgan_conv_bn_in_ok(d)) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "no kernel applies a batch norm to this convolution's staged input (rcgan_conv_bn_in_ok)");
   if (residual == nullptr && img_fwd_bn_ok(d)) return img_fwd_bn(ctx, d, x, prepared, bias, y, mean, rstd, gamma, beta, labels, segments, act);
   RC_REQUIRE(ctx, mfma_bn_in_route(d), "residual form needs a halo-patch kernel");
-  if (residual != nullptr && (d->flags & RCGAN_CONV_RESID_UPSAMPLE2X))
-    RC_REQUIRE(ctx, rcgan_conv_resid_up_ok(d), "half-resolution residual not available for this convolution (rcgan_conv_resid_up_ok)");
+  MfmaConvArgs a;
+  rc = mfma_conv_pose(ctx, d, CONV_FWD, x, prepared, bias, residual != nullptr, y, &a);
+  if (rc) return rc;
   rc = ensure_selftest(ctx);
   if (rc) return rc;
-  MfmaConvArgs a;
-  mfma_fwd_args(ctx, d, x, prepared, bias, residual, y, a);
+  a.resid = (const bf16_t*)residual;
   a.bn_mean = mean; a.bn_rstd = rstd; a.bn_gamma = gamma; a.bn_beta = beta; a.bn_labels = labels;
   a.bn_seg_samples = d->n / segments; a.bn_act = act;
   return mfma_conv_launch(ctx, a);
@@ -853,9 +890,8 @@ int rcgan_conv2d_fwd_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, const vo
                               const void* residual, void* y) {
   int rc = check_desc(ctx, d);
   if (rc) return rc;
-  if (residual != nullptr && (d->flags & RCGAN_CONV_RESID_UPSAMPLE2X))
-    RC_REQUIRE(ctx, rcgan_conv_resid_up_ok(d), "half-resolution residual not available for this convolution (rcgan_conv_resid_up_ok)");
   if (residual != nullptr && !mfma_eligible(d)) {      // other kernels: plain forward, then y += residual
+    RC_REQUIRE(ctx, !(d->flags & RCGAN_CONV_RESID_UPSAMPLE2X), "half-resolution residual not available for this convolution (rcgan_conv_resid_up_ok)");
     RC_REQUIRE(ctx, residual != y, "residual must not alias the output");
     rc = rcgan_conv2d_fwd_residual(ctx, d, x, prepared, bias, nullptr, y);
     if (rc) return rc;
@@ -864,39 +900,11 @@ int rcgan_conv2d_fwd_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, const vo
     same_pad(d->w, d->kw, d->stride, &ow, &p);
     return rcgan_axpby(ctx, (size_t)d->n * oh * ow * d->cout, d->dtype, 1.f, residual, 1.f, y);
   }
-  if (d->flags & RCGAN_CONV_OUT_MEANPOOL2) {
-    // ConvMeanPool as one 4x4 stride-2 convolution over x (16 taps, summed filters x 1/4): y over the pooled grid
-    RC_REQUIRE(ctx, mfma_pool_ok(d) && residual == nullptr, "fused mean pool not available for this convolution (rcgan_conv_fused_pool_ok)");
-    if ((long)d->n * d->h * d->w * (d->cin > d->cout ? d->cin : d->cout) >= (1L << 31))
-      RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "tensor exceeds the 32-bit element offsets of the MFMA kernels");
+  if ((d->flags & RCGAN_CONV_OUT_MEANPOOL2) || mfma_eligible(d)) {
     MfmaConvArgs a;
-    fill_mfma_args(d, a);
-    const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    a.in = (const bf16_t*)x; a.wt = (const bf16_t*)prepared; a.bias = bias; a.mask = nullptr; a.out = (bf16_t*)y; a.resid = nullptr;
-    a.zero = (const bf16_t*)ctx->zero_page;
-    a.Cin = d->cin; a.Cout = d->cout;
-    a.up = 0;
-    a.relu_in = (d->flags & RCGAN_CONV_IN_RELU) ? 1 : 0;
-    a.accumulate = (d->flags & RCGAN_CONV_ACCUMULATE) ? 1 : 0;
-    a.M = (long)d->n * (d->h / 2) * (d->w / 2);
-    a.wph = (const bf16_t*)prepared + 2 * elems;        // gather layout [Cout][16 * Cin]
-    a.phase = 2;
-    return mfma_conv_launch(ctx, a);
-  }
-  if (mfma_eligible(d)) {
-    if ((long)d->n * d->h * d->w * (d->cin > d->cout ? d->cin : d->cout) >= (1L << 31))
-      RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "tensor exceeds the 32-bit element offsets of the MFMA kernels");
-    MfmaConvArgs a;
-    fill_mfma_args(d, a);
-    a.in = (const bf16_t*)x; a.wt = (const bf16_t*)prepared; a.bias = bias; a.mask = nullptr; a.out = (bf16_t*)y;
-    if (mfma_phase_filters(d) && (d->flags & RCGAN_CONV_IN_UPSAMPLE2X)) a.wph = (const bf16_t*)prepared + 2 * (size_t)d->kh * d->kw * d->cin * d->cout;
+    rc = mfma_conv_pose(ctx, d, CONV_FWD, x, prepared, bias, residual != nullptr, y, &a);
+    if (rc) return rc;
     a.resid = (const bf16_t*)residual;
-    a.resid_up = (residual != nullptr && (d->flags & RCGAN_CONV_RESID_UPSAMPLE2X)) ? 1 : 0;
-    a.zero = (const bf16_t*)ctx->zero_page;
-    a.Cin = d->cin; a.Cout = d->cout;
-    a.up = (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) ? 1 : 0;
-    a.relu_in = (d->flags & RCGAN_CONV_IN_RELU) ? 1 : 0;
-    a.accumulate = (d->flags & RCGAN_CONV_ACCUMULATE) ? 1 : 0;
     return mfma_conv_launch(ctx, a);
   }
   if (img_side(d)) return img_fwd(ctx, d, x, prepared, bias, y);
@@ -928,60 +936,25 @@ int rcgan_conv2d_bwd_data_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, con
   const bool relu = d->flags & RCGAN_CONV_IN_RELU;
   const int acc = (d->flags & RCGAN_CONV_ACCUMULATE) ? 1 : 0;
   RC_REQUIRE(ctx, !relu || x != nullptr, "IN_RELU needs x for the mask");
-  if (d->flags & RCGAN_CONV_OUT_MEANPOOL2) {
-    // dy lives on the pooled grid: dx (full resolution) in the sub-pixel form -- pixel (2i + ph, 2j + pw) gathers the 2x2 pooled
-    // pixels around it with the transposed summed filters of its phase
-    RC_REQUIRE(ctx, mfma_pool_ok(d) && residual == nullptr, "fused mean pool not available for this convolution (rcgan_conv_fused_pool_ok)");
-    MfmaConvArgs a;
-    fill_mfma_args(d, a);
-    const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    a.in = (const bf16_t*)dy; a.wt = (const bf16_t*)prepared; a.bias = nullptr; a.mask = relu ? (const bf16_t*)x : nullptr;
-    a.resid = nullptr; a.out = (bf16_t*)dx;
-    a.zero = (const bf16_t*)ctx->zero_page;
-    a.Cin = d->cout; a.Cout = d->cin;
-    a.up = 1;                                             // source grid = the pooled one (h/2 x w/2)
-    a.relu_in = 0; a.accumulate = acc;
-    a.wph = (const bf16_t*)prepared + 2 * elems + 16 * (size_t)d->cin * d->cout;        // phase layout [4][Cin][4 * Cout]
-    a.phase = 1;
-    return mfma_conv_launch(ctx, a);
-  }
   void* target = dx;
   if (up) {
     size_t need = (size_t)d->n * d->h * d->w * d->cin * dtype_size(d->dtype);
     if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
     target = ws;
   }
-  if (up && mfma_phase_dgrad_ok(d)) {
-    // sub-pixel form: dx over the low-resolution grid straight from dy (16 taps at stride 2, transposed summed filters), the
-    // ReLU mask and the accumulation in the epilogue -- no full-resolution scratch, no 2x2 sum pass
-    MfmaConvArgs a;
-    fill_mfma_args(d, a);
-    const size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    a.in = (const bf16_t*)dy; a.wt = (const bf16_t*)prepared + elems; a.bias = nullptr; a.mask = relu ? (const bf16_t*)x : nullptr;
-    a.resid = nullptr; a.out = (bf16_t*)dx;
-    a.zero = (const bf16_t*)ctx->zero_page;
-    a.Cin = d->cout; a.Cout = d->cin;
-    a.up = 0; a.relu_in = 0; a.accumulate = acc;
-    a.M = (long)d->n * (d->h / 2) * (d->w / 2);
-    a.wph = (const bf16_t*)prepared + 2 * elems + 16 * (size_t)d->cin * d->cout;
-    a.phase = 2;
-    return mfma_conv_launch(ctx, a);
-  }
   const void* mask = (relu && !up) ? x : nullptr;
   const int acc_now = up ? 0 : acc;
-  if (mfma_eligible(d)) {
+  if ((d->flags & RCGAN_CONV_OUT_MEANPOOL2) || mfma_eligible(d)) {
     MfmaConvArgs a;
-    fill_mfma_args(d, a);
-    size_t elems = (size_t)d->kh * d->kw * d->cin * d->cout;
-    a.in = (const bf16_t*)dy; a.wt = (const bf16_t*)prepared + elems; a.bias = nullptr; a.mask = (const bf16_t*)mask;
-    a.resid = (const bf16_t*)residual;
-    a.out = (bf16_t*)target;
-    a.zero = (const bf16_t*)ctx->zero_page;
-    a.Cin = d->cout; a.Cout = d->cin;          // reduction over cout, output channels = cin
-    a.PT = d->kh - 1 - a.PT; a.PL = d->kw - 1 - a.PL;
-    a.up = 0; a.relu_in = 0; a.accumulate = acc_now;
-    rc = mfma_conv_launch(ctx, a);
+    rc = mfma_conv_pose(ctx, d, CONV_DGRAD, dy, prepared, nullptr, residual != nullptr, dx, &a);
     if (rc) return rc;
+    // an upsampled layer not taken in gather form: full-resolution dx into the scratch, mask and accumulation in the sum pass below
+    const bool scratch = up && a.phase == MFMA_FORM_PLAIN;
+    if (scratch) a.out = (bf16_t*)target;
+    a.mask = (relu && !scratch) ? (const bf16_t*)x : nullptr;
+    a.resid = (const bf16_t*)residual;
+    rc = mfma_conv_launch(ctx, a);
+    if (rc || !scratch) return rc;
   } else if (mask == nullptr && !up && img_side(d)) {
     rc = img_dgrad(ctx, d, dy, prepared, target, acc_now);
     if (rc) return rc;
@@ -999,9 +972,10 @@ int rcgan_conv2d_bwd_data_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, con
   return RCGAN_OK;
 }
 
-// The matrix-core filter-gradient problem of a layer (everything but the slab).  Upsample-3x3 and ConvMeanPool layers the
-// three-tap kernel takes are posed in their sub-pixel form (MfmaWgradArgs::sub): reduction over the low-resolution grid.
-static void wgrad_args_from_desc(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy, bool want_bias, MfmaWgradArgs& a) {
+// The matrix-core filter-gradient problem of a layer (everything but the slab) and the number of pixel chunks its slabs are sized for.
+// Upsample-3x3 and ConvMeanPool layers the three-tap kernel takes are posed in their sub-pixel form (MfmaWgradArgs::sub): reduction over
+// the low-resolution grid.
+static int wgrad_pose(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy, bool want_bias, MfmaWgradArgs& a, int* nz) {
   int oh, ow, pt, pl;
   same_pad(d->h, d->kh, 1, &oh, &pt);
   same_pad(d->w, d->kw, 1, &ow, &pl);
@@ -1012,6 +986,8 @@ static void wgrad_args_from_desc(rcgan_ctx* ctx, const rcgan_conv_desc* d, const
   a.relu_in = (d->flags & RCGAN_CONV_IN_RELU) ? 1 : 0;
   a.use_tr = g_use_tr;
   a.sub = mfma_wgrad_sub_kind(d, g_use_tr);
+  if ((d->flags & RCGAN_CONV_OUT_MEANPOOL2) && a.sub != 2)
+    RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "filter gradient from the pooled dy needs the sub-pixel three-tap kernel (rcgan_conv_wgrad_pool_ok)");
   if (a.sub == 1 || a.sub == 2) { a.H >>= 1; a.W >>= 1; a.up = 0; }
   a.cells = (a.sub == 1 || a.sub == 2) ? 16 : d->kh * d->kw;
   a.M = (long)d->n * a.H * a.W;
@@ -1020,6 +996,8 @@ static void wgrad_args_from_desc(rcgan_ctx* ctx, const rcgan_conv_desc* d, const
   a.slab_stride = (long)a.cells * d->cin * d->cout + d->cout;
   a.want_bias = want_bias ? 1 : 0;
   a.m_chunk = 0;
+  *nz = a.sub ? mfma_wgrad_sub_splits(d, a.M) : mfma_wgrad_splits(d, a.M);
+  return RCGAN_OK;
 }
 
 static SlabReduceGroup::Item wgrad_reduce_item(const rcgan_conv_desc* d, const MfmaWgradArgs& a, float* dw, float* dbias, int nbias, int nz, int accumulate) {
@@ -1047,11 +1025,10 @@ int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void
     rc = ensure_selftest(ctx);
     if (rc) return rc;
     MfmaWgradArgs a;
-    wgrad_args_from_desc(ctx, d, x, dy, dbias != nullptr, a);
-    if ((d->flags & RCGAN_CONV_OUT_MEANPOOL2) && a.sub != 2)
-      RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "filter gradient from the pooled dy needs the sub-pixel three-tap kernel (rcgan_conv_wgrad_pool_ok)");
+    int nz = 0;
+    rc = wgrad_pose(ctx, d, x, dy, dbias != nullptr, a, &nz);
+    if (rc) return rc;
     a.slab = (float*)ws;
-    int nz = a.sub ? mfma_wgrad_sub_splits(d, a.M) : mfma_wgrad_splits(d, a.M);
     long cnt = (long)d->kh * d->kw * d->cin * d->cout;
     size_t need = (size_t)nz * a.slab_stride * sizeof(float) + (size_t)(cdiv(a.M, 2048) + 1024) * d->cout * sizeof(float);
     if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
@@ -1083,6 +1060,20 @@ int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void
   return RCGAN_OK;
 }
 
+// The family (vector of planned problems) among fam[0, nfam) whose launch has the most workgroups; -1 if none qualifies.  Only the first
+// `counted` problems of a family count; skip_empty: a family without problems is no candidate; later_wins_ties: >= instead of >.
+static int wgrad_busiest_family(const std::vector<MfmaWgradPlanned>* fam, int nfam, size_t counted, bool skip_empty, bool later_wins_ties) {
+  int best_f = -1;
+  unsigned best = 0;
+  for (int f = 0; f < nfam; ++f) {
+    if (skip_empty && fam[f].empty()) continue;
+    unsigned tot = 0;
+    for (size_t q = 0; q < fam[f].size() && q < counted; ++q) tot += fam[f][q].gx * fam[f][q].gy;
+    if (best_f < 0 || (later_wins_ties ? tot >= best : tot > best)) { best = tot; best_f = f; }
+  }
+  return best_f;
+}
+
 // Filter gradients of several layers whose x / dy are all available (the end of a backward pass): the layers the
 // three-tap matrix-core kernel takes run as ONE grouped launch per input-ReLU flavour + ONE grouped slab reduction; every
 // other layer goes through rcgan_conv2d_bwd_weight as usual.
@@ -1090,8 +1081,8 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
                                   float* const* dws, float* const* dbiases, int accumulate, void* ws, size_t ws_bytes) {
   RC_REQUIRE(ctx, n >= 0 && (n == 0 || (descs && xs && dys && dws && dbiases)), "null argument");
   static const int target_blocks = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_BLOCKS"); return e ? atoi(e) : 448; }();      // (512 before the sub-pixel forms: 6.67 -> 6.64 ms with 384; round 4, the critic step's launch with its chunks' workgroups on one XCD and the generator step's big layers gone to the nine-tap kernel, same box: 384 5.65 ms, 448 5.59, 512 5.60, 576 5.75)
-  std::vector<MfmaWgradArgs> cand(n);
-  std::vector<char> takes(n, 0);
+  struct Cand { MfmaWgradArgs a; int nz; int takes; };      // takes: 0 not grouped, 1 three-tap kernel, 2 / 3 nine-tap kernel plain / sub-pixel
+  std::vector<Cand> cand(n);
   // The nine-tap kernel (conv_wgrad9.hip) takes the group's 3x3 layers when they are big: its one workgroup per CU writes a slab of ALL nine
   // (sixteen) cells, and the riders of the three-tap launch (image-end layers, 1x1 shortcuts, the head) lose the workgroups they hid under.
   // Measured on the bench iteration: the critic step's layers (n = 128, 128 channels: 1152 pixels per workgroup) 120 -> 172 us with it, the
@@ -1116,15 +1107,14 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
     if (!mfma_wgrad_eligible(d)) continue;
     rc = ensure_selftest(ctx);
     if (rc) return rc;
-    MfmaWgradArgs& a = cand[i];
-    wgrad_args_from_desc(ctx, d, xs[i], dys[i], dbiases[i] != nullptr, a);
-    if ((d->flags & RCGAN_CONV_OUT_MEANPOOL2) && a.sub != 2)
-      RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "filter gradient from the pooled dy needs the sub-pixel three-tap kernel (rcgan_conv_wgrad_pool_ok)");
+    MfmaWgradArgs& a = cand[i].a;
+    rc = wgrad_pose(ctx, d, xs[i], dys[i], dbiases[i] != nullptr, a, &cand[i].nz);
+    if (rc) return rc;
     if (mfma_wgrad9_takes(a) && wgrad9_group_on) {
-      takes[i] = a.sub ? 3 : 2;
+      cand[i].takes = a.sub ? 3 : 2;
       work9[a.sub ? 1 : 0] += (double)a.M * (a.Cin / 64) * (a.Cout / 128) * (a.sub ? 2 : 1);
     } else if (mfma_wgrad3_takes(a)) {
-      takes[i] = 1;
+      cand[i].takes = 1;
       // workgroup-passes over a pixel: 3 filter rows of three taps, or 8 (parity, row shift) tiles of two taps
       work += (double)a.M * (a.sub == 3 ? 1.0 / 3.0 : (a.sub ? 8 * 2.0 / 3.0 : a.KH)) * (a.Cin / 64) * (a.Cout / 128);
     }
@@ -1144,21 +1134,18 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
     for (int it = 0; it < 4096 && work9[f] > 0; ++it, px9[f] += 128) {
       long tot = 0;
       for (int i = 0; i < n; ++i)
-        if (takes[i] == 2 + f) {
-          MfmaWgradArgs b = cand[i];
+        if (cand[i].takes == 2 + f) {
+          MfmaWgradArgs b = cand[i].a;
           unsigned bgx = 0, bgy = 0;
           if (mfma_wgrad9_plan(b, 1 << 20, &bgx, &bgy, px9[f])) tot += (long)bgx * bgy;
         }
       if (tot <= target9) break;
     }
   }
-  std::vector<MfmaWgradArgs> args9[4];           // nine-tap kernel: plain without / with input ReLU, sub-pixel forms without / with
-  std::vector<unsigned> gxs9[4], gys9[4];
+  std::vector<MfmaWgradPlanned> fam9[4];         // nine-tap kernel: plain without / with input ReLU, sub-pixel forms without / with
   // pass 2: slabs, grouped launches per input-ReLU flavour, everything else on its own
-  std::vector<MfmaWgradArgs> args[3];            // three-tap kernel without / with input ReLU, per-tap kernel
-  std::vector<MfmaWgradArgs> late;               // small 1x1 layers on the two-tap body: join one of the first two
-  std::vector<unsigned> late_gx, late_gy;
-  std::vector<unsigned> gxs[3], gys[3];
+  std::vector<MfmaWgradPlanned> fam[3];          // three-tap kernel without / with input ReLU, per-tap kernel
+  std::vector<MfmaWgradPlanned> late;            // small 1x1 layers on the two-tap body: join one of the first two
   std::vector<SlabReduceGroup::Item> red;
   size_t used = 0;
   // image-end layers ride in the first grouped launch (if there is one) and in the grouped reduction
@@ -1167,7 +1154,7 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
   for (int q = 0; q <= IMG_GROUP_MAX; ++q) img.first[q] = 0;
   static const int img_group = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_IMG"); return e ? atoi(e) : 1; }();
   bool any_group = false;
-  for (int i = 0; i < n && img_group; ++i) any_group = any_group || takes[i] == 1;
+  for (int i = 0; i < n && img_group; ++i) any_group = any_group || cand[i].takes == 1;
   for (int i = 0; i < n; ++i) {
     const rcgan_conv_desc* d = descs + i;
     bool grouped = false;
@@ -1199,23 +1186,22 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
       }
     }
     if (!grouped && mfma_wgrad_eligible(d)) {
-      MfmaWgradArgs a = cand[i];
-      const int nz = a.sub ? mfma_wgrad_sub_splits(d, a.M) : mfma_wgrad_splits(d, a.M);
-      unsigned gx = 0, gy = 0;
+      MfmaWgradPlanned p = {cand[i].a, 0, 0};
+      MfmaWgradArgs& a = p.a;
+      const int nz = cand[i].nz, takes = cand[i].takes;
       // (the grouped slabs are fitted into the workspace below: no a-priori bound on the nine-tap kernel's pixel chunks)
-      const bool nine = takes[i] >= 2 && mfma_wgrad9_plan(a, 1 << 20, &gx, &gy, px9[takes[i] - 2]);
-      const bool three = !nine && takes[i] && mfma_wgrad3_plan(a, nz, &gx, &gy, px);
+      const bool nine = takes >= 2 && mfma_wgrad9_plan(a, 1 << 20, &p.gx, &p.gy, px9[takes - 2]);
+      const bool three = !nine && takes && mfma_wgrad3_plan(a, nz, &p.gx, &p.gy, px);
       if (a.sub && !three && !nine) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "sub-pixel filter gradient needs the three-tap kernel");
-      if (nine || three || mfma_wgrad_tap_plan(a, nz, &gx, &gy)) {
-        const size_t need = ((size_t)gy * a.slab_stride * sizeof(float) + 255) / 256 * 256;
+      if (nine || three || mfma_wgrad_tap_plan(a, nz, &p.gx, &p.gy)) {
+        const size_t need = ((size_t)p.gy * a.slab_stride * sizeof(float) + 255) / 256 * 256;
         if (used + need <= ws_bytes / 2) {
           a.slab = (float*)((char*)ws + used);
           used += need;
-          const int f = three ? (a.relu_in ? 1 : 0) : 2;
-          if (nine) { const int f9 = (a.sub ? 2 : 0) + (a.relu_in ? 1 : 0); args9[f9].push_back(a); gxs9[f9].push_back(gx); gys9[f9].push_back(gy); }
-          else if (three && a.sub == 3 && !a.relu_in) { late.push_back(a); late_gx.push_back(gx); late_gy.push_back(gy); }   // placed below
-          else { args[f].push_back(a); gxs[f].push_back(gx); gys[f].push_back(gy); }
-          red.push_back(wgrad_reduce_item(d, a, dws[i], dbiases[i], dbiases[i] ? d->cout : 0, (int)gy, accumulate));
+          if (nine) fam9[(a.sub ? 2 : 0) + (a.relu_in ? 1 : 0)].push_back(p);
+          else if (three && a.sub == 3 && !a.relu_in) late.push_back(p);       // placed below
+          else fam[three ? (a.relu_in ? 1 : 0) : 2].push_back(p);
+          red.push_back(wgrad_reduce_item(d, a, dws[i], dbiases[i], dbiases[i] ? d->cout : 0, (int)p.gy, accumulate));
           grouped = true;
         }
       }
@@ -1225,48 +1211,33 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
       if (rc) return rc;
     }
   }
-  // a riding 1x1 without input ReLU runs on either flavour of the three-tap kernel (the ReLU is a per-problem switch in the two-tap
-  // body): it joins the launch with the most workgroups
+  // Three riders each hide under the family of grouped launches with the most workgroups.  Their rules differ, and the differences decide
+  // which launch a rider lengthens (the bench iteration's timings were taken with exactly these): do not unify them.
+  // * a riding 1x1 without input ReLU runs on either flavour of the three-tap kernel (the ReLU is a per-problem switch in the two-tap
+  //   body): every planned problem counts, it may open a family of its own (an empty one is a candidate), and a tie stays with family 0
   if (!late.empty()) {
-    unsigned tot[2] = {0, 0};
-    for (int f = 0; f < 2; ++f)
-      for (size_t q = 0; q < args[f].size(); ++q) tot[f] += gxs[f][q] * gys[f][q];
-    const int f = tot[1] > tot[0] ? 1 : 0;
-    for (size_t q = 0; q < late.size(); ++q) { args[f].push_back(late[q]); gxs[f].push_back(late_gx[q]); gys[f].push_back(late_gy[q]); }
+    const int f = wgrad_busiest_family(fam, 2, (size_t)-1, false, false);
+    fam[f].insert(fam[f].end(), late.begin(), late.end());
   }
-  // the image-end workgroups go with the launch that has the most workgroups to hide under
+  // * the image-end workgroups ride in a family's FIRST launch (mfma_wgrad3_group_launch: WGRAD_GROUP_MAX_HOST problems) -- deliberately only
+  //   those count and the family must exist; a tie goes to the later one, and the per-tap family (2) is a candidate
   int img_f = -1;
   if (img.n) {
-    unsigned best = 0;
-    for (int f = 0; f < 3; ++f) {
-      unsigned tot = 0;
-      for (size_t q = 0; q < args[f].size() && q < WGRAD_GROUP_MAX_HOST; ++q) tot += gxs[f][q] * gys[f][q];
-      if (!args[f].empty() && tot >= best) { best = tot; img_f = f; }
-    }
+    img_f = wgrad_busiest_family(fam, 3, WGRAD_GROUP_MAX_HOST, true, true);
     RC_REQUIRE(ctx, img_f >= 0, "image-end filter gradients planned without a grouped launch");
   }
-  // the projection head's deferred parameter sums (head_rider.h) ride in the three-tap launch with the most workgroups
+  // * the projection head's deferred parameter sums (head_rider.h) need a three-tap launch (families 0, 1): they follow the image-end
+  //   workgroups there, else the same rule over those two
   int head_f = -1;
-  if (ctx->head_stage == 2) {
-    if (img_f == 0 || img_f == 1) head_f = img_f;
-    else {
-      unsigned best = 0;
-      for (int f = 0; f < 2; ++f) {
-        unsigned tot = 0;
-        for (size_t q = 0; q < args[f].size() && q < WGRAD_GROUP_MAX_HOST; ++q) tot += gxs[f][q] * gys[f][q];
-        if (!args[f].empty() && tot >= best) { best = tot; head_f = f; }
-      }
-    }
-  }
+  if (ctx->head_stage == 2) head_f = (img_f == 0 || img_f == 1) ? img_f : wgrad_busiest_family(fam, 2, WGRAD_GROUP_MAX_HOST, true, true);
   for (int f = 0; f < 4; ++f)
-    if (!args9[f].empty()) {
-      int rc = mfma_wgrad9_group_launch(ctx, (int)args9[f].size(), args9[f].data(), gxs9[f].data(), gys9[f].data());
+    if (!fam9[f].empty()) {
+      int rc = mfma_wgrad9_group_launch(ctx, (int)fam9[f].size(), fam9[f].data());
       if (rc) return rc;
     }
   for (int f = 0; f < 3; ++f)
-    if (!args[f].empty()) {
-      int rc = mfma_wgrad3_group_launch(ctx, (int)args[f].size(), args[f].data(), gxs[f].data(), gys[f].data(), f == 2 ? 1 : 0,
-                                        f == img_f ? &img : nullptr, f == head_f);
+    if (!fam[f].empty()) {
+      int rc = mfma_wgrad3_group_launch(ctx, (int)fam[f].size(), fam[f].data(), f == 2 ? 1 : 0, f == img_f ? &img : nullptr, f == head_f);
       if (rc) return rc;
     }
   for (size_t i0 = 0; i0 < red.size(); i0 += REDUCE_GROUP_MAX) {

@@ -26,7 +26,7 @@ struct MfmaConvArgs {
   // [phase = ph*2 + pw][Cout][(a*2 + b)*Cin + ci] (conv_prepare_phase_kernel), phase = 1: use them.  phase = 2: the data
   // gradient of that form, wph = [Cin][(u*4 + v)*Cout + co] (16 taps at source stride 2 over the full-resolution dy).
   const bf16_t* wph;
-  int phase;
+  int phase;              // MFMA_FORM_* below
   // eight-wave 256 x 256 kernel only: per-tile column sums of the stored output and of its squares, [pixel tile][Cout][2] fp32 --
   // the batch-norm statistics of the layer behind this convolution come out of its epilogue (bn.hip: bn_tile_stats_finish_kernel)
   float* stats;
@@ -41,6 +41,24 @@ struct MfmaConvArgs {
   const int32_t* bn_labels = nullptr;
   int bn_seg_samples = 1, bn_act = 0;
 };
+
+// MfmaConvArgs::phase.  (The kernels compare it with the literals.)
+constexpr int MFMA_FORM_PLAIN = 0;      // KH x KW taps over the output grid; with `up` and `wph` the eight-wave / 64 x 64 kernels may still evaluate it sub-pixel
+constexpr int MFMA_FORM_PHASE = 1;      // forced: four 2x2 convolutions over the low-resolution grid, filters = wph in the phase layout
+constexpr int MFMA_FORM_GATHER = 2;     // forced: one 4x4 stride-2 convolution over the full-resolution grid, filters = wph in the gather layout
+
+// The prepared buffer of a matrix-core layer, in 16-bit elements from its start (rcgan_conv_prepared_bytes sizes it, rcgan_conv_prepare /
+// conv_prepare_batch_launch write it, api.hip's mfma_conv_pose reads it):
+//   [0, T cin cout)              the forward layout [Cout][T*Cin]
+//   [mfma_prepared_rot, ...)     the data gradient's: rotated taps, [Cin][T*Cout]
+// and, where mfma_phase_filters(d), two blocks of 16 cin cout summed sub-pixel filters (conv_prepare_phase_kernel / prepare_phase_units
+// get the first block's address and place the second themselves):
+//   [mfma_prepared_sum_fwd, ...) the layer's FORWARD: phase layout of an upsample-3x3, gather layout of a ConvMeanPool
+//   [mfma_prepared_sum_bwd, ...) its DATA GRADIENT: gather layout of an upsample-3x3, phase layout of a ConvMeanPool
+static inline size_t mfma_prepared_rot(const rcgan_conv_desc* d) { return (size_t)d->kh * d->kw * d->cin * d->cout; }
+static inline size_t mfma_prepared_sum_fwd(const rcgan_conv_desc* d) { return 2 * mfma_prepared_rot(d); }
+static inline size_t mfma_prepared_sum_bwd(const rcgan_conv_desc* d) { return mfma_prepared_sum_fwd(d) + 16 * (size_t)d->cin * d->cout; }
+static inline size_t mfma_prepared_sum_end(const rcgan_conv_desc* d) { return mfma_prepared_sum_bwd(d) + 16 * (size_t)d->cin * d->cout; }
 
 struct MfmaWgradArgs {
   const bf16_t* x;        // [N][H(/2)][W(/2)][Cin]
@@ -73,6 +91,9 @@ static inline int wgrad3_rows(const MfmaWgradArgs& a) { return a.sub == 3 ? 1 : 
 static inline int wgrad3_alg_taps(const MfmaWgradArgs& a) { return a.sub == 3 ? 1 : (a.sub ? 36 : a.KH * a.KW); }
 static inline int wgrad3_exec_taps(const MfmaWgradArgs& a) { return a.sub == 3 ? 1 : (a.sub ? 16 : a.KH * a.KW); }
 
+// a filter-gradient problem planned into a grouped launch: gx tiles x gy pixel chunks of workgroups
+struct MfmaWgradPlanned { MfmaWgradArgs a; unsigned gx, gy; };
+
 static inline int ilog2_exact(int v) {
   int l = 0;
   while ((1 << l) < v) ++l;
@@ -96,14 +117,13 @@ bool mfma_wgrad3_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy, long
 bool mfma_wgrad3_takes(const MfmaWgradArgs& a);
 int mfma_wgrad_sub_kind(const rcgan_conv_desc* d, int use_tr);
 int mfma_wgrad_sub_splits(const rcgan_conv_desc* d, long M);
-int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradArgs* args, const unsigned* gx, const unsigned* gy, int family,
-                             const ImgWGroup* img, bool carry_head = false);
+int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs, int family, const ImgWGroup* img, bool carry_head = false);
 bool mfma_wgrad_tap_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy);
 // conv_wgrad9.hip: all nine taps of a plain 3x3 layer in one workgroup (dy and x staged once for the three filter rows)
 #define WGRAD9_GROUP_MAX 12
 bool mfma_wgrad9_takes(const MfmaWgradArgs& a);
 bool mfma_wgrad9_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy, long px_per_block);
-int mfma_wgrad9_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradArgs* args, const unsigned* gx, const unsigned* gy);
+int mfma_wgrad9_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs);
 int mfma_wgrad_launch(rcgan_ctx* ctx, MfmaWgradArgs& a, int nz, bool* bias_done, size_t ws_bytes);
 int mfma_prepare_launch(rcgan_ctx* ctx, const float* w, const float* sigma, bf16_t* wt, bf16_t* wd, int T, int Cin, int Cout);
 int direct_prepare_launch(rcgan_ctx* ctx, const float* w, const float* sigma, float* out, long total);

@@ -1506,7 +1506,7 @@ int conv_prepare_batch_launch(rcgan_ctx* ctx, const rcgan_prepare_item* items, i
     const rcgan_conv_desc& d = items[i].desc;
     if (!mfma_phase_filters(&d)) continue;
     pw_.push_back(items[i].w); ps_.push_back(items[i].sigma);
-    po_.push_back((bf16_t*)items[i].prepared + 2 * (size_t)d.kh * d.kw * d.cin * d.cout);
+    po_.push_back((bf16_t*)items[i].prepared + mfma_prepared_sum_fwd(&d));
     pci.push_back(d.cin); pco.push_back(d.cout); pk.push_back((d.flags & RCGAN_CONV_OUT_MEANPOOL2) ? 1 : 0);
   }
   int nride = ride ? (int)pw_.size() : 0;
@@ -1784,12 +1784,12 @@ static ConvRoute mfma_conv_route(const MfmaConvArgs& a) {
   static const int halo = env_int("RCGAN_P8_HALO", 1), halo_n = env_int("RCGAN_P8N_HALO", 1);
   static const int t128_min = env_int("RCGAN_T128_MINBLK", 384);
   static const int t256_min = env_int("RCGAN_T256_MINBLK", 1 << 30);     // experiment: 256-pixel tiles (1 wave/SIMD)
-  if (a.phase == 1 || a.phase == 2) {
+  if (a.phase == MFMA_FORM_PHASE || a.phase == MFMA_FORM_GATHER) {
     // forced sub-pixel forms.  1: the data gradient of a ConvMeanPool (a.wt is not a usable fallback); 2: the data gradient of the sub-pixel
     // form (the caller checked mfma_phase_dgrad_ok).  256-pixel tiles where the grid fills the chip, else the 64 x 64 kernel
-    const bool whole = a.phase == 1 ? ((a.M >> 2) % 256 == 0) : (a.M % 256 == 0);
+    const bool whole = a.phase == MFMA_FORM_PHASE ? ((a.M >> 2) % 256 == 0) : (a.M % 256 == 0);
     const long b8 = (a.M / 256) * (a.Cout / 256), b8n = (a.M / 256) * (a.Cout / 128);
-    if (a.phase == 2) {
+    if (a.phase == MFMA_FORM_GATHER) {
       // (round 5) the parity-plane patch form of the 256 x 128 halo kernel where its tiles fill the chip: G.Block.3.Conv1's data gradient
       // (128 x 2 tiles) 78 -> 61 us.  Measured and left to the 64 x 64 kernel: D.Block.1.Conv2's forward (128 tiles = half the CUs) 33 -> 37 us
       // (RCGAN_H8N_GATHER_MINBLK=120 takes it too; 100000 switches the form off -- since round 6 really off: the 256 x 128 tile-per-tap
@@ -1800,13 +1800,13 @@ static ConvRoute mfma_conv_route(const MfmaConvArgs& a) {
     if (whole && a.Cout % 256 == 0 && b8 >= p8_min && 4 * b8 >= 3 * (long)cdiv(b8, 256) * 256)
       return (halo && !a.stats && mfma_conv8_halo_takes(a)) ? CR_H8 : CR_P8;
     if (whole && a.Cout % 128 == 0 && b8n >= p8n_min)
-      return (a.phase == 1 && halo_n && mfma_conv8n_halo_takes(a)) ? CR_H8N : CR_P8N;
+      return (a.phase == MFMA_FORM_PHASE && halo_n && mfma_conv8n_halo_takes(a)) ? CR_H8N : CR_P8N;
     // (measured in round 5 and not kept: 128 x 128 tiles of the 64 x 64 kernel for D.Block.1.Conv2's forward -- 256 tiles, one per CU, against
     // 1024 of 64 x 64 -- same-box 5.20 -> 5.25 ms; for every 16-tap layer 5.40)
     return (a.M / 64) * (a.Cout / 64) <= ks2_max ? CR_PHASE_KS2 : CR_PHASE;
   }
   MfmaConvArgs b = a;
-  b.phase = mfma_conv8_phase_form(a) ? 1 : 0;                         // what mfma_conv8_launch will run it as
+  b.phase = mfma_conv8_phase_form(a) ? MFMA_FORM_PHASE : MFMA_FORM_PLAIN;       // what mfma_conv8_launch will run it as
   const bool off32 = (long)a.N * a.H * a.W * a.Cin < (1L << 32);      // the tap-source table holds 32-bit element offsets
   // one 256 x 256 workgroup per CU: a grid of 320 runs two rounds for 1.25 rounds of work -- such grids go to the
   // 256 x 128 kernel (twice the workgroups, finer rounds) when less than 3/4 of the last round would be busy
@@ -1822,7 +1822,7 @@ static ConvRoute mfma_conv_route(const MfmaConvArgs& a) {
 
 // an ordinary (phase 0 on entry) forward / data-gradient launch that runs on a 256 x 256 eight-wave kernel
 bool mfma_conv_is_p8(const MfmaConvArgs& a) {
-  if (a.phase != 0 || a.Cin % 64 || a.Cout % 64) return false;
+  if (a.phase != MFMA_FORM_PLAIN || a.Cin % 64 || a.Cout % 64) return false;
   const ConvRoute r = mfma_conv_route(a);
   return r == CR_H8 || r == CR_P8;
 }
@@ -1830,7 +1830,7 @@ bool mfma_conv_is_p8(const MfmaConvArgs& a) {
 // Does this (phase 0 on entry) forward launch run on one of the halo-patch kernels -- the ones that can apply a batch norm to their
 // staged input (MfmaConvArgs::bn_*)?  1: 256 x 256 tile, 2: 256 x 128 tile, 0: no.
 int mfma_conv_bn_route(const MfmaConvArgs& a) {
-  if (a.phase != 0 || a.Cin % 64 || a.Cout % 64 || a.zero == nullptr || a.stats || a.relu_in || a.Cin > 1024) return 0;
+  if (a.phase != MFMA_FORM_PLAIN || a.Cin % 64 || a.Cout % 64 || a.zero == nullptr || a.stats || a.relu_in || a.Cin > 1024) return 0;
   const ConvRoute r = mfma_conv_route(a);
   return r == CR_H8 ? 1 : r == CR_H8N ? 2 : 0;
 }
@@ -1840,15 +1840,15 @@ int mfma_conv_launch(rcgan_ctx* ctx, const MfmaConvArgs& a_in) {
   a.stamps = (unsigned long long*)ctx->dbg_stamps;       // diagnostics (rcgan_debug_stamps), normally null
   if (a.Cin % 64 || a.Cout % 64) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "channels %d -> %d", a.Cin, a.Cout);
   const ConvRoute r = mfma_conv_route(a);
-  if (a.bn_mean && !(a.phase == 0 && !a.stats && !a.relu_in && a.Cin <= 1024 && a.zero != nullptr && (r == CR_H8 || r == CR_H8N)))
+  if (a.bn_mean && !(a.phase == MFMA_FORM_PLAIN && !a.stats && !a.relu_in && a.Cin <= 1024 && a.zero != nullptr && (r == CR_H8 || r == CR_H8N)))
     RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "batch norm on the staged input needs a halo-patch kernel (rcgan_conv_bn_in_ok)");
-  if (a.stats && !(a.phase == 0 && a.zero != nullptr && (r == CR_H8 || r == CR_P8)))
+  if (a.stats && !(a.phase == MFMA_FORM_PLAIN && a.zero != nullptr && (r == CR_H8 || r == CR_P8)))
     RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "tile statistics need the 256 x 256 kernel (rcgan_conv_stats_ok)");
   switch (r) {
     case CR_H8: case CR_P8: return mfma_conv8_launch(ctx, a, true, r == CR_H8);
     case CR_H8N: case CR_P8N: return mfma_conv8_launch(ctx, a, false, r == CR_H8N);
-    case CR_PHASE_KS2: return a.phase == 1 ? launch_conv_glds_phase<64, 64, 2, 2, 1>(ctx, a) : launch_conv_glds_phase<64, 64, 2, 2, 2>(ctx, a);
-    case CR_PHASE: return a.phase == 1 ? launch_conv_glds_phase<64, 64, 2, 1, 1>(ctx, a) : launch_conv_glds_phase<64, 64, 2, 1, 2>(ctx, a);
+    case CR_PHASE_KS2: return a.phase == MFMA_FORM_PHASE ? launch_conv_glds_phase<64, 64, 2, 2, 1>(ctx, a) : launch_conv_glds_phase<64, 64, 2, 2, 2>(ctx, a);
+    case CR_PHASE: return a.phase == MFMA_FORM_PHASE ? launch_conv_glds_phase<64, 64, 2, 1, 1>(ctx, a) : launch_conv_glds_phase<64, 64, 2, 1, 2>(ctx, a);
     case CR_T256: return launch_conv_glds<256, 256, 2>(ctx, a);
     case CR_T256N: return launch_conv_glds<256, 128, 2>(ctx, a);
     case CR_T128: return launch_conv_mfma<128, 128>(ctx, a);
@@ -1951,16 +1951,15 @@ int mfma_wgrad_launch(rcgan_ctx* ctx, MfmaWgradArgs& a, int nz, bool* bias_done,
     // 21 -> 28, the sub-pixel forms 43 -> 83 / 122 -> 128: those stay on the three-tap kernel)
     const long min_work = env_int("RCGAN_WGRAD9_MINWORK", 200000);        // (read per call: the tests force the kernel on small shapes)
     const long work9 = a.M * (long)(a.Cin / 64) * (a.Cout / 128);
-    unsigned gx9 = 0, gy9 = 0;
     // (planned on a copy: the plan rewrites slab_stride -- the upsample form carries two bias tails per slab -- AFTER the caller sized
     // the workspace for the stride it knew; the nine-tap kernel only runs if its slabs fit what the caller really handed over)
-    MfmaWgradArgs a9 = a;
-    if ((a.sub ? min_work <= 0 : work9 >= min_work) && mfma_wgrad9_plan(a9, nz, &gx9, &gy9, 0) &&
-        (size_t)gy9 * (size_t)a9.slab_stride * sizeof(float) <= ws_bytes) {
-      a = a9;
-      int rc = mfma_wgrad9_group_launch(ctx, 1, &a, &gx9, &gy9);
+    MfmaWgradPlanned p9 = {a, 0, 0};
+    if ((a.sub ? min_work <= 0 : work9 >= min_work) && mfma_wgrad9_plan(p9.a, nz, &p9.gx, &p9.gy, 0) &&
+        (size_t)p9.gy * (size_t)p9.a.slab_stride * sizeof(float) <= ws_bytes) {
+      a = p9.a;
+      int rc = mfma_wgrad9_group_launch(ctx, 1, &p9);
       *bias_done = a.want_bias != 0;
-      return rc ? -1 : (int)gy9;
+      return rc ? -1 : (int)p9.gy;
     }
   }
   if (wgrad3_enabled() && a.use_tr && a.zero != nullptr && wgrad3_geom(a)) {
@@ -2075,10 +2074,9 @@ bool mfma_wgrad_tap_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy) {
   return true;
 }
 
-// args[i] planned by mfma_wgrad3_plan (family 0; all with the same relu_in) or mfma_wgrad_tap_plan (family 1)
+// probs[i] planned by mfma_wgrad3_plan (family 0; all with the same relu_in) or mfma_wgrad_tap_plan (family 1)
 // img (optional): image-end problems that ride in the FIRST launch
-int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradArgs* args, const unsigned* gx, const unsigned* gy, int family,
-                             const ImgWGroup* img, bool carry_head) {
+int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs, int family, const ImgWGroup* img, bool carry_head) {
   static_assert(ImgWGeom<128>::LDS <= 4 * (40 * 128 + 32 * 256), "image-end body needs more LDS than the three-tap kernel");
   static_assert((HEAD_MAX_V + 1) * HEAD_MAX_D * 4 <= 4 * (40 * 128 + 32 * 256), "head body needs more LDS than the three-tap kernel");
   for (int i0 = 0; i0 < n; i0 += WGRAD_GROUP_MAX) {
@@ -2092,15 +2090,15 @@ int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradArgs* args, c
     g.n = (n - i0 < WGRAD_GROUP_MAX) ? n - i0 : WGRAD_GROUP_MAX;
     unsigned tot = 0;
     for (int p = 0; p < g.n; ++p) {
-      g.a[p] = args[i0 + p];
-      g.gx[p] = gx[i0 + p];
+      g.a[p] = probs[i0 + p].a;
+      g.gx[p] = probs[i0 + p].gx;
       g.first[p] = tot;
-      tot += gx[i0 + p] * gy[i0 + p];
+      tot += probs[i0 + p].gx * probs[i0 + p].gy;
     }
     for (int p = g.n; p <= WGRAD_GROUP_MAX; ++p) g.first[p] = tot;
-    for (int p = g.n; p < WGRAD_GROUP_MAX; ++p) { g.gx[p] = 1; g.a[p] = args[i0]; }
+    for (int p = g.n; p < WGRAD_GROUP_MAX; ++p) { g.gx[p] = 1; g.a[p] = probs[i0].a; }
     int rc = family == 1 ? launch_wgrad_glds_group(ctx, g)
-                         : (args[i0].relu_in ? launch_wgrad3_group<true>(ctx, g) : launch_wgrad3_group<false>(ctx, g));
+                         : (probs[i0].a.relu_in ? launch_wgrad3_group<true>(ctx, g) : launch_wgrad3_group<false>(ctx, g));
     if (rc) return rc;
   }
   return RCGAN_OK;

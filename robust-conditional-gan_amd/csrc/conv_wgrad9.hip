@@ -433,21 +433,21 @@ static int launch_wgrad9_group(rcgan_ctx* ctx, const Wgrad9Group& g) {
   return RCGAN_OK;
 }
 
-// args[i] planned by mfma_wgrad9_plan, all with the same relu_in and all plain or all sub-pixel forms
-int mfma_wgrad9_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradArgs* args, const unsigned* gx, const unsigned* gy) {
+// probs[i] planned by mfma_wgrad9_plan, all with the same relu_in and all plain or all sub-pixel forms
+int mfma_wgrad9_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs) {
   for (int i0 = 0; i0 < n; i0 += WGRAD9_GROUP_MAX) {
     Wgrad9Group g;
     g.n = (n - i0 < WGRAD9_GROUP_MAX) ? n - i0 : WGRAD9_GROUP_MAX;
     unsigned tot = 0;
     for (int p = 0; p < g.n; ++p) {
-      g.a[p] = args[i0 + p];
-      g.gx[p] = gx[i0 + p];
+      g.a[p] = probs[i0 + p].a;
+      g.gx[p] = probs[i0 + p].gx;
       g.first[p] = tot;
-      tot += gx[i0 + p] * gy[i0 + p];
+      tot += probs[i0 + p].gx * probs[i0 + p].gy;
     }
     for (int p = g.n; p <= WGRAD9_GROUP_MAX; ++p) g.first[p] = tot;
-    for (int p = g.n; p < WGRAD9_GROUP_MAX; ++p) { g.gx[p] = 1; g.a[p] = args[i0]; }
-    const bool subk = args[i0].sub != 0, relu = args[i0].relu_in != 0;
+    for (int p = g.n; p < WGRAD9_GROUP_MAX; ++p) { g.gx[p] = 1; g.a[p] = probs[i0].a; }
+    const bool subk = probs[i0].a.sub != 0, relu = probs[i0].a.relu_in != 0;
     int rc = subk ? (relu ? launch_wgrad9_group<true, true>(ctx, g) : launch_wgrad9_group<false, true>(ctx, g))
                   : (relu ? launch_wgrad9_group<true, false>(ctx, g) : launch_wgrad9_group<false, false>(ctx, g));
     if (rc) return rc;
