@@ -541,6 +541,36 @@ int rcgan_softmax_rows_fwd(rcgan_ctx* ctx, int rows, int cols, const float* logi
 int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, const float* dp, float* dlogits,
                            int accumulate);
 
+/* ---- training the generated-label-accuracy classifier (csrc/classifier.hip; fp32 model, classifier.py) -------------------- */
+/* Sparse softmax cross-entropy (tf.nn.sparse_softmax_cross_entropy_with_logits + reduce_mean), one launch:
+ *   *loss_acc      += weight * mean_rows(-log softmax(logits)[label])
+ *   *n_correct_acc += the number of rows whose arg-max (lowest index on ties) equals the label   (fp32 scalar; may be NULL)
+ *   dlogits         = weight * (softmax - onehot) / rows, times the scale of rcgan_set_grad_scale   (may be NULL: evaluation)
+ * cols 2..1024, any rows; max-subtracted, log-sum-exp in fp32.  A wavefront per row; the sums over rows are per-workgroup partials
+ * in ws finished in workgroup order by the last workgroup to arrive (no floating-point atomics: the same bits run to run).
+ * ws: rcgan_softmax_xent_workspace_bytes(rows).  A label outside [0, cols) contributes nothing. */
+size_t rcgan_softmax_xent_workspace_bytes(int rows);
+int rcgan_softmax_xent_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* logits, const int32_t* labels, float weight,
+                               float* loss_acc, float* n_correct_acc, float* dlogits, void* ws, size_t ws_bytes);
+/* The option-A shortcut of the classifier's down-sampling blocks as one launch each way: y[n, h/2, w/2, 2c] = the 2x2 mean of
+ * x[n, h, w, c] in channels [c/2, c/2 + c), zeros elsewhere -- the bits of rcgan_meanpool2_fwd followed by rcgan_pad_channels
+ * without the intermediate tensor.  Backward: dx (=|+=) the middle channels of dy, a quarter to each of the four pixels.
+ * h, w, c even. */
+int rcgan_shortcut_a_fwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* x, void* y);
+int rcgan_shortcut_a_bwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* dy, void* dx, int accumulate);
+/* tf.train.MomentumOptimizer on a flat fp32 range with L2 weight decay on its first decay_count elements:
+ *   g' = grad_scale * g + weight_decay * w   (i < decay_count;  grad_scale * g for the rest)
+ *   accum = momentum * accum + g';   w -= lr * accum,   or with nesterov   w -= lr * (g' + momentum * accum)
+ * hyper: DEVICE float[1] = {lr}, read at execution time (a captured step follows the schedule, as with rcgan_adam_tf). */
+int rcgan_sgd_momentum(rcgan_ctx* ctx, size_t count, size_t decay_count, float* w, const float* g, float* accum, const float* hyper,
+                       float momentum, float weight_decay, int nesterov, float grad_scale);
+/* The classifier's input pipeline over a data set resident on the device: images_chw_u8 [n_images][3][32][32] bytes, labels_all
+ * [n_images].  Sample i = image index[i] translated by (shift_flip[i][0], shift_flip[i][1]) pixels down / right (each clamped to
+ * [-pad, pad], zeros shifted in), then mirrored left-right when shift_flip[i][2] != 0, written as raw pixel values 0..255 in NHWC in
+ * `dtype`; labels_out[i] = labels_all[index[i]] (either may be NULL).  An index outside [0, n_images) gives a zero image, label -1. */
+int rcgan_augment_cifar(rcgan_ctx* ctx, int n, int n_images, const uint8_t* images_chw_u8, const int32_t* labels_all,
+                        const int32_t* index, const int32_t* shift_flip, int pad, int dtype, void* y_nhwc, int32_t* labels_out);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

@@ -217,6 +217,12 @@ SIGNATURES = {
     "rcgan_recover_mse_fwd_bwd": (I, [P, I, I, I, I, P, P, P, P, P, P, P, SZ]),
     "rcgan_softmax_rows_fwd": (I, [P, I, I, P, P]),
     "rcgan_softmax_rows_bwd": (I, [P, I, I, P, P, P, I]),
+    "rcgan_softmax_xent_workspace_bytes": (SZ, [I]),
+    "rcgan_softmax_xent_fwd_bwd": (I, [P, I, I, P, P, F, P, P, P, P, SZ]),
+    "rcgan_shortcut_a_fwd": (I, [P, I, I, I, I, I, P, P]),
+    "rcgan_shortcut_a_bwd": (I, [P, I, I, I, I, I, P, P, I]),
+    "rcgan_sgd_momentum": (I, [P, SZ, SZ, P, P, P, P, F, F, I, F]),
+    "rcgan_augment_cifar": (I, [P, I, I, P, P, P, P, I, I, P, P]),
     "rcgan_adam_tf": (I, [P, SZ, P, P, P, P, P, F, F, F, F, F]),
     "rcgan_adam_tf_host": (I, [P, SZ, P, P, P, P, F, F, F, F, F, F, F]),
     "rcgan_fill_f32": (I, [P, SZ, P, F]),

@@ -1,0 +1,305 @@
+// Training the generated-label-accuracy classifier on the engine (classifier.py): the pieces of its step that the GAN steps never
+// needed -- sparse softmax cross-entropy, the option-A shortcut and its adjoint as one launch each, tf.train.MomentumOptimizer, and the
+// input pipeline (random translation + mirror) over a data set that lives on the device.  All plain vector loads and stores.
+#include "common.h"
+
+// ---------------------------------------------------------------------------------------------------------
+// sparse softmax cross-entropy: a wavefront per row, lanes over the columns (<= 1024 = 16 per lane, held in registers)
+// ---------------------------------------------------------------------------------------------------------
+#define XENT_MAX_COLS 1024
+#define XENT_PER_LANE (XENT_MAX_COLS / 64)
+#define XENT_MAX_WG 1024
+
+__device__ __forceinline__ float xent_grad_scale(float gs_host, const float* gs_dev) { return gs_dev ? gs_host * gs_dev[0] : gs_host; }
+
+// partials: [gridDim.x] loss sums, then [gridDim.x] correct counts.  Rows are dealt to the wavefronts round-robin, so every partial and
+// the final sums are formed in an order that depends on the shape alone: the same bits run to run.
+__global__ __launch_bounds__(256) void softmax_xent_kernel(int rows, int cols, const float* __restrict__ logits, const int32_t* __restrict__ labels,
+                                                            float weight, float* loss_acc, float* n_correct_acc, float* __restrict__ dlogits,
+                                                            float gs_host, const float* gs_dev, float* partials, unsigned* counter) {
+  __shared__ float red_l[4], red_c[4], red[4];
+  __shared__ int is_last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float inv_rows = 1.f / (float)rows;
+  const float gw = dlogits ? weight * xent_grad_scale(gs_host, gs_dev) * inv_rows : 0.f;
+  float lsum = 0.f, csum = 0.f;
+  for (long r = (long)blockIdx.x * 4 + wave; r < rows; r += (long)gridDim.x * 4) {
+    const float* x = logits + r * cols;
+    float v[XENT_PER_LANE];
+    float m = -INFINITY;
+    int mi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < XENT_PER_LANE; ++q) {
+      const int j = q * 64 + lane;
+      v[q] = j < cols ? x[j] : -INFINITY;
+      if (v[q] > m) { m = v[q]; mi = j; }           // strictly greater: the lowest index of this lane's maxima
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float om = __shfl_xor(m, o, 64);
+      const int oi = __shfl_xor(mi, o, 64);
+      if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+    }
+    float s = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_PER_LANE; ++q) {
+      v[q] = expf(v[q] - m);                       // (-inf - m -> 0 in the columns past the end)
+      s += v[q];
+    }
+    s = wave_sum(s);
+    const int lab = labels[r];
+    const bool lab_ok = (unsigned)lab < (unsigned)cols;
+    const float xl = lab_ok ? x[lab] : 0.f;
+    if (lab_ok) lsum += (m + logf(s)) - xl;
+    csum += (lab_ok && mi == lab) ? 1.f : 0.f;
+    if (dlogits) {
+      const float inv_s = 1.f / s;
+      float* d = dlogits + r * cols;
+#pragma unroll
+      for (int q = 0; q < XENT_PER_LANE; ++q) {
+        const int j = q * 64 + lane;
+        if (j < cols) d[j] = gw * (v[q] * inv_s - (j == lab ? 1.f : 0.f));
+      }
+    }
+  }
+  // ---- the sums over rows: per-workgroup partials, finished in workgroup order by the last workgroup to arrive ----
+  if (lane == 0) { red_l[wave] = lsum; red_c[wave] = csum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = (red_l[0] + red_l[1]) + (red_l[2] + red_l[3]);
+    partials[gridDim.x + blockIdx.x] = (red_c[0] + red_c[1]) + (red_c[2] + red_c[3]);
+    // release: the two stores above are visible to whoever reads the counter after this increment
+    const unsigned prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = prev == gridDim.x - 1u ? 1 : 0;
+    if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
+  }
+  __syncthreads();
+  if (!is_last) return;
+  float tl = 0.f, tc = 0.f;
+  for (unsigned w = threadIdx.x; w < gridDim.x; w += 256) {
+    tl += __hip_atomic_load(partials + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tc += __hip_atomic_load(partials + gridDim.x + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  tl = block_sum256(tl, red);
+  tc = block_sum256(tc, red);
+  if (threadIdx.x == 0) {
+    if (loss_acc) *loss_acc += weight * (tl * inv_rows);
+    if (n_correct_acc) *n_correct_acc += tc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// option-A shortcut: y[n][h/2][w/2][2c] = 2x2 mean of x[n][h][w][c] in channels [c/2, c/2 + c), zeros elsewhere.
+// The mean is formed exactly as meanpool2_fwd_kernel / resample2_vec_kernel form it: (((x00 + x10) + x01) + x11) * 0.25.
+// ---------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void shortcut_a_fwd_kernel(int n, int h, int w, int c, const T* __restrict__ x, T* __restrict__ y) {
+  const int oh = h >> 1, ow = w >> 1, co = 2 * c, before = c >> 1;
+  const size_t total = (size_t)n * oh * ow * co;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % co) - before;
+    float v = 0.f;
+    if (ch >= 0 && ch < c) {
+      size_t p = i / co;
+      const int x2 = (int)(p % ow);
+      p /= ow;
+      const int y2 = (int)(p % oh), b = (int)(p / oh);
+      const T* s = x + (((size_t)b * h + 2 * y2) * w + 2 * x2) * c + ch;
+      v = (((Elem<T>::ld(s) + Elem<T>::ld(s + (size_t)w * c)) + Elem<T>::ld(s + c)) + Elem<T>::ld(s + (size_t)w * c + c)) * 0.25f;
+    }
+    Elem<T>::st(y + i, v);
+  }
+}
+
+// fp32, c % 8 == 0: four channels per thread (the padding boundaries c/2 and c/2 + c then fall between the groups)
+__global__ void shortcut_a_fwd_vec_kernel(int n, int h, int w, int c, const float* __restrict__ x, float* __restrict__ y) {
+  const int oh = h >> 1, ow = w >> 1, cq = (2 * c) >> 2, before = c >> 1;
+  const size_t total = (size_t)n * oh * ow * cq;
+  const size_t rowpitch = (size_t)w * c;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % cq) * 4 - before;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (ch >= 0 && ch < c) {
+      size_t p = i / cq;
+      const int x2 = (int)(p % ow);
+      p /= ow;
+      const int y2 = (int)(p % oh), b = (int)(p / oh);
+      const float* s = x + (((size_t)b * h + 2 * y2) * w + 2 * x2) * c + ch;
+      const float4 a0 = *(const float4*)s, a1 = *(const float4*)(s + rowpitch), a2 = *(const float4*)(s + c), a3 = *(const float4*)(s + rowpitch + c);
+      o.x = (((a0.x + a1.x) + a2.x) + a3.x) * 0.25f;
+      o.y = (((a0.y + a1.y) + a2.y) + a3.y) * 0.25f;
+      o.z = (((a0.z + a1.z) + a2.z) + a3.z) * 0.25f;
+      o.w = (((a0.w + a1.w) + a2.w) + a3.w) * 0.25f;
+    }
+    *(float4*)(y + i * 4) = o;
+  }
+}
+
+// adjoint: dx[n][h][w][c] (=|+=) 0.25 * dy[n][h/2][w/2][c/2 + ch]
+template <typename T>
+__global__ void shortcut_a_bwd_kernel(int n, int h, int w, int c, const T* __restrict__ dy, T* __restrict__ dx, int accumulate) {
+  const int oh = h >> 1, ow = w >> 1, co = 2 * c, before = c >> 1;
+  const size_t total = (size_t)n * h * w * c;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % c);
+    size_t p = i / c;
+    const int xx = (int)(p % w);
+    p /= w;
+    const int yy = (int)(p % h), b = (int)(p / h);
+    float v = 0.25f * Elem<T>::ld(dy + (((size_t)b * oh + (yy >> 1)) * ow + (xx >> 1)) * co + before + ch);
+    if (accumulate) v += Elem<T>::ld(dx + i);
+    Elem<T>::st(dx + i, v);
+  }
+}
+
+__global__ void shortcut_a_bwd_vec_kernel(int n, int h, int w, int c, const float* __restrict__ dy, float* __restrict__ dx, int accumulate) {
+  const int oh = h >> 1, ow = w >> 1, co = 2 * c, before = c >> 1, cq = c >> 2;
+  const size_t total = (size_t)n * h * w * cq;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % cq) * 4;
+    size_t p = i / cq;
+    const int xx = (int)(p % w);
+    p /= w;
+    const int yy = (int)(p % h), b = (int)(p / h);
+    const float4 g = *(const float4*)(dy + (((size_t)b * oh + (yy >> 1)) * ow + (xx >> 1)) * co + before + ch);
+    float4 o = make_float4(0.25f * g.x, 0.25f * g.y, 0.25f * g.z, 0.25f * g.w);
+    if (accumulate) {
+      const float4 d = *(const float4*)(dx + i * 4);
+      o.x += d.x; o.y += d.y; o.z += d.z; o.w += d.w;
+    }
+    *(float4*)(dx + i * 4) = o;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// tf.train.MomentumOptimizer on a flat fp32 range; the first decay_count elements carry L2 weight decay
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void sgd_elem(float& w, float g, float& a, float lr, float momentum, float wd, int nesterov, float gs) {
+  const float gp = gs * g + wd * w;
+  a = momentum * a + gp;
+  w -= nesterov ? lr * (gp + momentum * a) : lr * a;
+}
+
+__global__ void sgd_momentum_kernel(size_t count, size_t decay_count, float* __restrict__ w, const float* __restrict__ g, float* __restrict__ accum,
+                                    const float* __restrict__ hyper, float momentum, float weight_decay, int nesterov, float grad_scale) {
+  const float lr = hyper[0];
+  const size_t n4 = ((((size_t)w | (size_t)g | (size_t)accum) & 15) == 0) ? count / 4 : 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
+    float4 wv = ((float4*)w)[i], av = ((float4*)accum)[i];
+    const float4 gv = ((const float4*)g)[i];
+    const size_t e = i * 4;
+    sgd_elem(wv.x, gv.x, av.x, lr, momentum, e + 0 < decay_count ? weight_decay : 0.f, nesterov, grad_scale);
+    sgd_elem(wv.y, gv.y, av.y, lr, momentum, e + 1 < decay_count ? weight_decay : 0.f, nesterov, grad_scale);
+    sgd_elem(wv.z, gv.z, av.z, lr, momentum, e + 2 < decay_count ? weight_decay : 0.f, nesterov, grad_scale);
+    sgd_elem(wv.w, gv.w, av.w, lr, momentum, e + 3 < decay_count ? weight_decay : 0.f, nesterov, grad_scale);
+    ((float4*)w)[i] = wv;
+    ((float4*)accum)[i] = av;
+  }
+  for (size_t i = n4 * 4 + (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+    float wv = w[i], av = accum[i];
+    sgd_elem(wv, g[i], av, lr, momentum, i < decay_count ? weight_decay : 0.f, nesterov, grad_scale);
+    w[i] = wv;
+    accum[i] = av;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// input pipeline: sample i = image index[i], translated by (dy, dx) with zeros shifted in, then mirrored left-right
+// ---------------------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void augment_cifar_kernel(int n, int n_images, const uint8_t* __restrict__ images, const int32_t* __restrict__ labels_all,
+                                     const int32_t* __restrict__ index, const int32_t* __restrict__ shift_flip, int pad, T* __restrict__ y,
+                                     int32_t* __restrict__ labels_out) {
+  const size_t total = (size_t)n * 3072;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % 3);
+    const int px = (int)((i / 3) % 1024);
+    const int b = (int)(i / 3072);
+    const int src = index[b];
+    const bool src_ok = (unsigned)src < (unsigned)n_images;
+    const int dy = min(max(shift_flip[b * 3 + 0], -pad), pad), dx = min(max(shift_flip[b * 3 + 1], -pad), pad);
+    const int yy = px >> 5, xx = px & 31;
+    const int sy = yy - dy, sx = (shift_flip[b * 3 + 2] ? 31 - xx : xx) - dx;
+    float v = 0.f;
+    if (src_ok && (unsigned)sy < 32u && (unsigned)sx < 32u) v = (float)images[(size_t)src * 3072 + ch * 1024 + sy * 32 + sx];
+    Elem<T>::st(y + i, v);
+    if (ch == 0 && px == 0 && labels_out) labels_out[b] = (src_ok && labels_all) ? labels_all[src] : -1;
+  }
+}
+
+static inline bool cls_aligned16(const void* a, const void* b) { return ((((size_t)a) | ((size_t)b)) & 15) == 0; }
+
+static inline int cls_grid(size_t count) {
+  size_t b = (count + 255) / 256;
+  if (b > 8192) b = 8192;
+  return b < 1 ? 1 : (int)b;
+}
+
+extern "C" {
+
+size_t rcgan_softmax_xent_workspace_bytes(int rows) {
+  const int nwg = rows < 4 * XENT_MAX_WG ? cdiv(rows > 0 ? rows : 1, 4) : XENT_MAX_WG;
+  return (size_t)nwg * 2 * sizeof(float);
+}
+
+int rcgan_softmax_xent_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* logits, const int32_t* labels, float weight, float* loss_acc,
+                               float* n_correct_acc, float* dlogits, void* ws, size_t ws_bytes) {
+  RC_REQUIRE(ctx, rows >= 1 && logits && labels, "bad arguments (rows %d)", rows);
+  if (cols < 2 || cols > XENT_MAX_COLS) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "%d classes (2..%d)", cols, XENT_MAX_COLS);
+  const size_t need = rcgan_softmax_xent_workspace_bytes(rows);
+  if (!ws || ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
+  const int nwg = (int)(need / (2 * sizeof(float)));
+  hipLaunchKernelGGL(softmax_xent_kernel, dim3(nwg), dim3(256), 0, ctx->stream, rows, cols, logits, labels, weight, loss_acc, n_correct_acc, dlogits,
+                     ctx->gscale_host, ctx->gscale_dev, (float*)ws, ctx->counters() + RC_COUNTER_XENT);
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_shortcut_a_fwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* x, void* y) {
+  RC_REQUIRE(ctx, n >= 1 && c >= 2 && h >= 2 && w >= 2 && x && y, "bad arguments");
+  RC_REQUIRE(ctx, h % 2 == 0 && w % 2 == 0 && c % 2 == 0, "odd shape %dx%dx%d", h, w, c);
+  const size_t cnt = (size_t)n * (h / 2) * (w / 2) * 2 * c;
+  if (dtype == RCGAN_F32 && c % 8 == 0 && cls_aligned16(x, y)) {
+    hipLaunchKernelGGL(shortcut_a_fwd_vec_kernel, dim3(cls_grid(cnt / 4)), dim3(256), 0, ctx->stream, n, h, w, c, (const float*)x, (float*)y);
+  } else {
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(shortcut_a_fwd_kernel<T>, dim3(cls_grid(cnt)), dim3(256), 0, ctx->stream, n, h, w, c, (const T*)x, (T*)y));
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_shortcut_a_bwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* dy, void* dx, int accumulate) {
+  RC_REQUIRE(ctx, n >= 1 && c >= 2 && h >= 2 && w >= 2 && dy && dx, "bad arguments");
+  RC_REQUIRE(ctx, h % 2 == 0 && w % 2 == 0 && c % 2 == 0, "odd shape %dx%dx%d", h, w, c);
+  const size_t cnt = (size_t)n * h * w * c;
+  if (dtype == RCGAN_F32 && c % 8 == 0 && cls_aligned16(dy, dx)) {
+    hipLaunchKernelGGL(shortcut_a_bwd_vec_kernel, dim3(cls_grid(cnt / 4)), dim3(256), 0, ctx->stream, n, h, w, c, (const float*)dy, (float*)dx, accumulate);
+  } else {
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(shortcut_a_bwd_kernel<T>, dim3(cls_grid(cnt)), dim3(256), 0, ctx->stream, n, h, w, c, (const T*)dy, (T*)dx, accumulate));
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_sgd_momentum(rcgan_ctx* ctx, size_t count, size_t decay_count, float* w, const float* g, float* accum, const float* hyper, float momentum,
+                       float weight_decay, int nesterov, float grad_scale) {
+  RC_REQUIRE(ctx, w && g && accum && hyper, "null pointer");
+  RC_REQUIRE(ctx, decay_count <= count, "decay_count %zu > count %zu", decay_count, count);
+  if (count == 0) return RCGAN_OK;
+  hipLaunchKernelGGL(sgd_momentum_kernel, dim3(cls_grid((count + 3) / 4)), dim3(256), 0, ctx->stream, count, decay_count, w, g, accum, hyper, momentum,
+                     weight_decay, nesterov ? 1 : 0, grad_scale);
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_augment_cifar(rcgan_ctx* ctx, int n, int n_images, const uint8_t* images_chw_u8, const int32_t* labels_all, const int32_t* index,
+                        const int32_t* shift_flip, int pad, int dtype, void* y_nhwc, int32_t* labels_out) {
+  RC_REQUIRE(ctx, n >= 1 && n_images >= 1 && images_chw_u8 && index && shift_flip && y_nhwc, "bad arguments");
+  RC_REQUIRE(ctx, pad >= 0 && pad < 32, "pad %d", pad);
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(augment_cifar_kernel<T>, dim3(cls_grid((size_t)n * 3072)), dim3(256), 0, ctx->stream, n, n_images,
+                                                   images_chw_u8, labels_all, index, shift_flip, pad, (T*)y_nhwc, labels_out));
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+}  // extern "C"

@@ -6,7 +6,7 @@ that file without TensorFlow by scripts/extract_label_classifier.py into assets/
 engine's own kernels in fp32: a pre-activation ResNet-32 (conv0 3->16, three stages of five basic blocks at 16/32/64
 channels, stride-2 first conv in stages 2 and 3 with the option-A shortcut = 2x2 average pool + zero channel padding),
 every batch norm on the moments of the evaluated batch itself (eps 1e-3, no moving statistics), ReLU, global average
-pool, 64->10 dense layer, softmax.  Inputs are the raw integer pixels 0..255 in NHWC, all 1000 samples in ONE batch
+pool, 64->K dense layer, softmax (K = 10 for the committed asset; classifier.py trains the same network for any K).  Inputs are the raw integer pixels 0..255 in NHWC, all 1000 samples in ONE batch
 (the batch statistics depend on it), exactly as ``generated_label_accuracy`` feeds them.
 """
 import os
@@ -20,6 +20,41 @@ from .runtime import Context
 ASSET = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets", "cifar_label_classifier.npz")
 BN_EPS = 1e-3
 STAGES, BLOCKS = 3, 5
+
+
+def classifier_logits(ctx, w, x):
+    """The forward pass of the label classifier, written once: x [n,32,32,3] fp32 device tensor of raw pixel values, w = {name: device
+    tensor} under the asset's names ('/'-separated) -> logits [n,K].  Every batch norm uses the moments of this batch.  Recorded on the
+    tape when ctx.recording is on and the weights require gradients (classifier.LabelClassifierTrainer), forward only otherwise."""
+    conv = lambda t, name, stride=1: O.conv2d(ctx, t, O.Weight(ctx, w[name + "/conv"]), None, 3, stride=stride)
+    bn_relu = lambda t, name: O.batch_norm_act(ctx, t, w[name + "/gamma"], w[name + "/beta"], act=L.ACT_RELU, eps=BN_EPS)
+    h = bn_relu(conv(x, "conv0"), "conv0")
+    for s in range(1, STAGES + 1):
+        for b in range(BLOCKS):
+            p = "conv%d_%d" % (s, b)
+            down = b == 0 and s > 1
+            t = h if (s == 1 and b == 0) else bn_relu(h, p + "/conv1_in_block")
+            c1 = conv(t, p + "/conv1_in_block", stride=2 if down else 1)
+            c2 = conv(bn_relu(c1, p + "/conv2_in_block"), p + "/conv2_in_block")
+            # option-A shortcut of the down-sampling blocks: AvgPool 2x2 + Pad channels (C/2 each side), one launch
+            h = O.add(ctx, c2, O.shortcut_a(ctx, h) if down else h)
+    feat = O.act_meanhw(ctx, bn_relu(h, "fc"), L.ACT_NONE)
+    return O.linear(ctx, feat, O.Weight(ctx, w["fc/fc_weights"]), w["fc/fc_bias"])
+
+
+def check_images(images):
+    x = np.ascontiguousarray(np.asarray(images, np.float32))
+    if x.ndim != 4 or x.shape[1:] != (32, 32, 3):
+        raise ValueError("expected [n,32,32,3] images, got %s" % (x.shape,))
+    return x
+
+
+def asset_n_classes(asset):
+    """Class count of a weight asset (the width of its dense layer); reads the file only, needs no GPU."""
+    if not os.path.exists(asset):
+        raise RuntimeError("label-classifier weights missing: %s" % asset)
+    with np.load(asset) as z:
+        return int(z["fc|fc_weights"].shape[1])
 
 
 class LabelClassifier:
@@ -39,38 +74,18 @@ class LabelClassifier:
             self.w[t.name] = t
         ctx.sync()
 
-    def _conv(self, x, name, stride=1):
-        return O.conv2d(self.ctx, x, O.Weight(self.ctx, self.w[name + "/conv"]), None, 3, stride=stride)
-
-    def _bn_relu(self, x, name):
-        return O.batch_norm_act(self.ctx, x, self.w[name + "/gamma"], self.w[name + "/beta"], act=L.ACT_RELU, eps=BN_EPS)
+    @property
+    def n_classes(self):
+        return self.w["fc/fc_weights"].shape[1]
 
     def softmax(self, images):
-        """images: [n,32,32,3] raw pixel values 0..255 (any numeric dtype).  -> softmax [n,10] float32."""
+        """images: [n,32,32,3] raw pixel values 0..255 (any numeric dtype).  -> softmax [n,K] float32."""
         ctx = self.ctx
-        x = np.ascontiguousarray(np.asarray(images, np.float32))
-        if x.ndim != 4 or x.shape[1:] != (32, 32, 3):
-            raise ValueError("expected [n,32,32,3] images, got %s" % (x.shape,))
+        x = check_images(images)
         ctx.new_step()
         rec, ctx.recording = ctx.recording, False
         try:
-            h = self._bn_relu(self._conv(ctx.upload(x, L.F32), "conv0"), "conv0")
-            for s in range(1, STAGES + 1):
-                for b in range(BLOCKS):
-                    p = "conv%d_%d" % (s, b)
-                    down = b == 0 and s > 1
-                    t = h if (s == 1 and b == 0) else self._bn_relu(h, p + "/conv1_in_block")
-                    c1 = self._conv(t, p + "/conv1_in_block", stride=2 if down else 1)
-                    c2 = self._conv(self._bn_relu(c1, p + "/conv2_in_block"), p + "/conv2_in_block")
-                    sc = h
-                    if down:                               # option-A shortcut: AvgPool 2x2 + Pad channels (C/2 each side)
-                        pooled = O.meanpool2(ctx, h)
-                        n, hh, ww, c = pooled.shape
-                        sc = ctx.empty((n, hh, ww, 2 * c), L.F32)
-                        ctx.check(ctx.lib.rcgan_pad_channels(ctx.h, n * hh * ww, c, c // 2, c // 2, L.F32, pooled.ptr, sc.ptr))
-                    h = O.add(ctx, c2, sc)
-            feat = O.act_meanhw(ctx, self._bn_relu(h, "fc"), L.ACT_NONE)
-            logits = O.linear(ctx, feat, O.Weight(ctx, self.w["fc/fc_weights"]), self.w["fc/fc_bias"])
+            logits = classifier_logits(ctx, self.w, ctx.upload(x, L.F32))
             return ctx.download(O.softmax_rows(ctx, logits))
         finally:
             ctx.recording = rec

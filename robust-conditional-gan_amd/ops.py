@@ -909,6 +909,22 @@ def meanpool2(ctx, x):
     return y
 
 
+def shortcut_a(ctx, x):
+    """Option-A shortcut of the label classifier's down-sampling blocks: [n,h,w,c] -> [n,h/2,w/2,2c], the 2x2 mean in the middle c
+    channels and zeros around them -- meanpool2 + rcgan_pad_channels as one launch (the same bits), with its adjoint."""
+    n, h, w, c = x.shape
+    y = ctx.empty((n, h // 2, w // 2, 2 * c), x.dtype)
+    ctx.check(ctx.lib.rcgan_shortcut_a_fwd(ctx.h, n, h, w, c, x.dtype, _p(x), _p(y)))
+    if _track(ctx, y, x):
+        def bw():
+            if y.grad is None:
+                return
+            dx, acc = grad_of(ctx, x)
+            ctx.check(ctx.lib.rcgan_shortcut_a_bwd(ctx.h, n, h, w, c, x.dtype, _p(y.grad), _p(dx), acc))
+        ctx.record(bw)
+    return y
+
+
 def upsample2(ctx, x):
     n, h, w, c = x.shape
     y = ctx.empty((n, h * 2, w * 2, c), x.dtype)
@@ -1244,6 +1260,18 @@ def bce_onehot_term(ctx, x, labels, weight, loss_acc):
     if x.req and ctx.recording:
         dx, _ = grad_of(ctx, x)
     ctx.check(ctx.lib.rcgan_bce_onehot_fwd_bwd(ctx.h, r, c, _p(x), _p(labels), float(weight), _p(loss_acc), _p(dx)))
+
+
+def softmax_xent(ctx, logits, labels, weight, loss_acc, n_correct=None):
+    """weight * reduce_mean(sparse_softmax_cross_entropy_with_logits(logits, labels)) added to the device scalar loss_acc, the number
+    of rows classified correctly added to n_correct (fp32 device scalar, optional).  Like loss_term the gradient is written in the
+    same launch: logits must have this term as their only consumer."""
+    r, c = logits.shape
+    dl = None
+    if logits.req and ctx.recording:
+        dl, _ = grad_of(ctx, logits)
+    ctx.check(ctx.lib.rcgan_softmax_xent_fwd_bwd(ctx.h, r, c, _p(logits), _p(labels), float(weight), _p(loss_acc), _p(n_correct), _p(dl),
+                                                 C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
 
 
 def softmax_rows(ctx, logits):

@@ -63,6 +63,8 @@ def define_flags():
     f.DEFINE_string("data_dir", DATA_DIR, "CIFAR-10 python batches (--dataset cifar100: the cifar-100-python directory, default %s)"
                     % DATA_DIR_100)
     f.DEFINE_boolean("coarse_labels", False, "--dataset cifar100: train on the 20 coarse labels instead of the 100 fine ones")
+    f.DEFINE_string("label_classifier", None, "weight asset of the generated-label-accuracy classifier (python -m "
+                    "rcgan_amd.train_classifier writes one for any class count); default: the built-in CIFAR-10 network")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -84,12 +86,28 @@ def grid_labels(n_classes):
     return np.sort(np.arange(100) % n_classes).astype('int32')
 
 
+def gen_acc_label_lists(n_classes, balanced=False):
+    """The conditioning labels of the ten 100-sample Generator calls behind one generated-label accuracy.  Default: the reference's
+    list every time (ten per class of CIFAR-10, gan_resnet.py:847-861).  balanced (--label_classifier): sample i of the 1000 gets
+    label i % K, each call's hundred sorted -- balanced over the K classes to within one sample per class."""
+    if not balanced:
+        return [[label for label in range(10) for _ in range(10)]] * 10
+    return [np.sort((100 * j + np.arange(100)) % n_classes).tolist() for j in range(10)]
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     FLAGS = define_flags().parse(argv)
     if FLAGS.log_file is None:
         raise ValueError('flag log_file is required')                         # gan_resnet.py:81-82
     N_CLASSES, DATA = dataset_setup(FLAGS)
+    if FLAGS.label_classifier is not None:
+        # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
+        from .eval_cifar import asset_n_classes
+        asset_classes = asset_n_classes(FLAGS.label_classifier)
+        if asset_classes != N_CLASSES:
+            raise ValueError("--label_classifier %s classifies %d classes, this run has %d"
+                             % (FLAGS.label_classifier, asset_classes, N_CLASSES))
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
@@ -176,9 +194,9 @@ def main(argv=None):
                     inv_weights=sh(inv), labels_all=np.concatenate([sh(labels), sh(second)]))
 
     # generated-label accuracy (gan_resnet.py:424-455, 847-861): 1000 samples, 100 per class, ONE classifier batch
-    label_100_list = [label for label in range(10) for _ in range(10)]
+    label_lists = gen_acc_label_lists(N_CLASSES, balanced=FLAGS.label_classifier is not None)
     GEN_ACC_FREQ = FLAGS.generated_label_accuracy_freq
-    if N_CLASSES != 10 and GEN_ACC_FREQ > 0:
+    if N_CLASSES != 10 and FLAGS.label_classifier is None and GEN_ACC_FREQ > 0:
         # the label classifier (and the templates' reader) know the ten CIFAR-10 classes only
         logging.info('generated label accuracy: skipped, its classifier is CIFAR-10-only ({} classes here)'.format(N_CLASSES))
         GEN_ACC_FREQ = 0
@@ -187,15 +205,19 @@ def main(argv=None):
     def save_samples(n):
         # the reference draws these latents with TensorFlow's generator (Generator(noise=None), gan_resnet.py:847-861): a private
         # stream, so that evaluating does not shift the numpy stream the data and label noise come from
-        all_samples = [m.sample(label_100_list, is_rs.normal(size=(100, Z_DIM)).astype('float32')) for _ in range(int(n / 100))]
+        calls = [label_lists[j % len(label_lists)] for j in range(int(n / 100))]
+        all_samples = [m.sample(labels, is_rs.normal(size=(100, Z_DIM)).astype('float32')) for labels in calls]
         all_samples = ((np.concatenate(all_samples, axis=0) + 1.) * (255.99 / 2)).astype('int32')     # gan_resnet.py:858
-        return all_samples.reshape((-1, 32, 32, 3)), np.concatenate([label_100_list] * int(n / 100), axis=0)
+        return all_samples.reshape((-1, 32, 32, 3)), np.concatenate(calls, axis=0)
 
     def label_accuracy(confusion_matrix=None):
         from .eval_cifar import LabelClassifier, TemplateClassifier, generated_label_accuracy
         if acc_state["clf"] is None:
             templates = FLAGS.synthetic and FLAGS.synthetic_kind == 'templates'
-            acc_state["clf"] = TemplateClassifier() if templates else LabelClassifier(local)
+            if FLAGS.label_classifier is not None:
+                acc_state["clf"] = LabelClassifier(local, asset=FLAGS.label_classifier)
+            else:
+                acc_state["clf"] = TemplateClassifier() if templates else LabelClassifier(local)
         samples, labels = save_samples(1000)
         acc = generated_label_accuracy(samples, labels, confusion_matrix=confusion_matrix, classifier=acc_state["clf"])
         logging.info('generated label accuracy: {}'.format(acc))
