@@ -571,6 +571,39 @@ int rcgan_sgd_momentum(rcgan_ctx* ctx, size_t count, size_t decay_count, float* 
 int rcgan_augment_cifar(rcgan_ctx* ctx, int n, int n_images, const uint8_t* images_chw_u8, const int32_t* labels_all,
                         const int32_t* index, const int32_t* shift_flip, int pad, int dtype, void* y_nhwc, int32_t* labels_out);
 
+/* ---- differentiable augmentation of the critic's input (csrc/augment.hip; Zhao et al., "Differentiable Augmentation for
+ * Data-Efficient GAN Training", NeurIPS 2020) --------------------------------------------------------------------------------
+ * y = A_u(x) over NHWC images x[n, h, w, 3] (fp32 or the library's 16-bit dtype), and the adjoint of that map.  Nothing random
+ * happens inside: u[n][8] holds eight fp32 uniforms in [0, 1) per sample, drawn by the caller (rcgan_rng_fill, kind 0), and both
+ * entry points are pure functions of (images, u, policy).  policy is a mask of the RCGAN_AUG_* bits; a step whose bit is clear is
+ * skipped (policy 0: a copy).  Per sample, in this order, all arithmetic in fp32, the output rounded once to `dtype`:
+ *   COLOR        b = u0 - 0.5, s = 2 u1, k = u2 + 0.5
+ *                brightness  x1 = x + b
+ *                saturation  x2 = (x1 - m) s + m,   m[p][q] = mean of x1[p][q][:] over the 3 channels
+ *                contrast    x3 = (x2 - M) k + M,   M = mean of x2 over all h w 3 values of the sample
+ *   TRANSLATION  S_h = (h + 4) / 8, S_w = (w + 4) / 8 (integer division: 4 pixels of 32);
+ *                ty = min(floor(u3 (2 S_h + 1)), 2 S_h) - S_h, tx likewise from u4 and S_w (the product in fp32)
+ *                x4[p][q] = x3[p + ty][q + tx] where that pixel exists, 0 elsewhere
+ *   CUTOUT       oy = min(floor(u5 (h + 1)), h), ox likewise from u6 and w
+ *                rows max(oy - h/4, 0) .. min(oy + h/4 - 1, h - 1) x columns max(ox - w/4, 0) .. min(ox + w/4 - 1, w - 1) are set to 0
+ *                (a window of h/2 x w/2 pixels, clipped at the border)
+ *   u7 is reserved and ignored.
+ * y_pool (may be NULL): [n, h/2, w/2, 3], the 2x2 mean of the STORED y -- the bits rcgan_meanpool2_fwd gives on y -- out of the
+ * same launch (D.Block.1's shortcut reads the pooled critic input, gan_resnet.py:346).
+ * Backward: dx (=|+=) A_u^T dy.  The map is affine in x, so the adjoint needs u only: dy is masked by the cutout window, shifted by
+ * (-ty, -tx) with zero fill (g3), then g2 = k g3 + (1 - k) mean_all(g3) and dx = s g2 + (1 - s) mean_c(g2); the brightness offset has
+ * no term.  Without COLOR the pixels that are cut out or shifted out of the frame get exactly 0.
+ * One workgroup per sample, the sample in LDS; the means are summed in a fixed order (no floating-point atomics): the same bits on
+ * every run, eager or replayed.  h and w multiples of 4, 2 h w 3 floats (the sample and its transform) within the 160 KiB of LDS of a compute unit (up to 80 x 80), n >= 1, image pointers
+ * aligned to four elements; anything else is RCGAN_EINVALID_ARG. */
+#define RCGAN_AUG_COLOR 1
+#define RCGAN_AUG_TRANSLATION 2
+#define RCGAN_AUG_CUTOUT 4
+int rcgan_diffaugment_fwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* x, const float* u, void* y,
+                          void* y_pool);
+int rcgan_diffaugment_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* dy, const float* u, void* dx,
+                          int accumulate);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

@@ -16,6 +16,9 @@ ACT_NONE, ACT_RELU, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3, 4
 CONV_IN_UPSAMPLE2X, CONV_IN_RELU, CONV_ACCUMULATE, CONV_FORCE_DIRECT, CONV_OUT_MEANPOOL2, CONV_RESID_UPSAMPLE2X = 1, 2, 4, 8, 16, 32
 LOSS_HINGE_REAL, LOSS_HINGE_FAKE, LOSS_NEG_MEAN, LOSS_CE_ONES, LOSS_CE_ZEROS = 0, 1, 2, 3, 4
 QUERY_TR_READ = 0
+# rcgan_diffaugment_*: the policy bits, and the names CifarRCGAN(diffaugment=...) / --diffaugment take for them
+AUG_COLOR, AUG_TRANSLATION, AUG_CUTOUT = 1, 2, 4
+AUG_POLICIES = {"color": AUG_COLOR, "translation": AUG_TRANSLATION, "cutout": AUG_CUTOUT}
 F32_PRECISION_HIGHEST, F32_PRECISION_HIGH = 0, 1     # rcgan_set_f32_matmul_precision
 F32_PRECISIONS = {"highest": F32_PRECISION_HIGHEST, "high": F32_PRECISION_HIGH}
 
@@ -221,6 +224,8 @@ SIGNATURES = {
     "rcgan_softmax_xent_fwd_bwd": (I, [P, I, I, P, P, F, P, P, P, P, SZ]),
     "rcgan_shortcut_a_fwd": (I, [P, I, I, I, I, I, P, P]),
     "rcgan_shortcut_a_bwd": (I, [P, I, I, I, I, I, P, P, I]),
+    "rcgan_diffaugment_fwd": (I, [P, I, I, I, I, I, P, P, P, P]),
+    "rcgan_diffaugment_bwd": (I, [P, I, I, I, I, I, P, P, P, I]),
     "rcgan_sgd_momentum": (I, [P, SZ, SZ, P, P, P, P, F, F, I, F]),
     "rcgan_augment_cifar": (I, [P, I, I, P, P, P, P, I, I, P, P]),
     "rcgan_adam_tf": (I, [P, SZ, P, P, P, P, P, F, F, F, F, F]),

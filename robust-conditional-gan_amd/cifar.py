@@ -146,6 +146,20 @@ def check_n_classes(n_classes):
     return k
 
 
+def parse_diffaugment(policy):
+    """The ``diffaugment`` argument of CifarRCGAN / --diffaugment: a comma-separated subset of color,translation,cutout (empty: off)
+    -> the policy bits of rcgan_diffaugment_fwd (include/rcgan_hip.h).  Raises ValueError; needs no GPU."""
+    bits = 0
+    for name in (policy or "").split(","):
+        name = name.strip()
+        if not name:
+            continue
+        if name not in L.AUG_POLICIES:
+            raise ValueError("Unknown diffaugment policy %r: a comma-separated subset of %s" % (name, ",".join(L.AUG_POLICIES)))
+        bits |= L.AUG_POLICIES[name]
+    return bits
+
+
 def confusion_logits_initial(confuse_init, confuse_init_diag, rs, n_classes=VOCAB_SIZE):
     """gan_resnet.py:499-520 with VOCAB_SIZE = n_classes (the reference's special case of 10 classes kept for K = 10 only)."""
     K = n_classes
@@ -410,9 +424,13 @@ class CifarRCGAN:
                  confuse_init=False, confuse_init_diag=0.2, confuse_multiplier=1.0, confuse_lr_decay=False,
                  device=0, use_graphs=True, device_rng=True, arena_bytes=None, world_size=1, rank=0,
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
-                 grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE):
+                 grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE,
+                 diffaugment=""):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # DiffAugment of every image the critic sees ("Differentiable augmentation"): policy bits, 0 = off.  Checked
+        # before any context exists.
+        self.aug = parse_diffaugment(diffaugment)
         # class count K (2 .. 1024): checked before any context exists; K > 16 takes the kernels' wide routes
         self.K = check_n_classes(n_classes)
         # "high": the fp32 gather GEMMs on split-bf16 matrix cores (rcgan_set_f32_matmul_precision), on every context of the engine
@@ -529,6 +547,12 @@ class CifarRCGAN:
             "g": [("labels_random_G", (2 * B,), i32), ("labels_biased_G", (2 * B,), i32)],
             # generator labels of the N_CRITIC critic steps of one iteration (prepare_critic_fakes)
             "gf": [("labels_random_all", (N_CRITIC * B,), i32)]}
+        # the augmentation's uniforms, one row of eight per image the critic sees: step inputs where the host draws (device_rng=False),
+        # buffers the step's own launch fills otherwise (_draw_aug); absent with the option off
+        aug_shapes = {"aug_u": (2 * B, 8), "aug_u_G": (GEN_BS_MULTIPLE * B, 8)} if self.aug else {}
+        if self.aug and not device_rng:
+            self.feed_layout["d"].append(("aug_u", aug_shapes["aug_u"], f32))
+            self.feed_layout["g"].append(("aug_u_G", aug_shapes["aug_u_G"], f32))
         self.feed, self.inp = {}, {}
         self._feed_ring = {}
         for key, fields in self.feed_layout.items():
@@ -554,6 +578,8 @@ class CifarRCGAN:
         self.inp.update(noise=P((B, OUTPUT_DIM), f32), z=P((B, Z_DIM), act), z_G=P((2 * B, Z_DIM), act),
                         z_all=P((N_CRITIC * B, Z_DIM), act),
                         arange=P((self.K,), i32), C_const=P((self.K, self.K), f32))
+        if self.aug and device_rng:
+            self.inp.update({name: P(shp, f32) for name, shp in aug_shapes.items()})
         ctx.view(self.inp["arange"]).copy_(torch.arange(self.K, dtype=torch.int32))
         ctx.view(self.inp["C_const"]).copy_(torch.from_numpy(C_ALPHA(alpha, self.K).astype(np.float32)))
         # the critic steps' generator forwards evaluated as one batch (prepare_critic_fakes): fakes of all N_CRITIC steps,
@@ -565,6 +591,9 @@ class CifarRCGAN:
         self.loss_d = self.PD.scalar(0)
         self.loss_g = self.PG.scalar(0)
         self.rng_state = torch.zeros(2, dtype=torch.int64, device=ctx.device)
+        # the augmentation draws from a stream of its own: noise and z of a run do not move when the option is turned on.  Like
+        # rng_state it is not part of state_dict.
+        self.aug_rng_state = torch.zeros(2, dtype=torch.int64, device=ctx.device) if self.aug else None
         # (round 6) The critic steps' generator forwards on a SECOND stream.  The generator does not change during the N_CRITIC critic
         # updates of an iteration (gan_resnet.py:928-947), so step k + 1's Generator() call can run while critic step k does: a critic
         # step is a chain of ~26 small-grid launches that leaves half the chip idle most of the time, the generator forward is the
@@ -671,6 +700,15 @@ class CifarRCGAN:
         ctx = self.ctx
         ctx.check(ctx.lib.rcgan_rng_fill(ctx.h, t.size, t.dtype, kind, lo, hi, self.seed * 1000003 + self.rank,
                                          C.c_void_p(self.rng_state.data_ptr()), C.c_void_p(t.ptr)))
+
+    def _draw_aug(self, u):
+        """The uniforms of one augmentation call: drawn here, by a launch of the step, on the device (fresh on every replay of a
+        captured step), or whatever the host has put into the step input."""
+        if self.device_rng:
+            ctx = self.ctx
+            ctx.check(ctx.lib.rcgan_rng_fill(ctx.h, u.size, u.dtype, 0, 0.0, 1.0, self.seed * 1000003 + self.rank + 700001,
+                                             C.c_void_p(self.aug_rng_state.data_ptr()), C.c_void_p(u.ptr)))
+        return u
 
     def _sn_entries(self, conv_update, proj_update):
         ents = []
@@ -805,9 +843,16 @@ class CifarRCGAN:
             fake = self.x_all.rows(B, 2 * B)
         else:
             fake = Generator(B, inp["labels_random"], inp["z"], out=fake_dst)             # :540-546
+        d_in = x_all
+        if self.aug:
+            # the critic sees [real ; fake] augmented, one independent draw per image; the pooled input of D.Block.1's shortcut comes
+            # out of the same launch (the rider's pool is of the un-augmented images: where the rider runs it still fills its own
+            # [2B, 16, 16, 3] buffer, part of its launch and 98 KB of arena at B = 64, which nothing reads).  perm_classifier below
+            # keeps `real`.
+            d_in, g.image_pool = O.diffaugment(ctx, x_all, self._draw_aug(inp["aug_u"]), self.aug, pool=True)
         w = 1.0       # (the gradient scale of 16-bit activations is applied inside the loss kernels: rcgan_set_grad_scale)
         if self.fused_head:
-            feat = Discriminator(x_all, None, update_collection=None, _head=False)        # :584
+            feat = Discriminator(d_in, None, update_collection=None, _head=False)         # :584
             lab_r, lab_f = inp["labels_all"].rows(0, B), inp["labels_all"].rows(B, 2 * B)
             if self.alg == "rcgan-u":          # fake logits for every label, weighted by the confusion rows (:654-684)
                 y_conf = O.gather_rows(ctx, self.confusion_matrix(), inp["labels_random"], B)
@@ -818,7 +863,7 @@ class CifarRCGAN:
                 parts = [(B, L.LOSS_HINGE_REAL, lab_r, None), (B, L.LOSS_HINGE_FAKE, lab_f, None)]
             Discriminator_head(feat, parts, w, self.loss_d, update_collection=None, logits=self.head_logits)
         elif self.alg == "rcgan-u":
-            feat_a, wgan_a = Discriminator(x_all, None, update_collection=None)
+            feat_a, wgan_a = Discriminator(d_in, None, update_collection=None)
             feat, wgan = O.rows(ctx, feat_a, 0, B), O.rows(ctx, wgan_a, 0, B)
             feat_f, wgan_f = O.rows(ctx, feat_a, B, 2 * B), O.rows(ctx, wgan_a, B, 2 * B)
             emb = Discriminator_projection(inp["labels"], update_collection=None)
@@ -829,7 +874,7 @@ class CifarRCGAN:
             O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d, wts=y_conf)   # :673,684
             O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real, w, self.loss_d)               # :674
         else:
-            feat, wgan = Discriminator(x_all, None, update_collection=None)              # :584
+            feat, wgan = Discriminator(d_in, None, update_collection=None)               # :584
             if self.alg in ("biased", "rcgan"):
                 emb = Discriminator_projection(inp["labels_all"], update_collection=None)    # :585
                 disc_all = O.proj_logit(ctx, feat, wgan, emb)                            # :588
@@ -876,8 +921,10 @@ class CifarRCGAN:
         self._prepare_all((self.PG, self.PD), head_update=NO_OPS)
         fake = Generator(n, inp["labels_random_G"], inp["z_G"])                                      # :719
         lab = inp["labels_random_G"] if self.alg in ("biased", "unbiased") else inp["labels_biased_G"]
+        # (augmented between Generator and Discriminator, the adjoint on the tape; perm_classifier below keeps `fake`)
+        d_in = O.diffaugment(ctx, fake, self._draw_aug(inp["aug_u_G"]), self.aug) if self.aug else fake
         if self.fused_head:
-            feat = Discriminator(fake, lab, update_collection=NO_OPS, _head=False)                   # :721-730
+            feat = Discriminator(d_in, lab, update_collection=NO_OPS, _head=False)                   # :721-730
             if self.alg == "rcgan-u":
                 y_conf = O.gather_rows(ctx, self.confusion_matrix(), inp["labels_random_G"], n)      # :757-758
                 parts = [(n, L.LOSS_NEG_MEAN, None, y_conf)]                                         # :751,759
@@ -885,7 +932,7 @@ class CifarRCGAN:
                 parts = [(n, L.LOSS_NEG_MEAN, lab, None)]                                            # :763,773
             Discriminator_head(feat, parts, 1.0, self.loss_g, update_collection=NO_OPS, logits=self.head_logits)
         else:
-            self._g_head_unfused(fake, lab, n)
+            self._g_head_unfused(d_in, lab, n)
         if self.perm:
             logits = perm_classifier(fake, self.perm_type)                                           # :781
             O.bce_onehot_term(ctx, logits, inp["labels_random_G"], self.perm_mult, self.loss_g)      # :782-784

@@ -925,6 +925,35 @@ def shortcut_a(ctx, x):
     return y
 
 
+def diffaugment(ctx, x, u, policy, pool=False):
+    """DiffAugment of NHWC images x [n, h, w, 3] (or their flattened rows [n, h*w*3] of square images) under the policy bits
+    L.AUG_*: colour jitter, integer translation, cutout, each sample from its row of u [n, 8] (fp32 uniforms in [0, 1), drawn by the
+    caller) -- rcgan_diffaugment_fwd, one launch, with its adjoint on the tape when x is tracked.  pool=True: also returns the 2x2
+    mean of the result out of the same launch (the bits of meanpool2 on it; not tracked: for a critic input that needs no gradient)."""
+    if len(x.shape) == 4:
+        n, h, w, c = x.shape
+    elif len(x.shape) == 2:
+        n, c = x.shape[0], 3
+        h = w = int(round((x.shape[1] // 3) ** 0.5))
+    if len(x.shape) not in (2, 4) or (len(x.shape) == 2 and h * w * 3 != x.shape[1]):
+        raise ValueError("diffaugment: images [n, h, w, 3] or rows of square 3-channel images, got %r" % (x.shape,))
+    if c != 3:
+        raise ValueError("diffaugment: 3-channel images, got %d channels" % c)
+    if tuple(u.shape) != (n, 8) or u.dtype != L.F32:
+        raise ValueError("diffaugment: u must be fp32 [%d, 8], got %r" % (n, u.shape))
+    y = ctx.empty(x.shape, x.dtype)
+    yp = ctx.empty((n, h // 2, w // 2, 3), x.dtype) if pool else None
+    ctx.check(ctx.lib.rcgan_diffaugment_fwd(ctx.h, n, h, w, x.dtype, policy, _p(x), _p(u), _p(y), _p(yp)))
+    if _track(ctx, y, x):
+        def bw():
+            if y.grad is None:
+                return
+            dx, acc = grad_of(ctx, x)
+            ctx.check(ctx.lib.rcgan_diffaugment_bwd(ctx.h, n, h, w, x.dtype, policy, _p(y.grad), _p(u), _p(dx), acc))
+        ctx.record(bw)
+    return (y, yp) if pool else y
+
+
 def upsample2(ctx, x):
     n, h, w, c = x.shape
     y = ctx.empty((n, h * 2, w * 2, c), x.dtype)

@@ -65,6 +65,8 @@ def define_flags():
     f.DEFINE_boolean("coarse_labels", False, "--dataset cifar100: train on the 20 coarse labels instead of the 100 fine ones")
     f.DEFINE_string("label_classifier", None, "weight asset of the generated-label-accuracy classifier (python -m "
                     "rcgan_amd.train_classifier writes one for any class count); default: the built-in CIFAR-10 network")
+    f.DEFINE_string("diffaugment", '', "differentiable augmentation of every image the critic sees: a comma-separated subset of "
+                    "color,translation,cutout (empty: off)")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -108,12 +110,15 @@ def main(argv=None):
         if asset_classes != N_CLASSES:
             raise ValueError("--label_classifier %s classifies %d classes, this run has %d"
                              % (FLAGS.label_classifier, asset_classes, N_CLASSES))
+    from .cifar import parse_diffaugment
+    parse_diffaugment(FLAGS.diffaugment)          # (a bad name fails here, before anything touches the GPU)
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
     logging.info('alpha = {}'.format(ALPHA))
     C_ALPHA = D.C_ALPHA(ALPHA, N_CLASSES)
     logging.info('dataset = {} ({} classes)'.format(FLAGS.dataset, N_CLASSES))
+    logging.info('diffaugment = {}'.format(FLAGS.diffaugment or 'off'))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -160,7 +165,7 @@ def main(argv=None):
                    confuse_init=FLAGS.confuse_init, confuse_init_diag=FLAGS.confuse_init_diag,
                    confuse_multiplier=FLAGS.confuse_multiplier, confuse_lr_decay=FLAGS.confuse_lr_decay,
                    device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision,
-                   n_classes=N_CLASSES)
+                   n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     if FLAGS.synthetic:
