@@ -403,6 +403,12 @@ int rcgan_preprocess_cifar(rcgan_ctx* ctx, int n, const int32_t* images_chw, con
                            int dtype, void* y_nhwc);
 
 /* Counter-based device RNG (Philox4x32-10).  kind 0: uniform [lo,hi); kind 1: normal(mean=lo, std=hi).
+ * Quad q of a stream is philox4x32-10 of the counter {lo32(offset + q), hi32(offset + q), 0x5eed5eed, 0} under the key
+ * {lo32(seed), hi32(seed)}; a draw of count numbers takes ceil(count / 4) quads (the last one may be cut).  With u = (r >> 8) * 2^-24
+ * of a word r, kind 0 is the fp32 number lo + (hi - lo) * u, and kind 1 is Box-Muller on the word pairs (0, 1) and (2, 3) of a quad
+ * with u = ((float)(r >> 8) + 0.5f) * 2^-24.  Kind 0 needs finite lo < hi and returns values of the OUTPUT type in [lo, hi): the fp32
+ * number is kept at the largest float below hi (the sum can round up to hi when lo != 0), and a 16-bit result between the smallest
+ * 16-bit value >= lo and the largest one < hi (EINVALID_ARG when there is none); fp32 draws with lo = 0 are hi * u unchanged.
  * state: DEVICE uint64[1] stream offset, advanced on the stream after the draw (so a replayed graph
  * draws fresh numbers), or NULL for offset 0.  Replaces tf.random_normal (gan_resnet.py:359) and the
  * tf.random_uniform dequantisation noise (gan_resnet.py:549); the TF Philox stream itself is not

@@ -276,8 +276,10 @@ __global__ void preprocess_cifar_kernel(int n, const int32_t* img, const float* 
 // tf.random_uniform (gan_resnet.py:549).  state[0..1] = 64-bit stream offset kept on the device so a
 // captured graph draws fresh numbers on every replay; rng_advance_kernel bumps it after each use.
 // kind 0: uniform [lo, hi)   kind 1: normal(mean=lo, std=hi)
+// [vmin, vmax]: for a 16-bit uniform draw, the smallest value >= lo and the largest value < hi the stored type holds (the rounding
+// of the fp32 number could leave [lo, hi): 0.0078124995 -> 1/128 in bf16); fp32 draws are kept below hi by philox_uniform
 template <typename T>
-__global__ void rng_fill_kernel(size_t count, int kind, float lo, float hi, uint64_t seed, const uint64_t* state, T* y) {
+__global__ void rng_fill_kernel(size_t count, int kind, float lo, float hi, float vmin, float vmax, uint64_t seed, const uint64_t* state, T* y) {
   const uint64_t base = state ? state[0] : 0;
   const size_t nquad = (count + 3) / 4;
   for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (size_t)gridDim.x * blockDim.x) {
@@ -286,7 +288,10 @@ __global__ void rng_fill_kernel(size_t count, int kind, float lo, float hi, uint
     float v[4];
     if (kind == 0) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = philox_uniform(r[i], lo, hi);
+      for (int i = 0; i < 4; ++i) {
+        v[i] = philox_uniform(r[i], lo, hi);
+        if (sizeof(T) == 2) v[i] = fminf(fmaxf(v[i], vmin), vmax);
+      }
     } else {
 #pragma unroll
       for (int i = 0; i < 4; i += 2) {
@@ -305,6 +310,21 @@ __global__ void rng_fill_kernel(size_t count, int kind, float lo, float hi, uint
 
 __global__ void rng_advance_kernel(uint64_t* state, uint64_t n) { state[0] += n; }
 
+// the next 16-bit value above / below b (sign-magnitude patterns, both formats)
+static inline bf16_t h16_step(bf16_t b, bool up) {
+  if ((b & 0x7fff) == 0) return up ? 0x0001 : 0x8001;
+  return (((b & 0x8000) != 0) != up) ? b + 1 : b - 1;
+}
+
+// the smallest value >= lo and the largest value < hi that `dtype` holds
+static inline void uniform_bounds(int dtype, float lo, float hi, float* vmin, float* vmax) {
+  if (dtype != RCGAN_H16) { *vmin = lo; *vmax = float_below(hi); return; }
+  bf16_t bl = f32_to_bf16(lo), bh = f32_to_bf16(hi);
+  if (bf16_to_f32(bl) < lo) bl = h16_step(bl, true);
+  if (bf16_to_f32(bh) >= hi) bh = h16_step(bh, false);
+  *vmin = bf16_to_f32(bl); *vmax = bf16_to_f32(bh);
+}
+
 // y[row][before + c] = x[row][c], zero in the `before` leading and `after` trailing channels (tf.pad on the channel axis:
 // the option-A shortcut of the label-classifier ResNet, resnet-110/graph_optimized.pb nodes conv{2,3}_0/Pad)
 template <typename T>
@@ -322,7 +342,14 @@ extern "C" {
 
 int rcgan_rng_fill(rcgan_ctx* ctx, size_t count, int dtype, int kind, float lo, float hi, uint64_t seed, void* state, void* y) {
   RC_REQUIRE(ctx, kind == 0 || kind == 1, "kind %d", kind);
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(rng_fill_kernel<T>, dim3(ew_grid((count + 3) / 4)), dim3(EW_BLOCK), 0, ctx->stream, count, kind, lo, hi, seed, (const uint64_t*)state, (T*)y));
+  float vmin = lo, vmax = hi;
+  if (kind == 0) {
+    RC_REQUIRE(ctx, lo < hi && lo - lo == 0.f && hi - hi == 0.f, "uniform range [%g, %g) is empty or not finite", lo, hi);
+    RC_REQUIRE(ctx, dtype == RCGAN_F32 || dtype == RCGAN_H16, "bad dtype %d", dtype);
+    uniform_bounds(dtype, lo, hi, &vmin, &vmax);
+    RC_REQUIRE(ctx, vmin <= vmax, "the output type holds no value in [%g, %g)", lo, hi);
+  }
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(rng_fill_kernel<T>, dim3(ew_grid((count + 3) / 4)), dim3(EW_BLOCK), 0, ctx->stream, count, kind, lo, hi, vmin, vmax, seed, (const uint64_t*)state, (T*)y));
   RC_LAUNCH_CHECK(ctx);
   if (state) {
     hipLaunchKernelGGL(rng_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, (uint64_t*)state, (uint64_t)((count + 3) / 4));

@@ -22,4 +22,17 @@ __device__ __forceinline__ void philox4(uint64_t ctr, uint32_t seed_lo, uint32_t
   out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
 }
 
-__device__ __forceinline__ float philox_uniform(uint32_t r, float lo, float hi) { return lo + (hi - lo) * ((float)(r >> 8) * (1.0f / 16777216.0f)); }
+// the largest float below x (x finite)
+__host__ __device__ inline float float_below(float x) {
+  uint32_t u = __builtin_bit_cast(uint32_t, x);
+  u = (u << 1) == 0 ? 0x80000001u : (u >> 31) ? u + 1 : u - 1;
+  return __builtin_bit_cast(float, u);
+}
+
+// uniform in [lo, hi): lo + (hi - lo) * u with u = (r >> 8) * 2^-24 in [0, 1 - 2^-24].  The fp32 sum can round up to hi itself when
+// lo != 0 ((1, 2) and (0.5, 1.5) at u = 1 - 2^-24), so it is kept at the largest float below hi; with lo = 0 the product hi * u is
+// below hi already and passes unchanged.
+__device__ __forceinline__ float philox_uniform(uint32_t r, float lo, float hi) {
+  const float v = lo + (hi - lo) * ((float)(r >> 8) * (1.0f / 16777216.0f));
+  return v < hi ? v : float_below(hi);
+}
