@@ -671,10 +671,6 @@ int rcgan_conv_prepare_batch_frags(rcgan_ctx* ctx, const rcgan_prepare_item* ite
 }
 
 size_t rcgan_conv_workspace_bytes(const rcgan_conv_desc* d) {
-  int oh, ow, p;
-  same_pad(d->h, d->kh, d->stride, &oh, &p);
-  same_pad(d->w, d->kw, d->stride, &ow, &p);
-  long M = (long)d->n * oh * ow;
   size_t ws = direct_wgrad_ws_bytes(d);
   if (small_wgrad_kind(d)) {
     size_t s = small_wgrad_ws_bytes(d);
@@ -684,10 +680,7 @@ size_t rcgan_conv_workspace_bytes(const rcgan_conv_desc* d) {
     size_t s = img_wgrad_ws_bytes(d);
     if (s > ws) ws = s;
   }
-  if (mfma_wgrad_eligible(d)) {
-    size_t s = (size_t)mfma_wgrad_splits(d, M) * ((size_t)d->kh * d->kw * d->cin + 1) * d->cout * sizeof(float) + (size_t)(cdiv(M, 2048) + 1024) * d->cout * sizeof(float) + 256;
-    if (s > ws) ws = s;
-  }
+  if (mfma_wgrad_eligible(d)) ws = std::max(ws, mfma_wgrad_ws_bytes(d));
   // upsample-folded data gradient: full-resolution dx scratch
   if (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) {
     size_t s = (size_t)d->n * d->h * d->w * d->cin * dtype_size(d->dtype) + 256;
@@ -993,10 +986,10 @@ static int wgrad_pose(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, c
   a.M = (long)d->n * a.H * a.W;
   a.lw = ilog2_exact(a.W); a.lh = ilog2_exact(a.H);
   if (a.lw < 0 || a.lh < 0) { a.lw = -1; a.lh = -1; }
-  a.slab_stride = (long)a.cells * d->cin * d->cout + d->cout;
+  a.slab_stride = wgrad_slab_floats(a, 1);
   a.want_bias = want_bias ? 1 : 0;
   a.m_chunk = 0;
-  *nz = a.sub ? mfma_wgrad_sub_splits(d, a.M) : mfma_wgrad_splits(d, a.M);
+  *nz = mfma_wgrad_splits(d, a.M, a.sub);
   return RCGAN_OK;
 }
 
@@ -1030,7 +1023,7 @@ int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void
     if (rc) return rc;
     a.slab = (float*)ws;
     long cnt = (long)d->kh * d->kw * d->cin * d->cout;
-    size_t need = (size_t)nz * a.slab_stride * sizeof(float) + (size_t)(cdiv(a.M, 2048) + 1024) * d->cout * sizeof(float);
+    size_t need = mfma_wgrad_ws_need(nz, a.slab_stride, a.M, d->cout);
     if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
     bool bias_done = false;
     int nzz = mfma_wgrad_launch(ctx, a, nz, &bias_done, ws_bytes);
@@ -1081,7 +1074,7 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
                                   float* const* dws, float* const* dbiases, int accumulate, void* ws, size_t ws_bytes) {
   RC_REQUIRE(ctx, n >= 0 && (n == 0 || (descs && xs && dys && dws && dbiases)), "null argument");
   static const int target_blocks = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_BLOCKS"); return e ? atoi(e) : 448; }();      // (512 before the sub-pixel forms: 6.67 -> 6.64 ms with 384; round 4, the critic step's launch with its chunks' workgroups on one XCD and the generator step's big layers gone to the nine-tap kernel, same box: 384 5.65 ms, 448 5.59, 512 5.60, 576 5.75)
-  struct Cand { MfmaWgradArgs a; int nz; int takes; };      // takes: 0 not grouped, 1 three-tap kernel, 2 / 3 nine-tap kernel plain / sub-pixel
+  struct Cand { MfmaWgradArgs a = {}; int nz = 0; WgradKernel k = WK_TAP_REG; };      // (WK_TAP_REG: not grouped -- no matrix-core layer, or that kernel)
   std::vector<Cand> cand(n);
   // The nine-tap kernel (conv_wgrad9.hip) takes the group's 3x3 layers when they are big: its one workgroup per CU writes a slab of ALL nine
   // (sixteen) cells, and the riders of the three-tap launch (image-end layers, 1x1 shortcuts, the head) lose the workgroups they hid under.
@@ -1110,11 +1103,11 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
     MfmaWgradArgs& a = cand[i].a;
     rc = wgrad_pose(ctx, d, xs[i], dys[i], dbiases[i] != nullptr, a, &cand[i].nz);
     if (rc) return rc;
-    if (mfma_wgrad9_takes(a) && wgrad9_group_on) {
-      cand[i].takes = a.sub ? 3 : 2;
+    rc = mfma_wgrad_choose(ctx, a, wgrad9_group_on ? WGRAD9_ON : WGRAD9_OFF, &cand[i].k);
+    if (rc) return rc;
+    if (cand[i].k == WK_NINE) {
       work9[a.sub ? 1 : 0] += (double)a.M * (a.Cin / 64) * (a.Cout / 128) * (a.sub ? 2 : 1);
-    } else if (mfma_wgrad3_takes(a)) {
-      cand[i].takes = 1;
+    } else if (cand[i].k == WK_THREE) {
       // workgroup-passes over a pixel: 3 filter rows of three taps, or 8 (parity, row shift) tiles of two taps
       work += (double)a.M * (a.sub == 3 ? 1.0 / 3.0 : (a.sub ? 8 * 2.0 / 3.0 : a.KH)) * (a.Cin / 64) * (a.Cout / 128);
     }
@@ -1134,10 +1127,10 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
     for (int it = 0; it < 4096 && work9[f] > 0; ++it, px9[f] += 128) {
       long tot = 0;
       for (int i = 0; i < n; ++i)
-        if (cand[i].takes == 2 + f) {
-          MfmaWgradArgs b = cand[i].a;
-          unsigned bgx = 0, bgy = 0;
-          if (mfma_wgrad9_plan(b, 1 << 20, &bgx, &bgy, px9[f])) tot += (long)bgx * bgy;
+        if (cand[i].k == WK_NINE && (cand[i].a.sub != 0) == (f != 0)) {
+          MfmaWgradPlanned b = {cand[i].a, 0, 0};
+          mfma_wgrad_plan(b, WK_NINE, 1 << 20, px9[f]);
+          tot += (long)b.gx * b.gy;
         }
       if (tot <= target9) break;
     }
@@ -1154,7 +1147,7 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
   for (int q = 0; q <= IMG_GROUP_MAX; ++q) img.first[q] = 0;
   static const int img_group = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_IMG"); return e ? atoi(e) : 1; }();
   bool any_group = false;
-  for (int i = 0; i < n && img_group; ++i) any_group = any_group || cand[i].takes == 1;
+  for (int i = 0; i < n && img_group; ++i) any_group = any_group || cand[i].k == WK_THREE;
   for (int i = 0; i < n; ++i) {
     const rcgan_conv_desc* d = descs + i;
     bool grouped = false;
@@ -1185,25 +1178,22 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
         grouped = true;
       }
     }
-    if (!grouped && mfma_wgrad_eligible(d)) {
+    const WgradKernel k = cand[i].k;
+    if (!grouped && k != WK_TAP_REG) {
       MfmaWgradPlanned p = {cand[i].a, 0, 0};
       MfmaWgradArgs& a = p.a;
-      const int nz = cand[i].nz, takes = cand[i].takes;
       // (the grouped slabs are fitted into the workspace below: no a-priori bound on the nine-tap kernel's pixel chunks)
-      const bool nine = takes >= 2 && mfma_wgrad9_plan(a, 1 << 20, &p.gx, &p.gy, px9[takes - 2]);
-      const bool three = !nine && takes && mfma_wgrad3_plan(a, nz, &p.gx, &p.gy, px);
-      if (a.sub && !three && !nine) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "sub-pixel filter gradient needs the three-tap kernel");
-      if (nine || three || mfma_wgrad_tap_plan(a, nz, &p.gx, &p.gy)) {
-        const size_t need = ((size_t)p.gy * a.slab_stride * sizeof(float) + 255) / 256 * 256;
-        if (used + need <= ws_bytes / 2) {
-          a.slab = (float*)((char*)ws + used);
-          used += need;
-          if (nine) fam9[(a.sub ? 2 : 0) + (a.relu_in ? 1 : 0)].push_back(p);
-          else if (three && a.sub == 3 && !a.relu_in) late.push_back(p);       // placed below
-          else fam[three ? (a.relu_in ? 1 : 0) : 2].push_back(p);
-          red.push_back(wgrad_reduce_item(d, a, dws[i], dbiases[i], dbiases[i] ? d->cout : 0, (int)p.gy, accumulate));
-          grouped = true;
-        }
+      if (k == WK_NINE) mfma_wgrad_plan(p, k, 1 << 20, px9[a.sub ? 1 : 0]);
+      else mfma_wgrad_plan(p, k, cand[i].nz, px);
+      const size_t need = ((size_t)p.gy * a.slab_stride * sizeof(float) + 255) / 256 * 256;
+      if (used + need <= ws_bytes / 2) {
+        a.slab = (float*)((char*)ws + used);
+        used += need;
+        if (k == WK_NINE) fam9[(a.sub ? 2 : 0) + (a.relu_in ? 1 : 0)].push_back(p);
+        else if (k == WK_THREE && a.sub == 3 && !a.relu_in) late.push_back(p);       // placed below
+        else fam[k == WK_THREE ? (a.relu_in ? 1 : 0) : 2].push_back(p);
+        red.push_back(wgrad_reduce_item(d, a, dws[i], dbiases[i], dbiases[i] ? d->cout : 0, (int)p.gy, accumulate));
+        grouped = true;
       }
     }
     if (!grouped) {          // its own launches, with the workspace half the grouped slabs do not use
@@ -1219,17 +1209,17 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
     const int f = wgrad_busiest_family(fam, 2, (size_t)-1, false, false);
     fam[f].insert(fam[f].end(), late.begin(), late.end());
   }
-  // * the image-end workgroups ride in a family's FIRST launch (mfma_wgrad3_group_launch: WGRAD_GROUP_MAX_HOST problems) -- deliberately only
+  // * the image-end workgroups ride in a family's FIRST launch (mfma_wgrad3_group_launch: WGRAD_GROUP_MAX problems) -- deliberately only
   //   those count and the family must exist; a tie goes to the later one, and the per-tap family (2) is a candidate
   int img_f = -1;
   if (img.n) {
-    img_f = wgrad_busiest_family(fam, 3, WGRAD_GROUP_MAX_HOST, true, true);
+    img_f = wgrad_busiest_family(fam, 3, WGRAD_GROUP_MAX, true, true);
     RC_REQUIRE(ctx, img_f >= 0, "image-end filter gradients planned without a grouped launch");
   }
   // * the projection head's deferred parameter sums (head_rider.h) need a three-tap launch (families 0, 1): they follow the image-end
   //   workgroups there, else the same rule over those two
   int head_f = -1;
-  if (ctx->head_stage == 2) head_f = (img_f == 0 || img_f == 1) ? img_f : wgrad_busiest_family(fam, 2, WGRAD_GROUP_MAX_HOST, true, true);
+  if (ctx->head_stage == 2) head_f = (img_f == 0 || img_f == 1) ? img_f : wgrad_busiest_family(fam, 2, WGRAD_GROUP_MAX, true, true);
   for (int f = 0; f < 4; ++f)
     if (!fam9[f].empty()) {
       int rc = mfma_wgrad9_group_launch(ctx, (int)fam9[f].size(), fam9[f].data());

@@ -91,8 +91,19 @@ static inline int wgrad3_rows(const MfmaWgradArgs& a) { return a.sub == 3 ? 1 : 
 static inline int wgrad3_alg_taps(const MfmaWgradArgs& a) { return a.sub == 3 ? 1 : (a.sub ? 36 : a.KH * a.KW); }
 static inline int wgrad3_exec_taps(const MfmaWgradArgs& a) { return a.sub == 3 ? 1 : (a.sub ? 16 : a.KH * a.KW); }
 
-// a filter-gradient problem planned into a grouped launch: gx tiles x gy pixel chunks of workgroups
+// floats of one slab: the filter cells, then bias_tails rows of bias-gradient partials
+static inline long wgrad_slab_floats(const MfmaWgradArgs& a, int bias_tails) { return (long)a.cells * a.Cin * a.Cout + (long)bias_tails * a.Cout; }
+// a planned filter-gradient problem (mfma_wgrad_plan): gx tiles x gy pixel chunks of workgroups
 struct MfmaWgradPlanned { MfmaWgradArgs a; unsigned gx, gy; };
+// The four filter-gradient kernels in their order of precedence (mfma_wgrad_choose): all nine taps (sixteen sub-pixel cells) of a tile per
+// workgroup (conv_wgrad9.hip); a filter row of three taps, the only home of the 1x1 form; one tap, direct-to-LDS; one tap, register-staged
+// (single launches only).  WgradNine: the nine-tap kernel is on offer by the layer's own work (a launch alone), not at all, or wherever it
+// takes the layer (a group decides for all its layers).  WGRAD*_ALONE_WGS: the workgroups a layer's launch alone aims at, per kernel.
+enum WgradKernel { WK_NINE, WK_THREE, WK_TAP_GLDS, WK_TAP_REG };
+enum WgradNine { WGRAD9_BY_WORK, WGRAD9_OFF, WGRAD9_ON };
+constexpr int WGRAD_TAP_ALONE_WGS = 768, WGRAD3_ALONE_WGS = 512, WGRAD9_ALONE_WGS = 256;
+// a filter gradient's workspace: nz slabs, then the column-sum partials of a bias gradient that the kernel leaves to colsum_launch
+static inline size_t mfma_wgrad_ws_need(size_t nz, size_t slab_floats, long M, int cout) { return (nz * slab_floats + (size_t)((M + 2047) / 2048 + 1024) * cout) * sizeof(float); }
 
 static inline int ilog2_exact(int v) {
   int l = 0;
@@ -112,24 +123,23 @@ int bn_tile_stats_finish_launch(rcgan_ctx* ctx, const float* part, int c, int ns
                                 double count, float eps, float* mean, float* rstd);      // bn.hip
 bool mfma_conv_is_p8(const MfmaConvArgs& a);              // routed to the 256 x 256 eight-wave kernel
 bool mfma_conv8_phase_form(const MfmaConvArgs& a);        // ... which evaluates it in the sub-pixel (phase-major tile) form
-int mfma_wgrad_splits(const rcgan_conv_desc* d, long M);
-bool mfma_wgrad3_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy, long px_per_block);
-bool mfma_wgrad3_takes(const MfmaWgradArgs& a);
+int mfma_wgrad_splits(const rcgan_conv_desc* d, long M, int sub);
+size_t mfma_wgrad_ws_bytes(const rcgan_conv_desc* d);
 int mfma_wgrad_sub_kind(const rcgan_conv_desc* d, int use_tr);
-int mfma_wgrad_sub_splits(const rcgan_conv_desc* d, long M);
+int mfma_wgrad_choose(rcgan_ctx* ctx, const MfmaWgradArgs& a, WgradNine nine, WgradKernel* k);
+void mfma_wgrad_plan(MfmaWgradPlanned& p, WgradKernel k, int nz, long px_per_block);
+#define WGRAD_GROUP_MAX 12        // problems per grouped launch of the three-tap / per-tap kernels (WgradGroup)
 int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs, int family, const ImgWGroup* img, bool carry_head = false);
-bool mfma_wgrad_tap_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy);
 // conv_wgrad9.hip: all nine taps of a plain 3x3 layer in one workgroup (dy and x staged once for the three filter rows)
 #define WGRAD9_GROUP_MAX 12
 bool mfma_wgrad9_takes(const MfmaWgradArgs& a);
-bool mfma_wgrad9_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy, long px_per_block);
+void mfma_wgrad9_plan(MfmaWgradPlanned& p, int nz, long px_per_block);      // mfma_wgrad_plan's nine-tap case
 int mfma_wgrad9_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs);
 int mfma_wgrad_launch(rcgan_ctx* ctx, MfmaWgradArgs& a, int nz, bool* bias_done, size_t ws_bytes);
 int mfma_prepare_launch(rcgan_ctx* ctx, const float* w, const float* sigma, bf16_t* wt, bf16_t* wd, int T, int Cin, int Cout);
 int direct_prepare_launch(rcgan_ctx* ctx, const float* w, const float* sigma, float* out, long total);
 int mfma_selftest(rcgan_ctx* ctx, int* host_result);
 // image-end kernels (conv_image.hip): bf16 convs with a <= 3-channel side
-#define WGRAD_GROUP_MAX_HOST 12   /* = WGRAD_GROUP_MAX of conv_mfma.hip */
 int img_side(const rcgan_conv_desc* d);          // 0: not taken; 1: cin small; 2: cout small
 size_t img_extra_offset(const rcgan_conv_desc* d);
 size_t img_extra_bytes(const rcgan_conv_desc* d);

@@ -980,7 +980,7 @@ __device__ __forceinline__ void wgrad3_body(const MfmaWgradArgs& a, const unsign
   // to the sub-pixel form sub = 1).  A K-step advances the reduction index by 32 pixels = whole grid
   // rows (W divides 32), so every lane's source address advances by the SAME amount per step, also in the strided sub-pixel forms (4 W elements
   // per grid row of the full-resolution tensor): dy is fetched through a scalar base that steps + a constant per-lane offset -- no vector ALU
-  // work at all (chunks are whole K-steps: mfma_wgrad3_takes) --, x through a per-lane offset that steps, with the in-image test (halo rows
+  // work at all (chunks are whole K-steps: wgrad3_geom) --, x through a per-lane offset that steps, with the in-image test (halo rows
   // read the zero page) as two compares and a select instead of the pixel's decomposition, three multiplies and two divergent branches.
   auto y_lin = [&](int row) -> unsigned {        // element offset of pixel (step base + row), step base = a multiple of 32
     if (sub != 1) return (unsigned)(row * aCout);
@@ -1139,8 +1139,6 @@ __global__ __launch_bounds__(256) void conv_mfma_wgrad3_kernel(MfmaWgradArgs a) 
 // Several layers' filter gradients in ONE launch: workgroup b belongs to the problem p with first[p] <= b < first[p+1]
 // and plays (b - first[p]) % gx[p], (b - first[p]) / gx[p] of that problem's own grid.  The 8x8 / 16x16 discriminator layers
 // launch 224..602 workgroups each and are latency-bound alone; together their workgroups share the CUs (3 fit per CU).
-#define WGRAD_GROUP_MAX 12
-static_assert(WGRAD_GROUP_MAX == WGRAD_GROUP_MAX_HOST, "group size");
 // The image-end layers' filter gradients (conv_image.h: D.Block.1.Conv1 / Shortcut) ride in the same launch as its LAST
 // img.first[IMG_GROUP_MAX] workgroups.  Alone they are two launches of a few hundred short workgroups plus two slab reductions
 // (59 us per critic step, 4 % of the iteration); here ~128 workgroups per layer walk their pixel blocks in the CU slots the
@@ -1866,9 +1864,11 @@ static bool wgrad3_geom(const MfmaWgradArgs& a) {     // (sub-pixel and 1x1 form
   return a.sub ? wgrad3_shape(3, 3, a.H, a.W) : (wgrad3_shape(a.KH, a.KW, a.H, a.W) && a.PL == 1);
 }
 
-static int wgrad3_enabled() {
+// RCGAN_WGRAD_IMPL (read once): unset = every kernel; "glds" = the per-tap kernels only; "reg" = only the register-staged per-tap kernel
+enum { WGRAD_IMPL_ALL, WGRAD_IMPL_GLDS, WGRAD_IMPL_REG };
+static int wgrad_impl() {
   static int v = -1;
-  if (v < 0) { const char* e = getenv("RCGAN_WGRAD_IMPL"); v = (e && (e[0] == 'r' || e[0] == 'g')) ? 0 : 1; }
+  if (v < 0) { const char* e = getenv("RCGAN_WGRAD_IMPL"); v = (e && e[0] == 'r') ? WGRAD_IMPL_REG : (e && e[0] == 'g') ? WGRAD_IMPL_GLDS : WGRAD_IMPL_ALL; }
   return v;
 }
 
@@ -1881,28 +1881,41 @@ static long wgrad_clamp_splits(long want, long M) {
   return want;
 }
 
-int mfma_wgrad_splits(const rcgan_conv_desc* d, long M) {
+// the three-tap kernel's tiles (rows: wgrad3_rows) and the pixel chunks of a layer ALONE on it
+static long wgrad3_tiles(int rows, int cin, int cout) { return (long)rows * (cin / 64) * (cout / 128); }
+static long wgrad3_alone_chunks(int rows, int cin, int cout, long M) {
+  return wgrad_clamp_splits((WGRAD3_ALONE_WGS + wgrad3_tiles(rows, cin, cout) - 1) / wgrad3_tiles(rows, cin, cout), M);
+}
+
+// The pixel chunks a layer's slabs are sized for: the most that any kernel mfma_wgrad_choose may pick plans for it alone (sub, M: as posed)
+int mfma_wgrad_splits(const rcgan_conv_desc* d, long M, int sub) {
+  if (sub) return (int)wgrad3_alone_chunks(d->kh == 1 ? 1 : 8, d->cin, d->cout, M);
   long tiles = (long)d->kh * d->kw * (d->cin / 128) * (d->cout / 128);
-  long want = wgrad_clamp_splits((768 + tiles - 1) / tiles, M);
-  if (wgrad3_shape(d->kh, d->kw, d->h, d->w)) {      // workspace must cover whichever kernel the launch picks
-    long tiles3 = (long)d->kh * (d->cin / 64) * (d->cout / 128);
-    long want3 = wgrad_clamp_splits((512 + tiles3 - 1) / tiles3, M);
-    if (want3 > want) want = want3;
-    // ... or the nine-tap kernel: one round of 256 workgroups (a 256-channel layer: 8 tiles x 32 chunks, not the 22 of the rule above)
-    if (d->cin % 64 == 0 && d->cout % 128 == 0) {
-      long tiles9 = (long)(d->cin / 64) * (d->cout / 128);
-      long want9 = wgrad_clamp_splits((256 + tiles9 - 1) / tiles9, M);
-      if (want9 > want) want = want9;
-    }
+  long want = wgrad_clamp_splits((WGRAD_TAP_ALONE_WGS + tiles - 1) / tiles, M);
+  if (wgrad3_shape(d->kh, d->kw, d->h, d->w)) {
+    want = std::max(want, wgrad3_alone_chunks(d->kh, d->cin, d->cout, M));
+    // ... or the nine-tap kernel: one round of workgroups (a 256-channel layer: 8 tiles x 32 chunks, not the 22 of the rule above)
+    const long tiles9 = (long)(d->cin / 64) * (d->cout / 128);
+    if (d->cin % 64 == 0 && d->cout % 128 == 0) want = std::max(want, wgrad_clamp_splits((WGRAD9_ALONE_WGS + tiles9 - 1) / tiles9, M));
   }
   return (int)want;
+}
+
+// What rcgan_conv_workspace_bytes promises a matrix-core filter gradient: the slabs of the PLAIN pose on the full-resolution grid.  (The call
+// checks mfma_wgrad_ws_need of its own pose -- the sub-pixel one: 16 cells per slab, chunks of the low-resolution grid --, not this promise.)
+size_t mfma_wgrad_ws_bytes(const rcgan_conv_desc* d) {
+  int oh, ow, p;
+  same_pad(d->h, d->kh, d->stride, &oh, &p);
+  same_pad(d->w, d->kw, d->stride, &ow, &p);
+  const long M = (long)d->n * oh * ow;
+  return mfma_wgrad_ws_need(mfma_wgrad_splits(d, M, 0), ((size_t)d->kh * d->kw * d->cin + 1) * d->cout, M, d->cout) + 256;
 }
 
 // Sub-pixel filter gradient (MfmaWgradArgs::sub) of an upsample-3x3 (1) or ConvMeanPool (2) layer: 0 where the layer is posed
 // as an ordinary 3x3 filter gradient (shape the three-tap kernel does not take, RCGAN_WGRAD_SUBPIXEL=0)
 int mfma_wgrad_sub_kind(const rcgan_conv_desc* d, int use_tr) {
   static const int on = env_int("RCGAN_WGRAD_SUBPIXEL", 1);
-  if (!use_tr || !wgrad3_enabled() || !mfma_wgrad_eligible(d)) return 0;
+  if (!use_tr || wgrad_impl() != WGRAD_IMPL_ALL || !mfma_wgrad_eligible(d)) return 0;
   if (d->kh == 1 && d->kw == 1) {
     // a SMALL 1x1 (the down blocks' shortcuts: 0.27 GFLOP at the bench batch) rides in the grouped launch on the two-tap body; a big
     // one keeps the per-tap kernel's 128 x 128 tiles (a staged pixel feeds one tap's MFMAs here: a third of the arithmetic intensity)
@@ -1917,11 +1930,6 @@ int mfma_wgrad_sub_kind(const rcgan_conv_desc* d, int use_tr) {
   if (up == pool || (d->h & 1) || (d->w & 1)) return 0;
   if (!wgrad3_shape(3, 3, d->h / 2, d->w / 2) || ((long)d->n * (d->h / 2) * (d->w / 2)) % 32 != 0) return 0;
   return up ? 1 : 2;
-}
-
-int mfma_wgrad_sub_splits(const rcgan_conv_desc* d, long M) {
-  const long tiles3 = (d->kh == 1 ? 1L : 8L) * (d->cin / 64) * (d->cout / 128);
-  return (int)wgrad_clamp_splits((512 + tiles3 - 1) / tiles3, M);
 }
 
 template <bool RELU>
@@ -1942,85 +1950,85 @@ static int launch_wgrad3(rcgan_ctx* ctx, MfmaWgradArgs& a, dim3 grid) {
   return RCGAN_OK;
 }
 
-int mfma_wgrad_launch(rcgan_ctx* ctx, MfmaWgradArgs& a, int nz, bool* bias_done, size_t ws_bytes) {
-  *bias_done = false;
-  if (a.sub && !mfma_wgrad3_takes(a)) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "sub-pixel filter gradient needs the three-tap kernel");
+template <bool GLDS>      // the per-tap kernels: direct-to-LDS or register-staged
+static int launch_wgrad_tap(rcgan_ctx* ctx, const MfmaWgradArgs& a, dim3 grid) {
+  constexpr int NS = 4;
+  const void* kernel = GLDS ? (const void*)conv_mfma_wgrad_glds_kernel<NS> : (const void*)conv_mfma_wgrad_kernel;
+  const size_t lds = GLDS ? (size_t)NS * 2 * 32 * 256 : (size_t)4 * 64 * WG_PITCH * sizeof(bf16_t);
+  static bool attr = false;
+  if (!attr) {
+    RC_HIP(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    attr = true;
+  }
   {
+    ProfScope ps(ctx, RCGAN_PROF_WGRAD_MFMA, 2.0 * (double)a.M * a.KH * a.KW * a.Cin * a.Cout);
+    if constexpr (GLDS) hipLaunchKernelGGL(conv_mfma_wgrad_glds_kernel<NS>, grid, dim3(256), lds, ctx->stream, a);
+    else hipLaunchKernelGGL(conv_mfma_wgrad_kernel, grid, dim3(256), lds, ctx->stream, a);
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+// THE choice of a filter-gradient kernel for a posed problem: the only holder of the precedence nine-tap > three-tap > per-tap direct-to-LDS >
+// per-tap register-staged, the only reader of RCGAN_WGRAD_IMPL (wgrad_impl) and of RCGAN_WGRAD9_MINWORK; mfma_wgrad_launch and the group
+// planner (rcgan_conv2d_bwd_weight_group) launch what it returns.  nine: how the nine-tap kernel is on offer (WgradNine).
+int mfma_wgrad_choose(rcgan_ctx* ctx, const MfmaWgradArgs& a, WgradNine nine, WgradKernel* k) {
+  const bool three = wgrad_impl() == WGRAD_IMPL_ALL && a.use_tr && a.zero != nullptr && wgrad3_geom(a);
+  if (a.sub && !three) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "sub-pixel filter gradient needs the three-tap kernel");
+  if (nine == WGRAD9_BY_WORK) {
     // the nine-tap kernel where a workgroup's share of the pixels amortises its nine-cell slab (scripts/bench_conv.py, n = 128, layers alone:
     // 32x32 256-channel 175 -> 142 us, 32x32 128-channel 72 -> 67, 16x16 256-channel 60 -> 60; but 8x8 256-channel 32 -> 37, 8x8 128-channel
     // 21 -> 28, the sub-pixel forms 43 -> 83 / 122 -> 128: those stay on the three-tap kernel)
     const long min_work = env_int("RCGAN_WGRAD9_MINWORK", 200000);        // (read per call: the tests force the kernel on small shapes)
     const long work9 = a.M * (long)(a.Cin / 64) * (a.Cout / 128);
-    // (planned on a copy: the plan rewrites slab_stride -- the upsample form carries two bias tails per slab -- AFTER the caller sized
-    // the workspace for the stride it knew; the nine-tap kernel only runs if its slabs fit what the caller really handed over)
-    MfmaWgradPlanned p9 = {a, 0, 0};
-    if ((a.sub ? min_work <= 0 : work9 >= min_work) && mfma_wgrad9_plan(p9.a, nz, &p9.gx, &p9.gy, 0) &&
-        (size_t)p9.gy * (size_t)p9.a.slab_stride * sizeof(float) <= ws_bytes) {
-      a = p9.a;
-      int rc = mfma_wgrad9_group_launch(ctx, 1, &p9);
-      *bias_done = a.want_bias != 0;
-      return rc ? -1 : (int)p9.gy;
-    }
+    nine = (a.sub ? min_work <= 0 : work9 >= min_work) ? WGRAD9_ON : WGRAD9_OFF;
   }
-  if (wgrad3_enabled() && a.use_tr && a.zero != nullptr && wgrad3_geom(a)) {
-    long tiles3 = (long)wgrad3_rows(a) * (a.Cin / 64) * (a.Cout / 128);
-    int want = (int)wgrad_clamp_splits((512 + tiles3 - 1) / tiles3, a.M);
+  *k = nine == WGRAD9_ON && mfma_wgrad9_takes(a) ? WK_NINE : three ? WK_THREE
+     : wgrad_impl() != WGRAD_IMPL_REG && a.zero != nullptr ? WK_TAP_GLDS : WK_TAP_REG;
+  return RCGAN_OK;
+}
+
+// THE plan of problem p.a on kernel k: pixel chunk, slab stride and grid of gx tiles x gy <= nz pixel chunks.  px_per_block > 0 (three- and
+// nine-tap kernel in a group): the caller fixes the pixels per workgroup for all layers (equal workgroup run times, far fewer fp32 slabs to write
+// and reduce); 0: chunks for WGRAD*_ALONE_WGS workgroups.  The per-tap kernels take the nz chunks the slabs were sized for, alone or grouped.
+void mfma_wgrad_plan(MfmaWgradPlanned& p, WgradKernel k, int nz, long px_per_block) {
+  MfmaWgradArgs& a = p.a;
+  if (k == WK_NINE) return mfma_wgrad9_plan(p, nz, px_per_block);
+  long want = nz;
+  p.gx = (unsigned)(a.KH * a.KW * (a.Cin / 128) * (a.Cout / 128));
+  if (k == WK_THREE) {
+    want = px_per_block > 0 ? wgrad_clamp_splits(cdiv(a.M, px_per_block), a.M) : wgrad3_alone_chunks(wgrad3_rows(a), a.Cin, a.Cout, a.M);
     if (want > nz) want = nz;
-    a.m_chunk = ((a.M + want - 1) / want + 63) / 64 * 64;
-    int nzz = cdiv(a.M, a.m_chunk);
-    dim3 grid((unsigned)(tiles3 + (a.want_bias ? a.Cout / 128 : 0)), nzz);
-    int rc = a.relu_in ? launch_wgrad3<true>(ctx, a, grid) : launch_wgrad3<false>(ctx, a, grid);
-    *bias_done = a.want_bias != 0;
-    return rc ? -1 : nzz;
+    if (want < 1) want = 1;
+    p.gx = (unsigned)(wgrad3_tiles(wgrad3_rows(a), a.Cin, a.Cout) + (a.want_bias ? a.Cout / 128 : 0));
   }
-  static bool attr_set = false;
-  size_t lds = (size_t)4 * 64 * WG_PITCH * sizeof(bf16_t);
-  if (!attr_set) {
-    RC_HIP(ctx, hipFuncSetAttribute((const void*)conv_mfma_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    attr_set = true;
-  }
-  a.m_chunk = ((a.M + nz - 1) / nz + 63) / 64 * 64;
-  int nzz = cdiv(a.M, a.m_chunk);
-  dim3 grid(a.KH * a.KW * (a.Cin / 128) * (a.Cout / 128), nzz);
-  static int wg_glds = -1;     // per-tap kernels: direct-to-LDS (default) or register-staged (RCGAN_WGRAD_IMPL=reg)
-  if (wg_glds < 0) { const char* e = getenv("RCGAN_WGRAD_IMPL"); wg_glds = (e && e[0] == 'r') ? 0 : 1; }
-  if (wg_glds == 1 && a.zero != nullptr) {
-    constexpr int NS = 4;
-    static bool attr2 = false;
-    size_t lds2 = (size_t)NS * 2 * 32 * 256;
-    if (!attr2) {
-      RC_HIP(ctx, hipFuncSetAttribute((const void*)conv_mfma_wgrad_glds_kernel<NS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-      attr2 = true;
-    }
-    ProfScope ps(ctx, RCGAN_PROF_WGRAD_MFMA, 2.0 * (double)a.M * a.KH * a.KW * a.Cin * a.Cout);
-    hipLaunchKernelGGL(conv_mfma_wgrad_glds_kernel<NS>, grid, dim3(256), lds2, ctx->stream, a);
-    *bias_done = a.want_bias != 0;
-  } else {
-    ProfScope ps(ctx, RCGAN_PROF_WGRAD_MFMA, 2.0 * (double)a.M * a.KH * a.KW * a.Cin * a.Cout);
-    hipLaunchKernelGGL(conv_mfma_wgrad_kernel, grid, dim3(256), lds, ctx->stream, a);
-  }
-  RC_LAUNCH_CHECK(ctx);
-  return nzz;
-}
-
-// the three-tap kernel's plan for one problem (also what mfma_wgrad_launch does): grid and pixel chunk, or false
-bool mfma_wgrad3_takes(const MfmaWgradArgs& a) {
-  return wgrad3_enabled() && a.use_tr && a.zero != nullptr && wgrad3_geom(a);
-}
-
-bool mfma_wgrad3_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy, long px_per_block) {
-  if (!(wgrad3_enabled() && a.use_tr && a.zero != nullptr && wgrad3_geom(a))) return false;
-  long tiles3 = (long)wgrad3_rows(a) * (a.Cin / 64) * (a.Cout / 128);
-  // pixel chunks: alone, enough of them for ~512 workgroups; in a group the caller fixes the pixels per workgroup for all
-  // layers (equal workgroup run times, and far fewer fp32 slabs to write and reduce than 512 workgroups per layer)
-  int want = px_per_block > 0 ? (int)wgrad_clamp_splits(cdiv(a.M, px_per_block), a.M)
-                              : (int)wgrad_clamp_splits((512 + tiles3 - 1) / tiles3, a.M);
-  if (want > nz) want = nz;
-  if (want < 1) want = 1;
   a.m_chunk = ((a.M + want - 1) / want + 63) / 64 * 64;
-  *gx = (unsigned)(tiles3 + (a.want_bias ? a.Cout / 128 : 0));
-  *gy = (unsigned)cdiv(a.M, a.m_chunk);
-  return true;
+  a.slab_stride = wgrad_slab_floats(a, 1);
+  p.gy = (unsigned)cdiv(a.M, a.m_chunk);
+}
+
+// One layer alone: choose, plan, check the planned slabs against the workspace, launch.  Returns the number of slabs written (a: as planned).
+int mfma_wgrad_launch(rcgan_ctx* ctx, MfmaWgradArgs& a, int nz, bool* bias_done, size_t ws_bytes) {
+  *bias_done = false;
+  WgradKernel k;
+  int rc = mfma_wgrad_choose(ctx, a, WGRAD9_BY_WORK, &k);
+  if (rc) return rc;
+  MfmaWgradPlanned p = {a, 0, 0};
+  mfma_wgrad_plan(p, k, nz, 0);
+  const auto fits = [&] { return (size_t)p.gy * (size_t)p.a.slab_stride * sizeof(float) <= ws_bytes; };
+  if (k == WK_NINE && !fits()) {       // (its upsample form carries two bias tails per slab: more than the stride the caller sized for)
+    rc = mfma_wgrad_choose(ctx, a, WGRAD9_OFF, &k);
+    if (rc) return rc;
+    mfma_wgrad_plan(p, k, nz, 0);
+  }
+  if (!fits()) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "planned slabs need %zu have %zu", (size_t)p.gy * p.a.slab_stride * sizeof(float), ws_bytes);
+  a = p.a;
+  const dim3 grid(p.gx, p.gy);
+  rc = k == WK_NINE ? mfma_wgrad9_group_launch(ctx, 1, &p)
+     : k == WK_THREE ? (a.relu_in ? launch_wgrad3<true>(ctx, a, grid) : launch_wgrad3<false>(ctx, a, grid))
+     : k == WK_TAP_GLDS ? launch_wgrad_tap<true>(ctx, a, grid) : launch_wgrad_tap<false>(ctx, a, grid);
+  *bias_done = a.want_bias != 0 && k != WK_TAP_REG;
+  return rc ? rc : (int)p.gy;
 }
 
 template <bool RELU>
@@ -2063,18 +2071,7 @@ static int launch_wgrad_glds_group(rcgan_ctx* ctx, const WgradGroup& g) {
   return RCGAN_OK;
 }
 
-// the per-tap kernel's plan for one problem inside a group (its own pixel chunking rule, as mfma_wgrad_launch)
-bool mfma_wgrad_tap_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy) {
-  static int wg_glds = -1;
-  if (wg_glds < 0) { const char* e = getenv("RCGAN_WGRAD_IMPL"); wg_glds = (e && e[0] == 'r') ? 0 : 1; }
-  if (!(wg_glds == 1 && a.zero != nullptr && a.Cin % 128 == 0 && a.Cout % 128 == 0)) return false;
-  a.m_chunk = ((a.M + nz - 1) / nz + 63) / 64 * 64;
-  *gx = (unsigned)(a.KH * a.KW * (a.Cin / 128) * (a.Cout / 128));
-  *gy = (unsigned)cdiv(a.M, a.m_chunk);
-  return true;
-}
-
-// probs[i] planned by mfma_wgrad3_plan (family 0; all with the same relu_in) or mfma_wgrad_tap_plan (family 1)
+// probs[i] planned (mfma_wgrad_plan) for the three-tap kernel (family 0; all with the same relu_in) or the per-tap direct-to-LDS kernel (family 1)
 // img (optional): image-end problems that ride in the FIRST launch
 int mfma_wgrad3_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs, int family, const ImgWGroup* img, bool carry_head) {
   static_assert(ImgWGeom<128>::LDS <= 4 * (40 * 128 + 32 * 256), "image-end body needs more LDS than the three-tap kernel");

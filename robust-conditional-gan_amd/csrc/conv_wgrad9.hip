@@ -393,23 +393,22 @@ bool mfma_wgrad9_takes(const MfmaWgradArgs& a) {
   return true;
 }
 
-// grid of one problem: tiles (x 2 row parities in the sub-pixel forms) x pixel chunks of ~px_per_block pixels (0: enough chunks for ~256
-// workgroups), at most nz chunks
-bool mfma_wgrad9_plan(MfmaWgradArgs& a, int nz, unsigned* gx, unsigned* gy, long px_per_block) {
-  if (!mfma_wgrad9_takes(a)) return false;
+// grid of one problem the kernel takes: tiles (x 2 row parities in the sub-pixel forms) x pixel chunks of ~px_per_block pixels (0: enough
+// chunks for ~WGRAD9_ALONE_WGS workgroups), at most nz chunks
+void mfma_wgrad9_plan(MfmaWgradPlanned& p, int nz, long px_per_block) {
+  MfmaWgradArgs& a = p.a;
   const long tiles = (long)(a.Cin / 64) * (a.Cout / 128) * (a.sub ? 2 : 1);
   const int ms32 = (a.sub ? 2 : 4) * 32;
-  long want = px_per_block > 0 ? cdiv(a.M, px_per_block) : (256 + tiles - 1) / tiles;
+  long want = px_per_block > 0 ? cdiv(a.M, px_per_block) : (WGRAD9_ALONE_WGS + tiles - 1) / tiles;
   const long maxs = a.M / 256 > 0 ? a.M / 256 : 1;
   if (want > maxs) want = maxs;
   if (want > nz) want = nz;
   if (want < 1) want = 1;
   a.m_chunk = ((a.M + want - 1) / want + ms32 - 1) / ms32 * ms32;
   // (upsample form: two bias partials per chunk, one per row parity; the slab reduction adds both -- SlabReduceGroup::Item::bias_parts)
-  a.slab_stride = (long)a.cells * a.Cin * a.Cout + (a.sub == 1 ? 2 : 1) * a.Cout;
-  *gx = (unsigned)tiles;
-  *gy = (unsigned)cdiv(a.M, a.m_chunk);
-  return true;
+  a.slab_stride = wgrad_slab_floats(a, a.sub == 1 ? 2 : 1);
+  p.gx = (unsigned)tiles;
+  p.gy = (unsigned)cdiv(a.M, a.m_chunk);
 }
 
 template <bool RELU, bool SUBK>
@@ -433,7 +432,7 @@ static int launch_wgrad9_group(rcgan_ctx* ctx, const Wgrad9Group& g) {
   return RCGAN_OK;
 }
 
-// probs[i] planned by mfma_wgrad9_plan, all with the same relu_in and all plain or all sub-pixel forms
+// probs[i] planned for this kernel, all with the same relu_in and all plain or all sub-pixel forms
 int mfma_wgrad9_group_launch(rcgan_ctx* ctx, int n, const MfmaWgradPlanned* probs) {
   for (int i0 = 0; i0 < n; i0 += WGRAD9_GROUP_MAX) {
     Wgrad9Group g;

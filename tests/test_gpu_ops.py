@@ -1474,7 +1474,8 @@ def test_grouped_filter_gradients_equal_single_calls():
     inside one kernel (plus one grouped slab reduction), with the pixels per workgroup chosen for the group as a whole, so
     the fp32 partial sums are cut differently (1e-6 relative) -- also for the 3 -> 128 image-end layers, whose workgroups ride
     in the grouped launch and whose slabs go through the grouped reduction; the 1x1 layer keeps its own pixel chunking and the
-    256 -> 3 layers their own launches: bit-identical."""
+    256 -> 3 layers their own launches: bit-identical.  So are the two 3x3 layers on 12- and 24-pixel-wide grids: the three-tap kernel
+    refuses them, the per-tap family's grouped launch (conv_mfma_wgrad_glds_group_kernel) keeps the single call's chunking rule."""
     import ctypes as C
     from rcgan_amd import _lib as L
     ctx = make_ctx("bf16")
@@ -1484,7 +1485,8 @@ def test_grouped_filter_gradients_equal_single_calls():
         shapes = [(128, 8, 8, 128, 128, 3, L.CONV_IN_RELU), (16, 16, 16, 128, 128, 3, L.CONV_IN_RELU), (6, 8, 8, 256, 128, 3, 0),
                   (4, 32, 32, 3, 128, 3, 0), (8, 8, 8, 128, 128, 1, 0), (3, 32, 32, 128, 256, 3, L.CONV_IN_RELU),
                   (5, 32, 32, 3, 128, 3, 0), (16, 16, 16, 3, 128, 1, 0), (7, 16, 16, 3, 128, 1, 0),      # image-end layers: ride in the group
-                  (2, 32, 32, 256, 3, 3, L.CONV_IN_RELU), (3, 32, 32, 256, 3, 3, 0)]                       # 256 -> 3: own launches
+                  (2, 32, 32, 256, 3, 3, L.CONV_IN_RELU), (3, 32, 32, 256, 3, 3, 0),                       # 256 -> 3: own launches
+                  (4, 12, 12, 128, 128, 3, 0), (2, 24, 24, 128, 256, 3, L.CONV_IN_RELU)]       # widths the three-tap kernel refuses: per-tap family
         items = []
         for i, (n, hh, ww, cin, cout, k, fl) in enumerate(shapes):
             x, dy = ctx.empty((n, hh, ww, cin)), ctx.empty((n, hh, ww, cout))
@@ -1506,12 +1508,16 @@ def test_grouped_filter_gradients_equal_single_calls():
         for i, (d, x, dy, dws, dbs) in enumerate(items):
             a, b = ctx.download(dws[0]), ctx.download(dws[1])
             assert np.abs(a).max() > 0
-            own = (d.kh != 3 and d.cin % 128 == 0) or d.cout == 3
+            own = (d.kh != 3 and d.cin % 128 == 0) or d.cout == 3 or (d.w & (d.w - 1)) != 0
+            print("layer %d: grouped - single max %.3e of %.3e" % (i, np.abs(a - b).max(), np.abs(a).max()))
             if own:
                 assert np.array_equal(a, b), "layer %d filter gradient" % i
             else:
                 assert_close(b, a, 2e-6, "layer %d filter gradient" % i)
             if dbs[0] is not None:
+                print("layer %d: bias, grouped - single max %.3e" % (i, np.abs(ctx.download(dbs[1]) - ctx.download(dbs[0])).max()))
+                if (d.w & (d.w - 1)) != 0:
+                    assert np.array_equal(ctx.download(dbs[1]), ctx.download(dbs[0])), "layer %d bias gradient" % i
                 assert_close(ctx.download(dbs[1]), ctx.download(dbs[0]), 2e-6, "layer %d bias gradient" % i)
     finally:
         ctx.close()
