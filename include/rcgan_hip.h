@@ -300,7 +300,9 @@ int rcgan_bn_stats(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, fl
 /* y = act( gamma[l]*(x-mean)*rstd + beta[l] ), l = labels[row / rows_per_sample] (labels NULL -> row 0
  * of a [1][c] table = plain batch norm).  Replaces tf.nn.batch_normalization + embedding_lookup
  * (cifar10/common/ops/normalization.py:47-57) and tf.contrib.layers.batch_norm (mnist/ops.py:38-44)
- * fused with the following relu / lrelu (gan_resnet.py:305,317,366; mnist/model.py:661-719). */
+ * fused with the following relu / lrelu (gan_resnet.py:305,317,366; mnist/model.py:661-719).
+ * Every batch-norm call returns RCGAN_EINVALID_ARG, before it launches anything, for a non-positive shape, n_labels outside
+ * 1 .. 1024, n_labels > 1 with labels NULL (rcgan_bn_fwd_segments with y = NULL included), or a NULL tensor it would touch. */
 int rcgan_bn_apply_fwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x,
                        const int32_t* labels, const float* gamma, const float* beta,
                        const float* mean, const float* rstd, int act, void* y, void* ws, size_t ws_bytes);

@@ -6,8 +6,7 @@
 // (per-row-group partials in fp32, combined in fp64) -- no atomics.
 #include "common.h"
 #include "conv_mfma.h"
-
-#define MAX_LABELS 16
+#include "bn_plan.h"
 
 // partial[g][0][c] = sum_rows v1, partial[g][1][c] = sum_rows v2 over row group g (rows_per_group rows)
 // MODE 0: (x, x*x)         MODE 1: (dy', dy'*xhat) with dy' = dy*act'(y), xhat = (x-mean)*rstd
@@ -577,12 +576,6 @@ __global__ __launch_bounds__(256) void bn_fused_reduce_kernel(BnFusedArgs a) {
 #undef LACC
 }
 
-// dynamic LDS of the kernel above
-static inline size_t bn_fused_lds(int mode, int n_labels) {
-  size_t red = 2 * 32 * 64 * sizeof(float), lacc = mode == 1 ? (size_t)n_labels * 2 * 4 * 64 * sizeof(float) : 0;
-  return red > lacc ? red : lacc;
-}
-
 // ------------------------------------------------------------------------------------------------
 // Tree variant of the fused reduction for LARGE tensors (>= a few MB).  The kernel above gives every workgroup a 64-channel
 // column block: 128 bytes out of every 512-byte (c = 256) row, with the other three quarters of the row read by workgroups
@@ -905,103 +898,6 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_fused_kernel(long nchunks, i
   }
 }
 
-// fused path: 64-channel column blocks, thread-fixed channel chunks in the apply kernels
-static inline bool bn_fused_ok(int c) {
-  return c >= 64 && c <= 2048 && (c & (c - 1)) == 0;      // power of two: chunks per row divide (or are) the block size
-}
-
-static inline int apply_grid_fused(long nchunks, int c) {
-  const int cpr = c / 8;
-  long b = (nchunks + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (cpr > 256) { long m = cpr / 256; b = (b + m - 1) / m * m; }   // stride (b*256) must be a multiple of cpr
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-static inline long stats_group_rows(long rows, int c = 0, int dtype = -1) {
-  long g = 512;
-  while (rows / g > 2048) g *= 2;
-  // fp32 path (MNIST: 64-channel critic layers of 1024 .. 25088 rows): 512 rows per workgroup are 128 dependent rounds of loads in 2 .. 49
-  // workgroups -- a latency chain of 17-20 us for a few hundred KB.  Shorter groups until ~256 workgroups exist (the finisher reads <= 256 partials)
-  if (dtype == RCGAN_F32 && c > 0)
-    while (g > 32 && (rows / g) * (c / 64 > 0 ? c / 64 : 1) < 256) g /= 2;
-  return g;
-}
-
-static inline int ew_grid2(long total) {
-  long b = (total + 255) / 256;
-  if (b > 8192) b = 8192;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
-// tree path (power-of-two channel counts; full rows per workgroup need c/8 <= 256 chunk lanes): OFF unless RCGAN_BN_TREE_MIN gives
-// an element threshold.  Measured (scripts/bench_bn.py, MI355X): the reductions are bound by their serial arrival chain
-// (write-through partials, drain, counter, finisher loads), not by the access pattern, and the tree has one hop more than the column
-// kernel.  While the column kernel's arrival counters shared one 128-byte line the tree won on the biggest tensor ([320,32,32,256]
-// bf16, 168 MB: statistics 37 vs 55 us); with one counter per line (RC_LINE_STRIDE) the column kernel is faster at every size
-// (that tensor: 36.2 vs 36.7 us, backward 202 vs 226 us; [128,16,16,256]: 6.6 vs 16 us).  The tests lower the threshold so the
-// path stays covered.
-static inline bool bn_tree_ok(long rows, int c) {
-  static long min_elems = -1;
-  if (min_elems < 0) {
-    const char* e = getenv("RCGAN_BN_TREE");
-    const char* m = getenv("RCGAN_BN_TREE_MIN");
-    min_elems = (e && atoi(e) == 0) ? (1L << 62) : (m ? atol(m) : (1L << 62));
-  }
-  return bn_fused_ok(c) && rows * (long)c >= min_elems;
-}
-
-// launch of the tree reduction.  ws layout: partial [nseg][ng][2c] | cpart [nseg][ncl][2c] | (backward) PQ [2c]
-template <int MODE>
-static int launch_bn_tree(rcgan_ctx* ctx, int dtype, BnFusedArgs& a, int nseg, int cs, void* ws, size_t ws_bytes, float** pq_out) {
-  const int c = a.c, ng = a.ngroups;
-  const int ncl = cdiv(ng, cs);
-  const size_t n_part = (size_t)nseg * ng * 2 * c, n_cp = (size_t)nseg * ncl * 2 * c;
-  const size_t need = (n_part + n_cp + 2 * (size_t)c) * sizeof(float);
-  if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-  RC_REQUIRE(ctx, (size_t)nseg * (ncl + 1) <= 8192, "too many clusters (%d x %d)", nseg, ncl);
-  RC_REQUIRE(ctx, (size_t)ng * 2 * c * 4 < (1ull << 31) && (size_t)ncl * 2 * c * 4 < (1ull << 31), "partials exceed a buffer descriptor");
-  BnTreeArgs ta;
-  a.partial = (float*)ws;
-  a.nseg = nseg;
-  ta.cpart = a.partial + n_part;
-  if (pq_out) { *pq_out = ta.cpart + n_cp; a.PQ = *pq_out; }
-  ta.counters = ctx->tree_line_counters();
-  ta.cs = cs; ta.nclusters = ncl;
-  ta.f = a;
-  const int Q = 2 * c / 4, SL = Q >= 256 ? 1 : 256 / Q;
-  size_t lds = 16384;                                             // [2][RL][c] floats = 4096 floats
-  if ((size_t)4 * c * sizeof(float) > lds) lds = (size_t)4 * c * sizeof(float);
-  if (MODE == 1 && a.labels) { const size_t l2 = (size_t)SL * a.n_labels * 2 * c * sizeof(float); if (l2 > lds) lds = l2; }
-  RC_REQUIRE(ctx, lds <= 128 * 1024, "tree reduction needs %zu bytes of LDS", lds);
-  if (dtype == RCGAN_F32) {
-    static size_t set = 0;
-    if (lds > set) { RC_HIP(ctx, hipFuncSetAttribute((const void*)bn_tree_reduce_kernel<float, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); set = lds; }
-    hipLaunchKernelGGL((bn_tree_reduce_kernel<float, MODE>), dim3(ng, nseg), dim3(256), lds, ctx->stream, ta);
-  } else if (dtype == RCGAN_H16) {
-    static size_t set = 0;
-    if (lds > set) { RC_HIP(ctx, hipFuncSetAttribute((const void*)bn_tree_reduce_kernel<bf16_t, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); set = lds; }
-    hipLaunchKernelGGL((bn_tree_reduce_kernel<bf16_t, MODE>), dim3(ng, nseg), dim3(256), lds, ctx->stream, ta);
-  } else {
-    RC_FAIL(ctx, RCGAN_EINVALID_ARG, "bad dtype %d", dtype);
-  }
-  RC_LAUNCH_CHECK(ctx);
-  return RCGAN_OK;
-}
-
-// rows per group of the tree path: ~512 workgroups, a multiple of the row lanes, at least 16 rows
-static inline long tree_group_rows(long rows, int c) {
-  const int RL = 256 / (c / 8) > 0 ? 256 / (c / 8) : 1;
-  static long target = -1;
-  if (target < 0) { const char* e = getenv("RCGAN_BN_TREE_GROUPS"); target = e ? atol(e) : 512; }
-  long rpg = cdiv(rows, target);
-  if (rpg < 16) rpg = 16;
-  rpg = (rpg + RL - 1) / RL * RL;
-  return rpg;
-}
-
 // mean / rstd of `nseg` segments from the per-tile column sums a convolution's epilogue left (conv_mfma8.hip): part[tile][c][2] =
 // (sum, sum of squares) over the tile's 256 pixels.  Segment s owns the tiles [g * group_stride + s * tps, + tps) of every group g
 // (one group, or the four phases of the sub-pixel form).  grid (c / 16, nseg) x 256 threads: 16 channels x 16 tile subsets, every
@@ -1057,7 +953,6 @@ int bn_tile_stats_finish_launch(rcgan_ctx* ctx, const float* part, int c, int ns
 //   3. the existing apply kernels (gamma[label] read per row, no K-sized table).
 // No atomics: every sum has a fixed order, so results are bit-reproducible (graph replay).
 // ------------------------------------------------------------------------------------------------
-#define BN_MAX_LABELS_WIDE 1024
 
 // block = 32 channel chunks (256 channels) x 8 row lanes; grid = (ceil(chunks / 32), n).  beta (optional): ReLU / leaky-ReLU
 // mask recomputed from x with the forward's arithmetic (as bn_fused_reduce_kernel), y is then not read.
@@ -1164,44 +1059,207 @@ __global__ __launch_bounds__(256) void bn_bwd_class_kernel(int n, int c, int n_l
   PQ[c + ch] = -p * mean[ch] - r * (float)d1 * invM;
 }
 
-// workspace: partial [n][2][c] | s12 [2][c] | PQ [2][c] floats
-static int bn_bwd_wide(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x, const void* y,
-                       const void* dy, const int32_t* labels, const float* gamma, const float* beta_m, const float* mean, const float* rstd,
-                       int act, void* dx, int accumulate_dx, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes) {
-  RC_REQUIRE(ctx, n >= 1 && rows_per_sample >= 1 && c >= 1, "bad shape n %d rows %d c %d", n, rows_per_sample, c);
-  RC_REQUIRE(ctx, dgamma && dbeta, "the conditional backward needs dgamma and dbeta");
-  const long rows = (long)n * rows_per_sample;
-  const size_t need = ((size_t)n * 2 * c + 4 * (size_t)c) * sizeof(float);
-  if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-  float* partial = (float*)ws;
-  float* s12 = partial + (size_t)n * 2 * c;
-  float* PQ = s12 + 2 * (size_t)c;
-  const bool fused = bn_fused_ok(c);
-  if (c % 8 == 0) {
-    const float* bm = fused ? beta_m : nullptr;        // the mask from x wherever the apply below also takes it
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_sample_partial_kernel<T>, dim3(cdiv(c / 8, 32), n), dim3(256), 0, ctx->stream,
-                                                     rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, bm, mean,
-                                                     rstd, act, partial));
+// ------------------------------------------------------------------------------------------------
+// Host side.  bn_plan.h decides (bn_choose) and sizes (bn_plan) every launch, and holds the table of routes; here are the argument
+// check, one launcher per kernel family and the entry points, each of which is: check, choose, plan, workspace check, launch.
+// ------------------------------------------------------------------------------------------------
+// the planner's limits against the counter layout of common.h (36864 / 102400: rcgan_ctx::line_counters / tree_line_counters)
+static_assert(RC_LCOUNTER_BN + BN_COLUMN_LINES == RC_LCOUNTER_BNSEG, "column blocks of one reduction = the lines in front of the segmented forward's");
+static_assert(36864 + (RC_LCOUNTER_BNSEG + BN_SEG_LINES) * RC_LINE_STRIDE * 4 <= 102400, "the segmented forward's lines end before the tree's");
+static_assert(102400 + BN_TREE_LINES * RC_LINE_STRIDE * 4 == RC_ZERO_PAGE_BYTES, "the tree's lines are the end of the zero page");
+
+// the tensors and scalars of one call; what a direction does not use stays zero
+struct BnCall {
+  const void *x, *y, *dy;                     // y: the forward's output as the backward reads it
+  void* out;                                  // y of the forward, dx of the backward
+  const int32_t* labels;
+  const float *gamma, *beta;                  // backward: beta only where the activation mask is recomputed from x
+  const float *mean_in, *rstd_in;             // statistics read (apply, backward)
+  float *mean, *rstd, *mm, *mv;               // statistics written
+  float eps, decay;
+  float *dgamma, *dbeta;
+  int act, accumulate, accumulate_dx;
+};
+
+// What every entry point refuses before it launches anything.  `tensors`: the ones the call reads or writes on every route.
+static int bn_check_args(rcgan_ctx* ctx, const BnShape& s, const int32_t* labels, std::initializer_list<const void*> tensors) {
+  RC_REQUIRE(ctx, s.nseg >= 1 && s.n >= 1 && s.rows_per_sample >= 1 && s.c >= 1, "bad shape: %d segments x %d samples x %d rows x %d channels",
+             s.nseg, s.n, s.rows_per_sample, s.c);
+  RC_REQUIRE(ctx, s.n_labels >= 1 && s.n_labels <= BN_MAX_LABELS_WIDE, "n_labels %d (1 .. %d)", s.n_labels, BN_MAX_LABELS_WIDE);
+  RC_REQUIRE(ctx, labels != nullptr || s.n_labels == 1, "labels required for n_labels > 1");
+  // a segment's rows are an int in the kernels' arguments, element offsets 64-bit
+  RC_REQUIRE(ctx, s.rows() <= INT32_MAX && s.nseg <= INT64_MAX / (s.rows() * s.c), "%d x %ld rows x %d channels exceed the index types", s.nseg,
+             s.rows(), s.c);
+  for (const void* t : tensors) RC_REQUIRE(ctx, t != nullptr, "null tensor");
+  return RCGAN_OK;
+}
+
+// ---- reduce: tree or column, statistics (MODE 0) or backward (MODE 1), nseg as the grid's last dimension ----
+static BnFusedArgs bn_fused_args(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, float* ws) {
+  BnFusedArgs a = {};
+  a.rows = s.rows(); a.c = s.c; a.rows_per_group = p.rows_per_group; a.ngroups = p.workgroups;
+  // (the kernels ask "nseg > 1": the tree is always told the count, the column kernel only by the segmented forward)
+  a.nseg = (p.route == BN_TREE || s.op == BN_OP_STATS_SEG) ? s.nseg : 0;
+  a.x = t.x; a.partial = ws + p.partial;
+  if (p.route == BN_COLUMN) a.counter = ctx->line_counters() + (s.op == BN_OP_STATS_SEG ? RC_LCOUNTER_BNSEG : RC_LCOUNTER_BN) * RC_LINE_STRIDE;
+  if (s.op != BN_OP_BWD) {
+    a.eps = t.eps; a.mean = t.mean; a.rstd = t.rstd; a.mm = t.mm; a.mv = t.mv; a.decay = t.decay;
+    return a;
+  }
+  a.y = t.y; a.dy = t.dy; a.mean_in = t.mean_in; a.rstd_in = t.rstd_in; a.act = t.act;
+  a.n_labels = s.n_labels; a.groups_per_sample = p.groups_per_sample; a.labels = t.labels; a.n_samples = s.n;
+  a.gamma = t.gamma; a.dgamma = t.dgamma; a.dbeta = t.dbeta; a.accumulate = t.accumulate;
+  // mask from x needs a group's rows to belong to one sample (conditional grouping) or no labels at all
+  a.beta = t.beta;
+  a.PQ = ws + p.PQ;
+  if (p.route == BN_COLUMN) a.nsub = p.nsub;
+  return a;
+}
+
+template <int MODE>
+static int launch_bn_tree(rcgan_ctx* ctx, int dtype, const BnFusedArgs& a, const BnPlan& p, int nseg, float* ws) {
+  const size_t c = a.c, lds = p.lds;
+  RC_REQUIRE(ctx, (size_t)nseg * (p.nclusters + 1) <= BN_TREE_LINES, "too many clusters (%d x %d)", nseg, p.nclusters);
+  RC_REQUIRE(ctx, (size_t)p.ngroups * 2 * c * 4 < (1ull << 31) && (size_t)p.nclusters * 2 * c * 4 < (1ull << 31), "partials exceed a buffer descriptor");
+  RC_REQUIRE(ctx, lds <= BN_TREE_MAX_LDS, "tree reduction needs %zu bytes of LDS", lds);
+  BnTreeArgs ta;
+  ta.f = a;
+  ta.cpart = ws + p.cpart;
+  ta.counters = ctx->tree_line_counters();
+  ta.cs = p.cluster_size; ta.nclusters = p.nclusters;
+  if (dtype == RCGAN_F32) {
+    static size_t set = 0;
+    if (lds > set) { RC_HIP(ctx, hipFuncSetAttribute((const void*)bn_tree_reduce_kernel<float, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); set = lds; }
+    hipLaunchKernelGGL((bn_tree_reduce_kernel<float, MODE>), dim3(p.grid_x, p.grid_y), dim3(256), lds, ctx->stream, ta);
+  } else if (dtype == RCGAN_H16) {
+    static size_t set = 0;
+    if (lds > set) { RC_HIP(ctx, hipFuncSetAttribute((const void*)bn_tree_reduce_kernel<bf16_t, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); set = lds; }
+    hipLaunchKernelGGL((bn_tree_reduce_kernel<bf16_t, MODE>), dim3(p.grid_x, p.grid_y), dim3(256), lds, ctx->stream, ta);
   } else {
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_partial_kernel<T, 1>), dim3(cdiv(c, 64), n), dim3(256), 0, ctx->stream, rows, c,
-                                                     (long)rows_per_sample, (const T*)x, (const T*)y, (const T*)dy, mean, rstd, act, partial));
+    RC_FAIL(ctx, RCGAN_EINVALID_ARG, "bad dtype %d", dtype);
   }
   RC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(bn_bwd_class_kernel, dim3(cdiv(c, 256), n_labels + 1), dim3(256), 0, ctx->stream, n, c, n_labels, rows, labels, gamma,
-                     (const float*)partial, mean, rstd, dgamma, dbeta, accumulate, s12, PQ);
+  return RCGAN_OK;
+}
+
+template <int MODE>
+static int bn_launch_reduce(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, float* ws) {
+  const BnFusedArgs a = bn_fused_args(ctx, s, p, t, ws);
+  if (p.route == BN_TREE) return launch_bn_tree<MODE>(ctx, s.dtype, a, p, s.nseg, ws);
+  RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL((bn_fused_reduce_kernel<T, MODE>), dim3(p.grid_x, p.grid_y, s.nseg), dim3(256), p.lds, ctx->stream, a));
   RC_LAUNCH_CHECK(ctx);
-  if (fused) {
-    const long nchunks = rows * c / 8;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<T>, dim3(apply_grid_fused(nchunks, c)), dim3(256), 0, ctx->stream,
-                                                     nchunks, rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, rstd,
-                                                     (const float*)PQ, act, (T*)dx, accumulate_dx, beta_m, mean));
+  return RCGAN_OK;
+}
+
+// ---- partial + finish: vec or scalar partials per row group, then the statistics / the per-label sums; the wide backward's
+// per-sample partials and class kernel ----
+template <int MODE>
+static int bn_launch_partial(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, float* partial) {
+  const dim3 grid(p.grid_x, p.grid_y);
+  const long rows = s.rows();
+  if (p.route == BN_WIDE && p.partial_vec) {
+    const float* bm = p.apply == BN_COLUMN ? t.beta : nullptr;        // the mask from x wherever the apply also takes it
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_sample_partial_kernel<T>, grid, dim3(256), 0, ctx->stream, s.rows_per_sample, s.c,
+                                                       (const T*)t.x, (const T*)t.y, (const T*)t.dy, t.labels, t.gamma, bm, t.mean_in, t.rstd_in,
+                                                       t.act, partial));
+  } else if (p.partial_vec) {
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL((bn_partial_vec_kernel<T, MODE>), grid, dim3(256), 0, ctx->stream, rows, s.c, p.rows_per_group,
+                                                       (const T*)t.x, (const T*)t.y, (const T*)t.dy, t.mean_in, t.rstd_in, t.act, partial));
   } else {
-    const long total = rows * c;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_grid2(total)), dim3(256), 0, ctx->stream, total, rows,
-                                                     rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, mean,
-                                                     rstd, (const float*)s12, act, (T*)dx, accumulate_dx));
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL((bn_partial_kernel<T, MODE>), grid, dim3(256), 0, ctx->stream, rows, s.c, p.rows_per_group,
+                                                       (const T*)t.x, (const T*)t.y, (const T*)t.dy, t.mean_in, t.rstd_in, t.act, partial));
   }
   RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+static int bn_launch_partial_finish(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, float* ws) {
+  float* partial = ws + p.partial;
+  const int c = s.c;
+  if (int rc = s.op == BN_OP_BWD ? bn_launch_partial<1>(ctx, s, p, t, partial) : bn_launch_partial<0>(ctx, s, p, t, partial)) return rc;
+  if (s.op != BN_OP_BWD)
+    hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(cdiv(c, 256)), dim3(256), 0, ctx->stream, c, p.ngroups, s.rows(), (const float*)partial, t.eps,
+                       t.mean, t.rstd, t.mm, t.mv, t.decay);
+  else if (p.route == BN_WIDE)
+    hipLaunchKernelGGL(bn_bwd_class_kernel, dim3(cdiv(c, 256), s.n_labels + 1), dim3(256), 0, ctx->stream, s.n, c, s.n_labels, s.rows(), t.labels,
+                       t.gamma, (const float*)partial, t.mean_in, t.rstd_in, t.dgamma, t.dbeta, t.accumulate, ws + p.s12, ws + p.PQ);
+  else
+    hipLaunchKernelGGL(bn_bwd_combine_kernel, dim3(cdiv(c, 128)), dim3(128), 0, ctx->stream, c, p.ngroups, s.n_labels, t.labels, t.gamma,
+                       (const float*)partial, t.dgamma, t.dbeta, ws + p.s12, t.accumulate);
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+// workspace check, then the reduction the plan names
+static int bn_reduce(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, void* ws) {
+  if (s.ws_bytes < p.need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", p.need, s.ws_bytes);
+  if (p.route != BN_TREE && p.route != BN_COLUMN) return bn_launch_partial_finish(ctx, s, p, t, (float*)ws);
+  return s.op == BN_OP_BWD ? bn_launch_reduce<1>(ctx, s, p, t, (float*)ws) : bn_launch_reduce<0>(ctx, s, p, t, (float*)ws);
+}
+
+// ---- forward apply: fused (nseg segments in one launch), vec with tables, or scalar ----
+static int bn_launch_apply_fwd(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, float* ws) {
+  const int rps = s.rows_per_sample, c = s.c;
+  if (p.apply == BN_COLUMN) {
+    const int seg_samples = s.op == BN_OP_APPLY ? 0 : s.n;            // samples per segment; 0: the call has no segments
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_apply_fused_kernel<T>, dim3(p.apply_grid, s.nseg), dim3(256), 0, ctx->stream, p.apply_items,
+                                                       rps, c, (const T*)t.x, t.labels, t.gamma, t.beta, t.mean_in, t.rstd_in, t.act, (T*)t.out,
+                                                       seg_samples));
+  } else if (p.apply == BN_VEC) {
+    float *A = ws + p.A, *B = ws + p.B;
+    hipLaunchKernelGGL(bn_table_fwd_kernel, dim3(cdiv((long)s.n_labels * c, 256)), dim3(256), 0, ctx->stream, s.n_labels, c, t.gamma, t.beta,
+                       t.mean_in, t.rstd_in, A, B);
+    RC_LAUNCH_CHECK(ctx);
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_apply_vec_kernel<T>, dim3(p.apply_grid), dim3(256), 0, ctx->stream, p.apply_items, rps, c,
+                                                       (const T*)t.x, t.labels, (const float*)A, (const float*)B, t.act, (T*)t.out));
+  } else {
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_apply_fwd_kernel<T>, dim3(p.apply_grid), dim3(256), 0, ctx->stream, p.apply_items, rps, c,
+                                                       (const T*)t.x, t.labels, t.gamma, t.beta, t.mean_in, t.rstd_in, t.act, (T*)t.out));
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+// ---- backward apply: fused (dx constants PQ), vec with tables, or scalar (batch sums s12) ----
+static int bn_launch_apply_bwd(rcgan_ctx* ctx, const BnShape& s, const BnPlan& p, const BnCall& t, float* ws) {
+  const int rps = s.rows_per_sample, c = s.c;
+  const long rows = s.rows();
+  if (p.apply == BN_COLUMN) {
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<T>, dim3(p.apply_grid), dim3(256), 0, ctx->stream, p.apply_items, rps, c,
+                                                       (const T*)t.x, (const T*)t.y, (const T*)t.dy, t.labels, t.gamma, t.rstd_in,
+                                                       (const float*)(ws + p.PQ), t.act, (T*)t.out, t.accumulate_dx, t.beta, t.mean_in));
+  } else if (p.apply == BN_VEC) {
+    float *A = ws + p.A, *PQ = ws + p.PQ;
+    hipLaunchKernelGGL(bn_table_bwd_kernel, dim3(cdiv((long)s.n_labels * c, 256)), dim3(256), 0, ctx->stream, s.n_labels, c, rows, t.gamma, t.mean_in,
+                       t.rstd_in, (const float*)(ws + p.s12), A, PQ);
+    RC_LAUNCH_CHECK(ctx);
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<T>, dim3(p.apply_grid), dim3(256), 0, ctx->stream, p.apply_items, rps, c,
+                                                       (const T*)t.x, (const T*)t.y, (const T*)t.dy, t.labels, (const float*)A, (const float*)PQ,
+                                                       t.act, (T*)t.out, t.accumulate_dx));
+  } else {
+    RC_DISPATCH_DTYPE(ctx, s.dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(p.apply_grid), dim3(256), 0, ctx->stream, p.apply_items, rows, rps, c,
+                                                       (const T*)t.x, (const T*)t.y, (const T*)t.dy, t.labels, t.gamma, t.mean_in, t.rstd_in,
+                                                       (const float*)(ws + p.s12), t.act, (T*)t.out, t.accumulate_dx));
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+// The segmented calls' fallback: one segment at a time through the one-segment entry points, which choose their own route --
+// statistics (rcgan_bn_fwd_segments) and, where the call has an output, the apply.
+static int bn_each_segment(rcgan_ctx* ctx, bool with_stats, const BnShape& s, const BnCall& t, void* ws) {
+  const long rows = s.rows();
+  const size_t seg_bytes = (size_t)rows * s.c * dtype_size(s.dtype);
+  for (int sg = 0; sg < s.nseg; ++sg) {
+    const char* xs = (const char*)t.x + sg * seg_bytes;
+    const size_t so = (size_t)sg * s.c;
+    if (with_stats)
+      if (int rc = rcgan_bn_stats(ctx, (int)rows, s.c, s.dtype, xs, t.eps, t.mean + so, t.rstd + so, nullptr, nullptr, 0.f, ws, s.ws_bytes)) return rc;
+    if (!t.out) continue;
+    if (int rc = rcgan_bn_apply_fwd(ctx, s.n, s.rows_per_sample, s.c, s.n_labels, s.dtype, xs, t.labels ? t.labels + (size_t)sg * s.n : nullptr, t.gamma,
+                                    t.beta, t.mean_in + so, t.rstd_in + so, t.act, (char*)t.out + sg * seg_bytes, ws, s.ws_bytes))
+      return rc;
+  }
   return RCGAN_OK;
 }
 
@@ -1224,70 +1282,28 @@ size_t rcgan_bn_workspace_bytes_labels(int rows, int c, int n_labels) {
 
 int rcgan_bn_stats(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, float eps, float* mean, float* rstd,
                    float* mm, float* mv, float decay, void* ws, size_t ws_bytes) {
-  long rpg = stats_group_rows(rows, c, dtype);
-  int ng = cdiv(rows, rpg);
-  size_t need = (size_t)ng * 2 * c * sizeof(float);
-  if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-  float* partial = (float*)ws;
-  if (bn_tree_ok(rows, c)) {
-    BnFusedArgs a = {};
-    a.rows = rows; a.c = c; a.rows_per_group = tree_group_rows(rows, c); a.ngroups = (int)cdiv((long)rows, a.rows_per_group); a.x = x;
-    a.eps = eps; a.mean = mean; a.rstd = rstd; a.mm = mm; a.mv = mv; a.decay = decay;
-    return launch_bn_tree<0>(ctx, dtype, a, 1, 16, ws, ws_bytes, nullptr);
+  const BnShape s = {BN_OP_STATS, 1, 1, rows, c, 1, false, dtype, ws_bytes};
+  BnCall t = {};
+  t.x = x; t.eps = eps; t.mean = mean; t.rstd = rstd; t.mm = mm; t.mv = mv; t.decay = decay;
+  if (int rc = bn_check_args(ctx, s, nullptr, {x, mean, rstd})) return rc;
+  const BnRoute route = bn_choose(s).route;
+  // kept as it was: a call the tree takes must also hold what the column route would need (checked first)
+  if (route == BN_TREE) {
+    const size_t need = bn_plan(s, BN_COLUMN).need;
+    if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
   }
-  if (bn_fused_ok(c)) {
-    BnFusedArgs a = {};
-    a.rows = rows; a.c = c; a.rows_per_group = rpg; a.ngroups = ng; a.x = x; a.partial = partial;
-    a.counter = ctx->line_counters() + RC_LCOUNTER_BN * RC_LINE_STRIDE;
-    a.eps = eps; a.mean = mean; a.rstd = rstd; a.mm = mm; a.mv = mv; a.decay = decay;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_fused_reduce_kernel<T, 0>), dim3(c / 64, ng), dim3(256), bn_fused_lds(0, 0), ctx->stream, a));
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  if (c % 8 == 0) {
-    dim3 grid(cdiv(c / 8, 32), ng);
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_partial_vec_kernel<T, 0>), grid, dim3(256), 0, ctx->stream, (long)rows, c, rpg,
-                                                     (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr,
-                                                     (const float*)nullptr, 0, partial));
-  } else {
-    dim3 grid(cdiv(c, 64), ng);
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_partial_kernel<T, 0>), grid, dim3(256), 0, ctx->stream, (long)rows, c, rpg,
-                                                     (const T*)x, (const T*)nullptr, (const T*)nullptr, (const float*)nullptr,
-                                                     (const float*)nullptr, 0, partial));
-  }
-  RC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(cdiv(c, 256)), dim3(256), 0, ctx->stream, c, ng, (long)rows,
-                     (const float*)partial, eps, mean, rstd, mm, mv, decay);
-  RC_LAUNCH_CHECK(ctx);
-  return RCGAN_OK;
+  return bn_reduce(ctx, s, bn_plan(s, route), t, ws);
 }
 
 int rcgan_bn_apply_fwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x,
                        const int32_t* labels, const float* gamma, const float* beta, const float* mean, const float* rstd,
                        int act, void* y, void* ws, size_t ws_bytes) {
-  long total = (long)n * rows_per_sample * c;
-  if (bn_fused_ok(c)) {
-    long nchunks = total / 8;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_apply_fused_kernel<T>, dim3(apply_grid_fused(nchunks, c)), dim3(256), 0, ctx->stream,
-                                                     nchunks, rows_per_sample, c, (const T*)x, labels, gamma, beta, mean, rstd, act, (T*)y, 0));
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  if (c % 8 == 0 && ws_bytes >= (size_t)2 * n_labels * c * sizeof(float)) {
-    float* A = (float*)ws;
-    float* B = A + (size_t)n_labels * c;
-    hipLaunchKernelGGL(bn_table_fwd_kernel, dim3(cdiv((long)n_labels * c, 256)), dim3(256), 0, ctx->stream, n_labels, c, gamma, beta, mean, rstd, A, B);
-    RC_LAUNCH_CHECK(ctx);
-    long nchunks = total / 8;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_apply_vec_kernel<T>, dim3(ew_grid2(nchunks)), dim3(256), 0, ctx->stream, nchunks,
-                                                     rows_per_sample, c, (const T*)x, labels, (const float*)A, (const float*)B, act, (T*)y));
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_apply_fwd_kernel<T>, dim3(ew_grid2(total)), dim3(256), 0, ctx->stream, total,
-                                                   rows_per_sample, c, (const T*)x, labels, gamma, beta, mean, rstd, act, (T*)y));
-  RC_LAUNCH_CHECK(ctx);
-  return RCGAN_OK;
+  const BnShape s = {BN_OP_APPLY, 1, n, rows_per_sample, c, n_labels, labels != nullptr, dtype, ws_bytes};
+  BnCall t = {};
+  t.x = x; t.out = y; t.labels = labels; t.gamma = gamma; t.beta = beta; t.mean_in = mean; t.rstd_in = rstd; t.act = act;
+  if (int rc = bn_check_args(ctx, s, labels, {x, gamma, beta, mean, rstd, y})) return rc;
+  // (no workspace check: bn_choose takes the table route only where ws_bytes holds the tables)
+  return bn_launch_apply_fwd(ctx, s, bn_plan(s, bn_choose(s).route), t, (float*)ws);
 }
 
 // Forward batch norm of `nseg` independent segments of n_per_seg samples each (x = the segments back to back): every
@@ -1296,72 +1312,30 @@ int rcgan_bn_apply_fwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_
 int rcgan_bn_fwd_segments(rcgan_ctx* ctx, int nseg, int n_per_seg, int rows_per_sample, int c, int n_labels, int dtype, const void* x,
                           const int32_t* labels, const float* gamma, const float* beta, float eps, int act,
                           float* mean, float* rstd, void* y, void* ws, size_t ws_bytes) {
-  RC_REQUIRE(ctx, nseg >= 1 && n_per_seg >= 1, "segments %d x %d", nseg, n_per_seg);
-  const long rows = (long)n_per_seg * rows_per_sample;
-  if (!bn_fused_ok(c) || nseg * (c / 64) > 256) {       // other channel counts: one segment at a time
-    const size_t esz = dtype_size(dtype);
-    for (int sg = 0; sg < nseg; ++sg) {
-      const char* xs = (const char*)x + (size_t)sg * rows * c * esz;
-      char* ys = (char*)y + (size_t)sg * rows * c * esz;
-      int rc = rcgan_bn_stats(ctx, (int)rows, c, dtype, xs, eps, mean + (size_t)sg * c, rstd + (size_t)sg * c, nullptr, nullptr, 0.f, ws, ws_bytes);
-      if (rc) return rc;
-      if (!y) continue;
-      rc = rcgan_bn_apply_fwd(ctx, n_per_seg, rows_per_sample, c, n_labels, dtype, xs, labels ? labels + (size_t)sg * n_per_seg : nullptr,
-                              gamma, beta, mean + (size_t)sg * c, rstd + (size_t)sg * c, act, ys, ws, ws_bytes);
-      if (rc) return rc;
-    }
-    return RCGAN_OK;
-  }
-  if (bn_tree_ok(rows, c)) {
-    BnFusedArgs a = {};
-    a.rows = rows; a.c = c; a.rows_per_group = tree_group_rows(rows, c); a.ngroups = (int)cdiv(rows, a.rows_per_group); a.x = x;
-    a.eps = eps; a.mean = mean; a.rstd = rstd; a.mm = nullptr; a.mv = nullptr; a.decay = 0.f;
-    int rc = launch_bn_tree<0>(ctx, dtype, a, nseg, 16, ws, ws_bytes, nullptr);
-    if (rc) return rc;
-  } else {
-    const long rpg = stats_group_rows(rows);
-    const int ng = cdiv(rows, rpg);
-    const size_t need = (size_t)nseg * ng * 2 * c * sizeof(float);
-    if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-    BnFusedArgs a = {};
-    a.rows = rows; a.c = c; a.rows_per_group = rpg; a.ngroups = ng; a.nseg = nseg; a.x = x; a.partial = (float*)ws;
-    a.counter = ctx->line_counters() + RC_LCOUNTER_BNSEG * RC_LINE_STRIDE;
-    a.eps = eps; a.mean = mean; a.rstd = rstd; a.mm = nullptr; a.mv = nullptr; a.decay = 0.f;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_fused_reduce_kernel<T, 0>), dim3(c / 64, ng, nseg), dim3(256), bn_fused_lds(0, 0), ctx->stream, a));
-    RC_LAUNCH_CHECK(ctx);
-  }
+  const BnShape s = {BN_OP_STATS_SEG, nseg, n_per_seg, rows_per_sample, c, n_labels, labels != nullptr, dtype, ws_bytes};
+  BnCall t = {};
+  t.x = x; t.out = y; t.labels = labels; t.gamma = gamma; t.beta = beta; t.act = act;
+  t.eps = eps; t.mean = mean; t.rstd = rstd; t.mean_in = mean; t.rstd_in = rstd;
+  if (int rc = bn_check_args(ctx, s, labels, {x, mean, rstd})) return rc;
+  RC_REQUIRE(ctx, !y || (gamma && beta), "null gamma / beta");
+  const BnChoice ch = bn_choose(s);
+  if (ch.per_segment) return bn_each_segment(ctx, true, s, t, ws);
+  const BnPlan p = bn_plan(s, ch.route);
+  if (int rc = bn_reduce(ctx, s, p, t, ws)) return rc;
   if (!y) return RCGAN_OK;             // statistics only: the consumer normalises on load (rcgan_conv2d_fwd_bn)
-  const long nchunks = rows * c / 8;
-  int gx = apply_grid_fused(nchunks, c);
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_apply_fused_kernel<T>, dim3(gx, nseg), dim3(256), 0, ctx->stream,
-                                                   nchunks, rows_per_sample, c, (const T*)x, labels, gamma, beta, (const float*)mean, (const float*)rstd,
-                                                   act, (T*)y, n_per_seg));
-  RC_LAUNCH_CHECK(ctx);
-  return RCGAN_OK;
+  return bn_launch_apply_fwd(ctx, s, p, t, (float*)ws);
 }
 
 int rcgan_bn_apply_segments(rcgan_ctx* ctx, int nseg, int n_per_seg, int rows_per_sample, int c, int n_labels, int dtype, const void* x,
                             const int32_t* labels, const float* gamma, const float* beta, const float* mean, const float* rstd, int act,
                             void* y, void* ws, size_t ws_bytes) {
-  RC_REQUIRE(ctx, nseg >= 1 && n_per_seg >= 1, "segments %d x %d", nseg, n_per_seg);
-  if (nseg == 1) return rcgan_bn_apply_fwd(ctx, n_per_seg, rows_per_sample, c, n_labels, dtype, x, labels, gamma, beta, mean, rstd, act, y, ws, ws_bytes);
-  if (!bn_fused_ok(c)) {           // channel counts the fused kernel does not take: segment by segment, as rcgan_bn_fwd_segments does
-    const size_t seg_elems = (size_t)n_per_seg * rows_per_sample * c;
-    for (int sg = 0; sg < nseg; ++sg) {
-      int rc = rcgan_bn_apply_fwd(ctx, n_per_seg, rows_per_sample, c, n_labels, dtype, (const char*)x + sg * seg_elems * dtype_size(dtype),
-                                  labels ? labels + (size_t)sg * n_per_seg : nullptr, gamma, beta, mean + (size_t)sg * c, rstd + (size_t)sg * c,
-                                  act, (char*)y + sg * seg_elems * dtype_size(dtype), ws, ws_bytes);
-      if (rc != RCGAN_OK) return rc;
-    }
-    return RCGAN_OK;
-  }
-  const long rows = (long)n_per_seg * rows_per_sample;
-  const long nchunks = rows * c / 8;
-  const int gx = apply_grid_fused(nchunks, c);
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_apply_fused_kernel<T>, dim3(gx, nseg), dim3(256), 0, ctx->stream,
-                                                   nchunks, rows_per_sample, c, (const T*)x, labels, gamma, beta, mean, rstd, act, (T*)y, n_per_seg));
-  RC_LAUNCH_CHECK(ctx);
-  return RCGAN_OK;
+  const BnShape s = {BN_OP_APPLY_SEG, nseg, n_per_seg, rows_per_sample, c, n_labels, labels != nullptr, dtype, ws_bytes};
+  BnCall t = {};
+  t.x = x; t.out = y; t.labels = labels; t.gamma = gamma; t.beta = beta; t.mean_in = mean; t.rstd_in = rstd; t.act = act;
+  if (int rc = bn_check_args(ctx, s, labels, {x, gamma, beta, mean, rstd, y})) return rc;
+  const BnChoice ch = bn_choose(s);
+  if (ch.per_segment) return bn_each_segment(ctx, false, s, t, ws);
+  return bn_launch_apply_fwd(ctx, s, bn_plan(s, ch.route), t, (float*)ws);
 }
 
 int rcgan_bn_bwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x, const void* y,
@@ -1374,130 +1348,23 @@ int rcgan_bn_bwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels
 int rcgan_bn_bwd2(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x, const void* y,
                   const void* dy, const int32_t* labels, const float* gamma, const float* beta, const float* mean, const float* rstd,
                   int act, void* dx, int accumulate_dx, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes) {
+  const BnShape s = {BN_OP_BWD, 1, n, rows_per_sample, c, n_labels, labels != nullptr, dtype, ws_bytes};
+  BnCall t = {};
+  t.x = x; t.y = y; t.dy = dy; t.out = dx; t.labels = labels; t.gamma = gamma; t.mean_in = mean; t.rstd_in = rstd; t.act = act;
+  t.dgamma = dgamma; t.dbeta = dbeta; t.accumulate = accumulate; t.accumulate_dx = accumulate_dx;
   // with beta, ReLU / leaky ReLU masks are recomputed from x on the fused paths (two instead of three tensor reads per pass)
-  const float* beta_m = (beta && (act == RCGAN_ACT_RELU || act == RCGAN_ACT_LRELU)) ? beta : nullptr;
-  RC_REQUIRE(ctx, n_labels >= 1 && n_labels <= BN_MAX_LABELS_WIDE, "n_labels %d (1 .. %d)", n_labels, BN_MAX_LABELS_WIDE);
-  RC_REQUIRE(ctx, labels != nullptr || n_labels == 1, "labels required for n_labels > 1");
-  if (n_labels > MAX_LABELS)
-    return bn_bwd_wide(ctx, n, rows_per_sample, c, n_labels, dtype, x, y, dy, labels, gamma, beta_m, mean, rstd, act, dx, accumulate_dx,
-                       dgamma, dbeta, accumulate, ws, ws_bytes);
-  long rows = (long)n * rows_per_sample;
-  long rpg;
-  int ng;
-  if (bn_tree_ok(rows, c) && !(labels && (size_t)n_labels * 2 * c * sizeof(float) > 96 * 1024) && (!labels || n <= 8000)) {
-    // tree path: full rows per workgroup; with labels a cluster is exactly one sample (gps groups)
-    BnFusedArgs a = {};
-    int cs = 16;
-    if (labels) {
-      const int RL = 256 / (c / 8) > 0 ? 256 / (c / 8) : 1;
-      int gps = 1;
-      rpg = rows_per_sample;
-      static long target = -1;
-      if (target < 0) { const char* e = getenv("RCGAN_BN_TREE_GROUPS"); target = e ? atol(e) : 512; }
-      while ((long)n * gps < target && rpg % 2 == 0 && rpg / 2 >= 16 && (rpg / 2) % RL == 0 && gps < 16) { gps *= 2; rpg /= 2; }
-      ng = n * gps; cs = gps;
-    } else {
-      rpg = tree_group_rows(rows, c); ng = (int)cdiv(rows, rpg);
-    }
-    a.rows = rows; a.c = c; a.rows_per_group = rpg; a.ngroups = ng; a.x = x; a.y = y; a.dy = dy;
-    a.mean_in = mean; a.rstd_in = rstd; a.act = act;
-    a.n_labels = n_labels; a.groups_per_sample = cs; a.labels = labels; a.n_samples = n;
-    a.gamma = gamma; a.dgamma = dgamma; a.dbeta = dbeta; a.accumulate = accumulate; a.beta = beta_m;
-    float* PQ = nullptr;
-    int rc = launch_bn_tree<1>(ctx, dtype, a, 1, cs, ws, ws_bytes, &PQ);
-    if (rc) return rc;
-    long nchunks = rows * c / 8;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<T>, dim3(apply_grid_fused(nchunks, c)), dim3(256), 0, ctx->stream,
-                                                     nchunks, rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, rstd,
-                                                     (const float*)PQ, act, (T*)dx, accumulate_dx, beta_m, mean));
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  if (bn_fused_ok(c)) {
-    int gps = 1, nsub = 1;
-    if (labels) {
-      // groups never straddle samples; split each sample until the grid has enough workgroups (six fit on a CU); samples of
-      // fewer than 32 rows (the 4x4 stage) go nsub to a workgroup, which still writes one partial row per sample
-      static long target = -1, maxg = -1;
-      if (target < 0) {
-        // (round 3, same box: 512 / 512 -> 5.827 ms per iteration, 1024 / 1024 -> 5.801, 2048 / 2048 -> 5.815: the 32 x 32 layers gain from more
-        // workgroups, the 8 x 8 / 16 x 16 ones lose to the longer finisher)
-        const char* e = getenv("RCGAN_BN_BWD_WGS"); target = e ? atol(e) : 1024;
-        const char* m = getenv("RCGAN_BN_BWD_MAXG"); maxg = m ? atol(m) : 1024;
-      }
-      rpg = rows_per_sample;
-      if (rows_per_sample < 32 && 32 % rows_per_sample == 0 && n % (32 / rows_per_sample) == 0) { nsub = 32 / rows_per_sample; rpg = 32; }
-      else while ((long)n * gps * (c / 64) < target && rpg % 2 == 0 && rpg / 2 >= 32 && (long)n * gps * 2 <= maxg) { gps *= 2; rpg /= 2; }
-      ng = n * gps;
-    } else {
-      rpg = stats_group_rows(rows, c, dtype); ng = cdiv(rows, rpg);
-    }
-    const int nwg = ng / nsub;
-    size_t need = ((size_t)ng * 2 * c + 2 * (size_t)c) * sizeof(float);
-    if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-    BnFusedArgs a = {};
-    a.rows = rows; a.c = c; a.rows_per_group = rpg; a.ngroups = ng; a.x = x; a.y = y; a.dy = dy;
-    a.mean_in = mean; a.rstd_in = rstd; a.act = act; a.partial = (float*)ws; a.counter = ctx->line_counters() + RC_LCOUNTER_BN * RC_LINE_STRIDE;
-    a.ngroups = nwg; a.nsub = nsub;
-    a.n_labels = n_labels; a.groups_per_sample = gps; a.labels = labels; a.n_samples = n;
-    a.gamma = gamma; a.dgamma = dgamma; a.dbeta = dbeta; a.accumulate = accumulate;
-    // mask from x needs a group's rows to belong to one sample (conditional grouping) or no labels at all
-    a.beta = beta_m;
-    a.PQ = a.partial + (size_t)ng * 2 * c;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_fused_reduce_kernel<T, 1>), dim3(c / 64, nwg), dim3(256), bn_fused_lds(1, labels ? n_labels : 0), ctx->stream, a));
-    RC_LAUNCH_CHECK(ctx);
-    long nchunks = rows * c / 8;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_fused_kernel<T>, dim3(apply_grid_fused(nchunks, c)), dim3(256), 0, ctx->stream,
-                                                     nchunks, rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, rstd,
-                                                     (const float*)a.PQ, act, (T*)dx, accumulate_dx, beta_m, mean));
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  if (labels) { rpg = rows_per_sample; ng = n; }          // one group per sample: group label = sample label
-  else { rpg = stats_group_rows(rows, c, dtype); ng = cdiv(rows, rpg); }
-  size_t need = ((size_t)ng * 2 * c + 2 * (size_t)c) * sizeof(float);
-  if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-  float* partial = (float*)ws;
-  float* s12 = partial + (size_t)ng * 2 * c;
-  const bool vec = c % 8 == 0 && ws_bytes >= need + ((size_t)n_labels * c + 2 * (size_t)c) * sizeof(float);
-  if (vec) {
-    dim3 grid(cdiv(c / 8, 32), ng);
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_partial_vec_kernel<T, 1>), grid, dim3(256), 0, ctx->stream, rows, c, rpg,
-                                                     (const T*)x, (const T*)y, (const T*)dy, mean, rstd, act, partial));
-  } else {
-    dim3 grid(cdiv(c, 64), ng);
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((bn_partial_kernel<T, 1>), grid, dim3(256), 0, ctx->stream, rows, c, rpg,
-                                                     (const T*)x, (const T*)y, (const T*)dy, mean, rstd, act, partial));
-  }
-  RC_LAUNCH_CHECK(ctx);
-  hipLaunchKernelGGL(bn_bwd_combine_kernel, dim3(cdiv(c, 128)), dim3(128), 0, ctx->stream, c, ng, n_labels, labels, gamma,
-                     (const float*)partial, dgamma, dbeta, s12, accumulate);
-  RC_LAUNCH_CHECK(ctx);
-  long total = rows * c;
-  if (vec) {
-    float* A = s12 + 2 * (size_t)c;
-    float* PQ = A + (size_t)n_labels * c;
-    hipLaunchKernelGGL(bn_table_bwd_kernel, dim3(cdiv((long)n_labels * c, 256)), dim3(256), 0, ctx->stream, n_labels, c, rows, gamma, mean, rstd,
-                       (const float*)s12, A, PQ);
-    RC_LAUNCH_CHECK(ctx);
-    long nchunks = total / 8;
-    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_vec_kernel<T>, dim3(ew_grid2(nchunks)), dim3(256), 0, ctx->stream, nchunks,
-                                                     rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, (const float*)A,
-                                                     (const float*)PQ, act, (T*)dx, accumulate_dx));
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_bwd_apply_kernel<T>, dim3(ew_grid2(total)), dim3(256), 0, ctx->stream, total, rows,
-                                                   rows_per_sample, c, (const T*)x, (const T*)y, (const T*)dy, labels, gamma, mean,
-                                                   rstd, (const float*)s12, act, (T*)dx, accumulate_dx));
-  RC_LAUNCH_CHECK(ctx);
-  return RCGAN_OK;
+  t.beta = (beta && (act == RCGAN_ACT_RELU || act == RCGAN_ACT_LRELU)) ? beta : nullptr;
+  if (int rc = bn_check_args(ctx, s, labels, {x, dy, gamma, mean, rstd, dx, dgamma, dbeta})) return rc;
+  const BnPlan p = bn_plan(s, bn_choose(s).route);
+  RC_REQUIRE(ctx, y || act == RCGAN_ACT_NONE || (t.beta && p.apply == BN_COLUMN), "the activation's derivative needs y");
+  if (int rc = bn_reduce(ctx, s, p, t, ws)) return rc;
+  return bn_launch_apply_bwd(ctx, s, p, t, (float*)ws);
 }
 
 int rcgan_bn_infer(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, const float* gamma, const float* beta,
                    const float* mm, const float* mv, float eps, int act, void* y) {
   long total = (long)rows * c;
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_kernel<T>, dim3(ew_grid2(total)), dim3(256), 0, ctx->stream, total, c,
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_kernel<T>, dim3(bn_apply_grid(total, 0)), dim3(256), 0, ctx->stream, total, c,
                                                    (const T*)x, gamma, beta, mm, mv, eps, act, (T*)y));
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
@@ -1508,7 +1375,7 @@ int rcgan_bn_infer_bwd(rcgan_ctx* ctx, int rows, int c, int dtype, const void* y
   RC_REQUIRE(ctx, act == RCGAN_ACT_NONE || act == RCGAN_ACT_RELU || act == RCGAN_ACT_TANH || act == RCGAN_ACT_SIGMOID,
              "activation %d has no output-side derivative", act);
   long total = (long)rows * c;
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_bwd_kernel<T>, dim3(ew_grid2(total)), dim3(256), 0, ctx->stream, total, c,
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_bwd_kernel<T>, dim3(bn_apply_grid(total, 0)), dim3(256), 0, ctx->stream, total, c,
                                                    (const T*)y, (const T*)dy, gamma, mv, eps, act, (T*)dx, accumulate));
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;

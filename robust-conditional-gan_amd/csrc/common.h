@@ -77,12 +77,10 @@ struct rcgan_ctx {
 #define RC_LINE_STRIDE 32      // words between two line counters
 #define RC_LCOUNTER_BN 0       // lines [0,32)
 #define RC_LCOUNTER_BNSEG 32   // lines [32,288)
-#define RC_COUNTER_BN 0        // [0,32): one per 64-channel column block of the batch-norm reductions
 #define RC_COUNTER_WGRAD 32    // [32,..): filter-gradient finish
 #define RC_COUNTER_HEAD 500    // loss partials of the fused projection head
 #define RC_COUNTER_INPUTS 501  // the step-input rider of the filter preparation (step_inputs.h)
 #define RC_COUNTER_XENT 502    // row sums of the sparse softmax cross-entropy (classifier.hip)
-#define RC_COUNTER_BNSEG 512   // [512,768): segmented forward batch norm, one per (segment, 64-channel column block)
 
 // grow-only scratch (*buf, *cap) of at least `need` bytes; never inside a capture, and an outgrown buffer stays allocated (a graph
 // captured earlier replays launches that address it)

@@ -150,6 +150,31 @@ def test_bn_abi_bounds(dev):
     assert ctx.lib.rcgan_bn_workspace_bytes_labels(1024, 256, 1000) > ctx.lib.rcgan_bn_workspace_bytes(1024, 256)
 
 
+def test_bn_refuses_before_it_launches(dev):
+    """Conditional calls without labels and empty shapes return EINVALID_ARG and leave the output as it was."""
+    from rcgan_amd import _lib as L
+    ctx, mode = dev
+    n, rps, c, K = 4, 16, 128, 10
+    x = ctx.upload(np.ones((n * rps, c), np.float32), ctx.act_dtype)
+    f = ctx.upload(np.ones((K * c,), np.float32), L.F32)
+    ws, wsb = C.c_void_p(ctx.ws_ptr), ctx.ws_bytes
+    sentinel = -77.0
+    y = ctx.upload(np.full((n * rps, c), sentinel, np.float32), ctx.act_dtype)
+    mean, rstd = (ctx.upload(np.full((c,), sentinel, np.float32), L.F32) for _ in range(2))
+    calls = {
+        "apply_fwd without labels": lambda: ctx.lib.rcgan_bn_apply_fwd(ctx.h, n, rps, c, K, x.dtype, _p(x), None, _p(f), _p(f), _p(f), _p(f), L.ACT_NONE,
+                                                                        _p(y), ws, wsb),
+        "fwd_segments without labels": lambda: ctx.lib.rcgan_bn_fwd_segments(ctx.h, 2, n // 2, rps, c, K, x.dtype, _p(x), None, _p(f), _p(f), 1e-5,
+                                                                              L.ACT_NONE, _p(mean), _p(rstd), _p(y), ws, wsb),
+        "stats c = 0": lambda: ctx.lib.rcgan_bn_stats(ctx.h, n * rps, 0, x.dtype, _p(x), 1e-5, _p(mean), _p(rstd), None, None, 0.0, ws, wsb),
+        "stats rows = 0": lambda: ctx.lib.rcgan_bn_stats(ctx.h, 0, c, x.dtype, _p(x), 1e-5, _p(mean), _p(rstd), None, None, 0.0, ws, wsb),
+    }
+    for what, call in calls.items():
+        assert call() == L.EINVALID_ARG, what
+        for t in (y, mean, rstd):
+            assert (ctx.download(t) == sentinel).all(), what + ": output touched"
+
+
 HEAD_PARTS = [
     ("HINGE_REAL", "lab", "HINGE_FAKE", "lab"),     # rcgan / biased critic step
     ("HINGE_REAL", "lab", "HINGE_FAKE", "wts"),     # rcgan-u critic step: confusion rows

@@ -1193,6 +1193,51 @@ def test_batch_norm_segments_large(dev):
         assert_close(got[sl], np.maximum(pre, 0), TOL[mode], "segment %d" % k)
 
 
+# segmented forward at the smallest shapes that reach each branch of the planner (csrc/bn_plan.h): segments x shape of one segment
+BN_SEGMENT_CASES = [(5, (2, 8, 8, 64)),        # column route with the segment as the grid's z
+                    (3, (2, 4, 4, 24)),        # one segment at a time, scalar kernels
+                    (3, (2, 3, 3, 200)),       # one segment at a time, vector kernels
+                    (9, (1, 2, 2, 2048))]      # 9 * 32 > 256 counter lines: one segment at a time for a fused channel count
+
+
+@pytest.mark.parametrize("nseg,shape", BN_SEGMENT_CASES)
+def test_batch_norm_segments_routes(dev, nseg, shape):
+    """rcgan_bn_fwd_segments (conditional, ReLU) against the oracle applied to each segment on its own; then
+    rcgan_bn_apply_segments on the statistics of a statistics-only call (y = NULL) gives the one-call output bit for bit."""
+    from rcgan_amd import _lib as L
+    ctx, mode = dev
+    n, h, w, c = shape
+    rps, nl = h * w, 10
+    rs = np.random.RandomState(nseg * 1000 + c)
+    x = _prep(rs.randn(nseg * n, h, w, c) * 1.3 + rs.randn(nseg, 1, 1, 1, 1).repeat(n, 1).reshape(nseg * n, 1, 1, 1), mode)
+    gamma = (1 + 0.3 * rs.randn(nl, c)).astype(np.float32)
+    beta = (0.2 * rs.randn(nl, c)).astype(np.float32)
+    labels = rs.randint(nl, size=nseg * n).astype(np.int32)
+    ctx.new_step()
+    p = lambda t: C.c_void_p(t.ptr)
+    xd, lab, gd, bd = ctx.upload(x), ctx.upload(labels), ctx.upload(gamma, L.F32), ctx.upload(beta, L.F32)
+    ws, wsb = C.c_void_p(ctx.ws_ptr), ctx.ws_bytes
+
+    def stats_and_y(with_y):
+        mean, rstd = ctx.empty((nseg, c), L.F32), ctx.empty((nseg, c), L.F32)
+        y = ctx.empty(x.shape, xd.dtype)
+        ctx.check(ctx.lib.rcgan_bn_fwd_segments(ctx.h, nseg, n, rps, c, nl, xd.dtype, p(xd), p(lab), p(gd), p(bd), 1e-5, L.ACT_RELU, p(mean), p(rstd),
+                                                p(y) if with_y else None, ws, wsb))
+        return mean, rstd, y
+
+    mean, rstd, y = stats_and_y(True)
+    got = ctx.download(y).reshape(x.shape)
+    for k in range(nseg):
+        sl = slice(k * n, (k + 1) * n)
+        pre, _ = nn.cond_batchnorm_fwd(x[sl].astype(np.float64), labels[sl], gamma.astype(np.float64), beta.astype(np.float64))
+        assert_close(got[sl], np.maximum(pre, 0), TOL[mode], "segment %d" % k)
+    mean2, rstd2, y2 = stats_and_y(False)
+    assert np.array_equal(ctx.download(mean2), ctx.download(mean)) and np.array_equal(ctx.download(rstd2), ctx.download(rstd))
+    ctx.check(ctx.lib.rcgan_bn_apply_segments(ctx.h, nseg, n, rps, c, nl, xd.dtype, p(xd), p(lab), p(gd), p(bd), p(mean2), p(rstd2), L.ACT_RELU, p(y2),
+                                              ws, wsb))
+    assert np.array_equal(ctx.download(y2).reshape(x.shape), got), "apply_segments differs from the one-call output"
+
+
 def test_batch_norm_infer(dev):
     from rcgan_amd import _lib as L
     from rcgan_amd import ops as O
