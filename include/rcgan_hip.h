@@ -612,6 +612,19 @@ int rcgan_diffaugment_fwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int po
 int rcgan_diffaugment_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* dy, const float* u, void* dx,
                           int accumulate);
 
+/* ---- per-class moments of a feature stream (csrc/moments.hip; the Frechet distance of frechet.py) ------------------------------
+ * state (caller-owned, zeroed once by the caller, rcgan_class_moments_bytes(d, n_classes) bytes, 8-byte aligned), all fp64:
+ *   count[K], sum[K][d], sumsq[K][d][d] = the full matrix sum of x x^T over the rows of each class, then ONE counter of rejected rows.
+ * Every call adds a batch feat[n][d] (fp32) with labels[n]; labels may be NULL only with n_classes == 1 (every row is class 0).  A
+ * label outside [0, K) writes nowhere: its row is skipped and the rejected counter goes up by one.
+ * One launch on the context's stream, no host synchronisation, legal inside a captured graph.  The product of two fp32 values is
+ * exact in fp64; every entry is summed by one owner thread in row order and then added to the state (no floating-point atomics): the
+ * same bits on every run, and an error of at most n 2^-52 sum|x_i x_j| per entry.
+ * 1 <= d <= 256, 1 <= n_classes <= 1024, n >= 1, non-NULL feat / state: anything else is RCGAN_EINVALID_ARG before any launch (a
+ * NULL context included, so the checks need no device); rcgan_class_moments_bytes returns 0 for a d or n_classes outside the bounds. */
+size_t rcgan_class_moments_bytes(int d, int n_classes);
+int rcgan_class_moments_accum(rcgan_ctx* ctx, int n, int d, int n_classes, const float* feat, const int32_t* labels, void* state);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

@@ -713,13 +713,16 @@ BN_INTO_CONV = os.environ.get("RCGAN_BN_INTO_CONV", "1") != "0"
 
 
 def batch_norm_act(ctx, x, gamma, beta, act=L.ACT_NONE, labels=None, n_labels=1, moving=None, decay=0.9, eps=1e-5, segments=1,
-                   defer_apply=False):
+                   defer_apply=False, stats_out=None):
     """Batch statistics + (conditional) affine + activation, one fused op.
     labels=None: tf.contrib.layers.batch_norm (mnist/ops.py:38-44), ``moving`` = (moving_mean, moving_var)
     DTs updated in place.  labels=int32 DT [n]: cond_batchnorm (cifar10/common/ops/normalization.py:27-59),
     gamma/beta are [n_labels, c] tables.  segments > 1 (forward only): x holds that many independent batches back to
-    back, each normalised with its own statistics -- several Generator() calls of the reference evaluated as one."""
+    back, each normalised with its own statistics -- several Generator() calls of the reference evaluated as one.
+    stats_out = (mean, rstd) fp32 DTs [c] (plain route only): the batch moments are left there instead of in arena scratch."""
     n, rps, c = _rows(x)
+    if stats_out is not None and (segments > 1 or defer_apply):
+        raise NotImplementedError("stats_out is for the plain batch norm (one segment, applied at once)")
     rows = n * rps
     tile = getattr(x, "tile_stats", None) if moving is None else None      # statistics left by the producing convolution's epilogue
     if (defer_apply and BN_INTO_CONV and not ctx.recording and moving is None and tile is None and x.dtype != L.F32
@@ -780,8 +783,7 @@ def batch_norm_act(ctx, x, gamma, beta, act=L.ACT_NONE, labels=None, n_labels=1,
         ctx.check(ctx.lib.rcgan_bn_fwd_segments(ctx.h, segments, n // segments, rps, c, n_labels, x.dtype, _p(x), _p(labels), _p(gamma),
                                                 _p(beta), eps, act, _p(mean), _p(rstd), _p(y), C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
         return y
-    mean = ctx.empty((c,), L.F32)
-    rstd = ctx.empty((c,), L.F32)
+    mean, rstd = stats_out if stats_out is not None else (ctx.empty((c,), L.F32), ctx.empty((c,), L.F32))
     mm, mv = moving if moving is not None else (None, None)
     if tile is not None:
         ctx.check(ctx.lib.rcgan_bn_stats_from_tiles(ctx.h, C.byref(tile[0]), 1, eps, _p(tile[1]), _p(mean), _p(rstd)))

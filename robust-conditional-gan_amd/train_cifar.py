@@ -67,6 +67,10 @@ def define_flags():
                     "rcgan_amd.train_classifier writes one for any class count); default: the built-in CIFAR-10 network")
     f.DEFINE_string("diffaugment", '', "differentiable augmentation of every image the critic sees: a comma-separated subset of "
                     "color,translation,cutout (empty: off)")
+    f.DEFINE_integer("frechet_freq", 0, "period (iterations) of the Frechet distance on the label classifier's features, pooled and "
+                     "per class against the clean training set; also taken at the end of training (0: off)")
+    f.DEFINE_integer("frechet_samples", 10000, "generated samples per Frechet evaluation (hundreds), balanced over the classes")
+    f.DEFINE_integer("frechet_real_samples", 0, "real images behind the real-set statistics (0: the whole training set)")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -97,11 +101,23 @@ def gen_acc_label_lists(n_classes, balanced=False):
     return [np.sort((100 * j + np.arange(100)) % n_classes).tolist() for j in range(10)]
 
 
+def clean_training_set(FLAGS, data_dir):
+    """The training images [N,3072] (CHW rows) with their CLEAN labels, read again from --data_dir (``data.load`` hands out
+    generators over corrupted labels only)."""
+    if FLAGS.dataset == "cifar100":
+        tx, ty = D.unpickle100(os.path.join(data_dir, 'train'), FLAGS.coarse_labels)
+        return np.asarray(tx), np.asarray(ty)
+    parts = [D.unpickle(os.path.join(data_dir, 'data_batch_%d' % i)) for i in range(1, 6)]
+    return np.concatenate([p[0] for p in parts], axis=0), np.concatenate([p[1] for p in parts], axis=0)
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     FLAGS = define_flags().parse(argv)
     if FLAGS.log_file is None:
         raise ValueError('flag log_file is required')                         # gan_resnet.py:81-82
+    if FLAGS.frechet_freq < 0 or FLAGS.frechet_real_samples < 0 or (FLAGS.frechet_freq > 0 and FLAGS.frechet_samples < 100):
+        raise ValueError('--frechet_freq and --frechet_real_samples must not be negative, --frechet_samples at least 100')
     N_CLASSES, DATA = dataset_setup(FLAGS)
     if FLAGS.label_classifier is not None:
         # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
@@ -168,8 +184,10 @@ def main(argv=None):
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
+    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq
     if FLAGS.synthetic:
         tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
+        clean_train = (tx, np.array(ty))
         vx, vy = D.synthetic_cifar(10000, 1235, FLAGS.synthetic_kind, N_CLASSES)
         train_gen = D.cifar_generator(tx, ty, BATCH_SIZE, C_ALPHA)
         dev_gen = D.cifar_generator(vx, vy, BATCH_SIZE, C_ALPHA)
@@ -227,6 +245,33 @@ def main(argv=None):
         acc = generated_label_accuracy(samples, labels, confusion_matrix=confusion_matrix, classifier=acc_state["clf"])
         logging.info('generated label accuracy: {}'.format(acc))
         return acc
+
+    # Frechet distance on the label classifier's frozen features (frechet.py), pooled and per class against the CLEAN training set
+    FRECHET_FREQ = FLAGS.frechet_freq
+    frechet_state = {"ev": None}
+
+    def frechet_distances(confusion_matrix=None):
+        from . import frechet as FR
+        ev = frechet_state["ev"]
+        if ev is None:
+            ev = frechet_state["ev"] = FR.FrechetEvaluator(N_CLASSES, asset=FLAGS.label_classifier, device=local)
+            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
+            n_real = FLAGS.frechet_real_samples if FLAGS.frechet_real_samples > 0 else len(rx)
+            ev.prepare_real(rx[:n_real], ry[:n_real], cache_path=os.path.join(DIR, FR.CACHE_NAME))
+            logging.info('frechet real statistics: {} images, {}'.format(
+                min(n_real, len(rx)), 'reused from ' + FR.CACHE_NAME if ev.reused else 'computed'))
+        balanced = gen_acc_label_lists(N_CLASSES, balanced=True)
+        calls = [balanced[j % len(balanced)] for j in range(FLAGS.frechet_samples // 100)]
+        samples = [m.sample(labels, is_rs.normal(size=(100, Z_DIM)).astype('float32')) for labels in calls]
+        samples = ((np.concatenate(samples, axis=0) + 1.) * (255.99 / 2)).astype('int32').reshape((-1, 32, 32, 3))   # (NHWC, as save_samples)
+        labels = np.concatenate(calls, axis=0)
+        if confusion_matrix is not None:
+            labels = FR.permuted_labels(labels, confusion_matrix)
+        r = ev.evaluate(samples, labels)
+        logging.info('frechet_distance: {}'.format(r["frechet_distance"]))
+        logging.info('intra_class_frechet_distance: {} ({} of {} classes)'.format(
+            r["intra_class_frechet_distance"], r["classes_used"], N_CLASSES))
+        return r
 
     def inception_score(n):
         # gan_resnet.py:836-845: 100 samples with uniformly random labels per Generator call, n / 100 calls
@@ -316,6 +361,12 @@ def main(argv=None):
             plot.plot('gen_label_acc', accuracy)
             plot.plot('gen_label_acc_max', acc_state["max"])
             logging.info('finished calculating generated label accuracy.')
+        if rank == 0 and FRECHET_FREQ > 0 and iteration % FRECHET_FREQ == FRECHET_FREQ - 1:
+            logging.info('starting calculating frechet distance.')
+            r = frechet_distances()
+            plot.plot('frechet_distance', r["frechet_distance"])
+            plot.plot('intra_class_frechet_distance', r["intra_class_frechet_distance"])
+            logging.info('finished calculating frechet distance.')
         ECE = max(FLAGS.early_checkpoint_every, 1)
         if rank == 0 and ((iteration < 500 and iteration % ECE == ECE - 1) or (iteration % 1000 == 999)):      # :1007-1014
             drain_losses()
@@ -327,12 +378,21 @@ def main(argv=None):
         logging.info('starting calculating %sgenerated label accuracy.' % ('min. permuted ' if cm is not None else ''))
         plot.plot('gen_label_acc', label_accuracy(cm))
         logging.info('finished calculating generated label accuracy.')
+    if rank == 0 and FRECHET_FREQ > 0:
+        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
+        logging.info('starting calculating %sfrechet distance.' % ('min. permuted ' if cm is not None else ''))
+        r = frechet_distances(cm)
+        plot.plot('frechet_distance', r["frechet_distance"])
+        plot.plot('intra_class_frechet_distance', r["intra_class_frechet_distance"])
+        logging.info('finished calculating frechet distance.')
     drain_losses()
     if rank == 0 and ITERS:
         plot.dir_flush(DIR)
         saver.save(m.state_dict(), CHECKPOINT_DIR, 'model.ckpt', max(ITERS - 1, 0))
     if acc_state["clf"] is not None:
         acc_state["clf"].close()
+    if frechet_state["ev"] is not None:
+        frechet_state["ev"].close()
     m.ctx.close()
     return DIR
 
