@@ -232,13 +232,15 @@ int rcgan_conv2d_bwd_data(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* 
                           const void* x /* needed with IN_RELU */, void* dx, void* ws, size_t ws_bytes);
 /* dx = conv2d_backprop_input(dy) (masked by x > 0 under RCGAN_CONV_IN_RELU) + residual, written out of place: the
  * accumulate of a second gradient contribution without touching the buffer that holds the first one (needed when that
- * buffer is still to be read, e.g. by a deferred filter gradient).  residual: [n, h, w, cin], must not alias dx. */
+ * buffer is still to be read, e.g. by a deferred filter gradient).  residual: [n, h, w, cin], must not alias dx.
+ * ws: rcgan_conv_workspace_bytes(d), as for rcgan_conv2d_bwd_data. */
 int rcgan_conv2d_bwd_data_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* dy, const void* prepared,
                                    const void* x /* IN_RELU mask or NULL */, const void* residual, void* dx, void* ws, size_t ws_bytes);
 /* dw (fp32 HWIO) = d(conv)/dw (dw = or += by accumulate), dbias = sum dy (if non-NULL).
  * Replaces tf.nn.conv2d_backprop_filter + BiasAddGrad.  Upsample-3x3 (IN_UPSAMPLE2X: x stored at [n,h/2,w/2,cin]) and
  * ConvMeanPool (OUT_MEANPOOL2: dy pooled) layers on the matrix cores are computed in their sub-pixel form: 16 Cin x Cout
- * products over the low-resolution grid folded into the 9 taps by the slab reduction, instead of 9 over the full one. */
+ * products over the low-resolution grid folded into the 9 taps by the slab reduction, instead of 9 over the full one.
+ * ws: rcgan_conv_workspace_bytes(d). */
 /* 1 if rcgan_conv2d_bwd_weight takes d with RCGAN_CONV_OUT_MEANPOOL2 (dy = the pooled gradient) */
 int rcgan_conv_wgrad_pool_ok(const rcgan_conv_desc* d);
 int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy,
@@ -246,7 +248,10 @@ int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void
 /* The filter gradients of `n` layers in one call (all x / dy available: the end of a backward pass).  Same results as n
  * rcgan_conv2d_bwd_weight calls; the layers the three-tap matrix-core kernel takes share ONE launch (+ one slab reduction):
  * the discriminator's 8x8 / 16x16 layers are launch-latency-bound one by one.  dbiases[i] may be NULL.
- * ws: at least twice the largest rcgan_conv2d_workspace_bytes of the layers plus the sum of their slab sizes. */
+ * ws: rcgan_conv2d_bwd_weight_group_workspace_bytes(n, descs) suffices.  The call splits ws in two halves: the first holds the slabs of
+ * the grouped launches, the second serves every layer computed by a call of its own -- a layer whose slabs do not fit the first half is
+ * one of those (same values), so any ws of at least twice the largest rcgan_conv_workspace_bytes of the layers is enough to be correct. */
+size_t rcgan_conv2d_bwd_weight_group_workspace_bytes(int n, const rcgan_conv_desc* descs);
 int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* descs, const void* const* xs, const void* const* dys,
                                   float* const* dws, float* const* dbiases, int accumulate, void* ws, size_t ws_bytes);
 
@@ -261,6 +266,7 @@ int rcgan_deconv2d_bwd_data(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void
  * gradient -- the x part lands straight in x's gradient, a third of the column tiles (138 -> 128 channels) and the split kernel go away.
  * n_cols = 0: all of them. */
 int rcgan_deconv2d_bwd_data_cols(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* dy, const float* w, void* dx, int n_cols);
+/* dw [kh][kw][Cout][Cin] (= or +=), dbias = sum dy.  ws: rcgan_conv_workspace_bytes(d). */
 int rcgan_deconv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy,
                               float* dw, float* dbias, int accumulate, void* ws, size_t ws_bytes);
 /* The same filter gradient for x = conv_cond_concat(t, yb) (mnist/ops.py:46-51; the generator's g_h2 / g_h3, model.py:722-731): the first
@@ -280,7 +286,7 @@ int rcgan_linear_fwd(rcgan_ctx* ctx, int m, int k, int n, int dtype, const void*
                      const float* sigma, const float* bias, void* y);
 int rcgan_linear_bwd_data(rcgan_ctx* ctx, int m, int k, int n, int dtype, const void* dy, const float* w,
                           const float* sigma, void* dx, int accumulate);
-/* dw is the gradient w.r.t. the matrix actually multiplied (W or W_bar). */
+/* dw is the gradient w.r.t. the matrix actually multiplied (W or W_bar).  ws: rcgan_linear_workspace_bytes(m, k, n). */
 int rcgan_linear_bwd_weight(rcgan_ctx* ctx, int m, int k, int n, int dtype, const void* x, const void* dy,
                             float* dw, float* dbias, int accumulate, void* ws, size_t ws_bytes);
 size_t rcgan_linear_workspace_bytes(int m, int k, int n);
@@ -302,7 +308,8 @@ int rcgan_bn_stats(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, fl
  * (cifar10/common/ops/normalization.py:47-57) and tf.contrib.layers.batch_norm (mnist/ops.py:38-44)
  * fused with the following relu / lrelu (gan_resnet.py:305,317,366; mnist/model.py:661-719).
  * Every batch-norm call returns RCGAN_EINVALID_ARG, before it launches anything, for a non-positive shape, n_labels outside
- * 1 .. 1024, n_labels > 1 with labels NULL (rcgan_bn_fwd_segments with y = NULL included), or a NULL tensor it would touch. */
+ * 1 .. 1024, n_labels > 1 with labels NULL (rcgan_bn_fwd_segments with y = NULL included), or a NULL tensor it would touch.
+ * ws: rcgan_bn_workspace_bytes_labels(n*rows_per_sample, c, n_labels). */
 int rcgan_bn_apply_fwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x,
                        const int32_t* labels, const float* gamma, const float* beta,
                        const float* mean, const float* rstd, int act, void* y, void* ws, size_t ws_bytes);
@@ -317,13 +324,15 @@ int rcgan_bn_fwd_segments(rcgan_ctx* ctx, int nseg, int n_per_seg, int rows_per_
  * (= or += by accumulate); dx = or += by accumulate_dx.  y is the forward output (activation mask).
  * n_labels <= 16: per-label accumulators in registers / LDS (the fused, tree and generic paths).  17 .. 1024: per-sample partials
  * in ws, then a deterministic fp64 reduction per (label, channel) in sample order; a label absent from the batch gets 0 (left
- * untouched under accumulate).  ws: (n*2*c + 4*c) floats on that route (within rcgan_bn_workspace_bytes for n <= 8192). */
+ * untouched under accumulate).  ws: rcgan_bn_workspace_bytes_labels(n*rows_per_sample, c, n_labels); the per-sample route uses
+ * (n*2*c + 4*c) floats of it (within rcgan_bn_workspace_bytes for n <= 8192). */
 int rcgan_bn_bwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype,
                  const void* x, const void* y, const void* dy, const int32_t* labels,
                  const float* gamma, const float* mean, const float* rstd, int act,
                  void* dx, int accumulate_dx, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes);
 /* rcgan_bn_bwd with the forward's beta (offset) table: for ReLU / leaky-ReLU the activation mask is then recomputed from x with
- * the forward's exact arithmetic (the fused power-of-two-channel kernels), so y is not read: 2 instead of 3 tensor reads per pass. */
+ * the forward's exact arithmetic (the fused power-of-two-channel kernels), so y is not read: 2 instead of 3 tensor reads per pass.
+ * ws: rcgan_bn_workspace_bytes_labels(n*rows_per_sample, c, n_labels), as rcgan_bn_bwd. */
 int rcgan_bn_bwd2(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype, const void* x, const void* y,
                   const void* dy, const int32_t* labels, const float* gamma, const float* beta, const float* mean, const float* rstd,
                   int act, void* dx, int accumulate_dx, float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes);
@@ -506,7 +515,8 @@ int rcgan_conv2d_rf(rcgan_ctx* ctx, const rcgan_conv_desc* d, int backward, cons
  * Bounds: n <= 1024, d <= 256, 1 <= v <= 1024.  v <= 16: label embeddings in LDS, parameter gradients may ride (E_pre, defer_ws).
  * v > 16: a route with nothing sized by v in LDS or registers (a thread per output of E, dE and the parameter gradients; the
  * weight-row logits 64 labels at a time): defer_ws is ignored (the gradients are complete on return), E_pre is honoured,
- * ws: (v*d + n*(v+1) + (v+1)*d + n + n*d) floats. */
+ * ws: (v*d + n*(v+1) + (v+1)*d + n + n*d) floats.  rcgan_proj_head_workspace_bytes(n, d, v) is enough for either route. */
+size_t rcgan_proj_head_workspace_bytes(int n, int d, int v);
 typedef struct {
   int n, d, v, e_dim;
   int rows_a, kind_a, kind_b;
@@ -540,7 +550,8 @@ int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x,
 /* recover_labels objective (mnist/model.py:533-537): gen [r*ydim, pix] = one generated image per (real sample r, label y),
  * actual [r, pix], yrec [r, ydim] = softmax of the recovered label logits.
  *   loss = mean_r sum_y yrec[r,y] * mean_pix (actual[r] - gen[r,y])^2
- * Writes loss [1], dgen (same shape as gen, or NULL) and dyrec [r, ydim] (or NULL).  ws: r*ydim floats. */
+ * Writes loss [1], dgen (same shape as gen, or NULL) and dyrec [r, ydim] (or NULL).  ws: r*ydim floats = rcgan_recover_mse_workspace_bytes(r, ydim). */
+size_t rcgan_recover_mse_workspace_bytes(int r, int ydim);
 int rcgan_recover_mse_fwd_bwd(rcgan_ctx* ctx, int r, int ydim, int pix, int dtype, const void* gen, const void* actual,
                               const float* yrec, float* loss, void* dgen, float* dyrec, void* ws, size_t ws_bytes);
 /* C = softmax(logits) row-wise and its adjoint (gan_resnet.py:522, mnist/model.py:106).  A thread per row: any cols (the
@@ -647,7 +658,7 @@ int rcgan_copy_words(rcgan_ctx* ctx, size_t count, const void* src, void* dst);
  * sums of the STORED output (bias, residual and the 16-bit rounding included) and of its squares in tile_sums (rcgan_conv_stats_bytes);
  * rcgan_bn_stats_from_tiles turns them into mean / rstd [nseg][Cout] of nseg equal runs of samples (biased variance, as rcgan_bn_stats):
  * the statistics pass over the activation tensor (one full read) disappears.  rcgan_bn_apply_segments: the apply half of
- * rcgan_bn_fwd_segments for statistics obtained that way. */
+ * rcgan_bn_fwd_segments for statistics obtained that way (ws: nseg * rcgan_bn_workspace_bytes(n_per_seg*rows_per_sample, c), as there). */
 int rcgan_conv_stats_ok(const rcgan_conv_desc* d);
 size_t rcgan_conv_stats_bytes(const rcgan_conv_desc* d);
 int rcgan_conv2d_fwd_stats(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* prepared, const float* bias,

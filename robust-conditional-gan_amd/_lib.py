@@ -156,6 +156,7 @@ SIGNATURES = {
     "rcgan_conv2d_bwd_data_residual": (I, [P, DP, P, P, P, P, P, P, SZ]),
     "rcgan_conv2d_bwd_weight": (I, [P, DP, P, P, P, P, I, P, SZ]),
     "rcgan_conv2d_bwd_weight_group": (I, [P, I, P, P, P, P, P, I, P, SZ]),
+    "rcgan_conv2d_bwd_weight_group_workspace_bytes": (SZ, [I, P]),
     "rcgan_deconv2d_fwd": (I, [P, DP, P, P, P, P]),
     "rcgan_deconv2d_bwd_data": (I, [P, DP, P, P, P]),
     "rcgan_deconv2d_bwd_data_cols": (I, [P, DP, P, P, P, I]),
@@ -166,6 +167,8 @@ SIGNATURES = {
     "rcgan_linear_bwd_data": (I, [P, I, I, I, I, P, P, P, P, I]),
     "rcgan_linear_bwd_weight": (I, [P, I, I, I, I, P, P, P, P, I, P, SZ]),
     "rcgan_linear_workspace_bytes": (SZ, [I, I, I]),
+    "rcgan_proj_head_workspace_bytes": (SZ, [I, I, I]),
+    "rcgan_recover_mse_workspace_bytes": (SZ, [I, I]),
     "rcgan_bn_workspace_bytes": (SZ, [I, I]),
     "rcgan_bn_workspace_bytes_labels": (SZ, [I, I, I]),
     "rcgan_bn_stats": (I, [P, I, I, I, P, F, P, P, P, P, F, P, SZ]),

@@ -1246,6 +1246,23 @@ int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* 
   return RCGAN_OK;
 }
 
+// What rcgan_conv2d_bwd_weight_group needs at most: the call splits ws in two halves -- the second serves every layer that is computed by a
+// call of its own (rcgan_conv_workspace_bytes of the largest), the first holds the slabs of the grouped launches (a layer whose slabs do
+// not fit there is computed on its own instead: same values).  Each half: the largest single need plus the single needs of the layers
+// that can be grouped (matrix-core and image-end layers), every term rounded up to 256 bytes.
+size_t rcgan_conv2d_bwd_weight_group_workspace_bytes(int n, const rcgan_conv_desc* descs) {
+  if (n <= 0 || descs == nullptr) return 0;
+  size_t largest = 0, slabs = 0;
+  for (int i = 0; i < n; ++i) {
+    const rcgan_conv_desc* d = descs + i;
+    if (d->n < 1 || d->h < 1 || d->w < 1 || d->cin < 1 || d->cout < 1 || d->kh < 1 || d->kw < 1 || d->stride < 1) return 0;
+    const size_t one = (rcgan_conv_workspace_bytes(d) + 255) / 256 * 256;
+    largest = std::max(largest, one);
+    if (mfma_wgrad_eligible(d) || img_side(d)) slabs += one;
+  }
+  return 2 * (largest + slabs);
+}
+
 // transposed conv: d describes the forward conv whose data-gradient it is (see header)
 int rcgan_deconv2d_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const float* w, const float* bias, void* y) {
   int rc = check_desc(ctx, d);

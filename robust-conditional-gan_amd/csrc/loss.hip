@@ -746,6 +746,14 @@ static int head_wide(rcgan_ctx* ctx, HeadArgs& a, const rcgan_head_desc* hd, voi
   return RCGAN_OK;
 }
 
+// Enough for either route of rcgan_proj_head_fwd_bwd: E | dlogit | dE and the larger of the two tails (256 floats for v <= HEAD_MAX_V; loss
+// rows + pooled dfeat for the wide route).
+size_t rcgan_proj_head_workspace_bytes(int n, int d, int v) {
+  if (n < 1 || d < 1 || v < 1) return 0;
+  const size_t tail = std::max((size_t)256, (size_t)n + (size_t)n * d);
+  return ((size_t)v * d + (size_t)n * (v + 1) + (size_t)(v + 1) * d + tail) * sizeof(float);
+}
+
 int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const float* feat, const float* w_out, const float* sigma_out,
                             const float* b_out, const float* table, const float* w_e, const float* sigma_e, const float* b_e,
                             float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
@@ -846,6 +854,8 @@ int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, c
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }
+
+size_t rcgan_recover_mse_workspace_bytes(int r, int ydim) { return r > 0 && ydim > 0 ? (size_t)r * ydim * sizeof(float) : 0; }
 
 int rcgan_recover_mse_fwd_bwd(rcgan_ctx* ctx, int r_count, int ydim, int pix, int dtype, const void* gen, const void* actual,
                               const float* yrec, float* loss, void* dgen, float* dyrec, void* ws, size_t ws_bytes) {

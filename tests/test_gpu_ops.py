@@ -1408,6 +1408,7 @@ def test_head_and_losses(dev):
 
     # rcgan-u pieces: all-label logits, learned confusion softmax, weighted loss, perm BCE
     ctx.new_step()
+    lab = ctx.upload(labels)         # (an arena tensor does not outlive new_step)
     feat = FakeParam(ctx, rs.randn(n, d))
     psi = FakeParam(ctx, rs.randn(n))
     E = FakeParam(ctx, rs.randn(v, d) * 0.1)
@@ -1434,6 +1435,7 @@ def test_head_and_losses(dev):
     np.add.at(dC, labels, term / n)
     assert_close(cl.grad(ctx), nn.softmax_rows_bwd(dC, Cref), 1e-4, "d confusion_logits")
     ctx.new_step()
+    lab = ctx.upload(labels)
     xl = FakeParam(ctx, rs.randn(n, v) * 3)
     loss = ctx.persistent((1,), L.F32, fill=0.0)
     O.bce_onehot_term(ctx, xl.t, lab, 2.0, loss)
@@ -1521,51 +1523,65 @@ def test_grouped_filter_gradients_equal_single_calls():
     in the grouped launch and whose slabs go through the grouped reduction; the 1x1 layer keeps its own pixel chunking and the
     256 -> 3 layers their own launches: bit-identical.  So are the two 3x3 layers on 12- and 24-pixel-wide grids: the three-tap kernel
     refuses them, the per-tap family's grouped launch (conv_mfma_wgrad_glds_group_kernel) keeps the single call's chunking rule."""
-    import ctypes as C
-    from rcgan_amd import _lib as L
     ctx = make_ctx("bf16")
     try:
-        lib, h = ctx.lib, ctx.h
-        ctx.new_step()
-        shapes = [(128, 8, 8, 128, 128, 3, L.CONV_IN_RELU), (16, 16, 16, 128, 128, 3, L.CONV_IN_RELU), (6, 8, 8, 256, 128, 3, 0),
-                  (4, 32, 32, 3, 128, 3, 0), (8, 8, 8, 128, 128, 1, 0), (3, 32, 32, 128, 256, 3, L.CONV_IN_RELU),
-                  (5, 32, 32, 3, 128, 3, 0), (16, 16, 16, 3, 128, 1, 0), (7, 16, 16, 3, 128, 1, 0),      # image-end layers: ride in the group
-                  (2, 32, 32, 256, 3, 3, L.CONV_IN_RELU), (3, 32, 32, 256, 3, 3, 0),                       # 256 -> 3: own launches
-                  (4, 12, 12, 128, 128, 3, 0), (2, 24, 24, 128, 256, 3, L.CONV_IN_RELU)]       # widths the three-tap kernel refuses: per-tap family
-        items = []
-        for i, (n, hh, ww, cin, cout, k, fl) in enumerate(shapes):
-            x, dy = ctx.empty((n, hh, ww, cin)), ctx.empty((n, hh, ww, cout))
-            ctx.check(lib.rcgan_rng_fill(h, x.size, x.dtype, 1, 0.0, 1.0, 100 + i, None, C.c_void_p(x.ptr)))
-            ctx.check(lib.rcgan_rng_fill(h, dy.size, dy.dtype, 1, 0.0, 1.0, 200 + i, None, C.c_void_p(dy.ptr)))
-            dws = [ctx.zeros((k, k, cin, cout), L.F32) for _ in range(2)]
-            dbs = [ctx.zeros((cout,), L.F32) for _ in range(2)] if i % 2 == 0 else [None, None]
-            items.append((L.ConvDesc(n, hh, ww, cin, cout, k, k, 1, L.BF16, fl), x, dy, dws, dbs))
-        ws, wsb = C.c_void_p(ctx.ws_ptr), ctx.ws_bytes
-        for d, x, dy, dws, dbs in items:
-            ctx.check(lib.rcgan_conv2d_bwd_weight(h, C.byref(d), C.c_void_p(x.ptr), C.c_void_p(dy.ptr), C.c_void_p(dws[0].ptr),
-                                                  C.c_void_p(dbs[0].ptr) if dbs[0] else None, 1, ws, wsb))
-        n = len(items)
-        descs = (L.ConvDesc * n)(*[it[0] for it in items])
-        arr = lambda f: (C.c_void_p * n)(*[f(it) for it in items])
-        ctx.check(lib.rcgan_conv2d_bwd_weight_group(h, n, descs, arr(lambda it: it[1].ptr), arr(lambda it: it[2].ptr),
-                                                    arr(lambda it: it[3][1].ptr), arr(lambda it: it[4][1].ptr if it[4][1] else None),
-                                                    1, ws, wsb))
-        for i, (d, x, dy, dws, dbs) in enumerate(items):
-            a, b = ctx.download(dws[0]), ctx.download(dws[1])
-            assert np.abs(a).max() > 0
-            own = (d.kh != 3 and d.cin % 128 == 0) or d.cout == 3 or (d.w & (d.w - 1)) != 0
-            print("layer %d: grouped - single max %.3e of %.3e" % (i, np.abs(a - b).max(), np.abs(a).max()))
-            if own:
-                assert np.array_equal(a, b), "layer %d filter gradient" % i
-            else:
-                assert_close(b, a, 2e-6, "layer %d filter gradient" % i)
-            if dbs[0] is not None:
-                print("layer %d: bias, grouped - single max %.3e" % (i, np.abs(ctx.download(dbs[1]) - ctx.download(dbs[0])).max()))
-                if (d.w & (d.w - 1)) != 0:
-                    assert np.array_equal(ctx.download(dbs[1]), ctx.download(dbs[0])), "layer %d bias gradient" % i
-                assert_close(ctx.download(dbs[1]), ctx.download(dbs[0]), 2e-6, "layer %d bias gradient" % i)
+        grouped_filter_gradients_case(ctx)
     finally:
         ctx.close()
+
+
+def grouped_filter_gradient_descs():
+    """The layers of test_grouped_filter_gradients_equal_single_calls, as descriptors."""
+    from rcgan_amd import _lib as L
+    shapes = [(128, 8, 8, 128, 128, 3, L.CONV_IN_RELU), (16, 16, 16, 128, 128, 3, L.CONV_IN_RELU), (6, 8, 8, 256, 128, 3, 0),
+              (4, 32, 32, 3, 128, 3, 0), (8, 8, 8, 128, 128, 1, 0), (3, 32, 32, 128, 256, 3, L.CONV_IN_RELU),
+              (5, 32, 32, 3, 128, 3, 0), (16, 16, 16, 3, 128, 1, 0), (7, 16, 16, 3, 128, 1, 0),      # image-end layers: ride in the group
+              (2, 32, 32, 256, 3, 3, L.CONV_IN_RELU), (3, 32, 32, 256, 3, 3, 0),                       # 256 -> 3: own launches
+              (4, 12, 12, 128, 128, 3, 0), (2, 24, 24, 128, 256, 3, L.CONV_IN_RELU)]       # widths the three-tap kernel refuses: per-tap family
+    return [L.ConvDesc(n, hh, ww, cin, cout, k, k, 1, L.BF16, fl) for n, hh, ww, cin, cout, k, fl in shapes]
+
+
+def grouped_filter_gradients_case(ctx):
+    """The body of test_grouped_filter_gradients_equal_single_calls on a bf16 context; -> its (desc, x, dy, [dw single, dw grouped],
+    [dbias single, dbias grouped] or [None, None]) per layer."""
+    import ctypes as C
+    from rcgan_amd import _lib as L
+    lib, h = ctx.lib, ctx.h
+    ctx.new_step()
+    items = []
+    for i, d0 in enumerate(grouped_filter_gradient_descs()):
+        n, hh, ww, cin, cout, k = d0.n, d0.h, d0.w, d0.cin, d0.cout, d0.kh
+        x, dy = ctx.empty((n, hh, ww, cin)), ctx.empty((n, hh, ww, cout))
+        ctx.check(lib.rcgan_rng_fill(h, x.size, x.dtype, 1, 0.0, 1.0, 100 + i, None, C.c_void_p(x.ptr)))
+        ctx.check(lib.rcgan_rng_fill(h, dy.size, dy.dtype, 1, 0.0, 1.0, 200 + i, None, C.c_void_p(dy.ptr)))
+        dws = [ctx.zeros((k, k, cin, cout), L.F32) for _ in range(2)]
+        dbs = [ctx.zeros((cout,), L.F32) for _ in range(2)] if i % 2 == 0 else [None, None]
+        items.append((d0, x, dy, dws, dbs))
+    ws, wsb = C.c_void_p(ctx.ws_ptr), ctx.ws_bytes
+    for d, x, dy, dws, dbs in items:
+        ctx.check(lib.rcgan_conv2d_bwd_weight(h, C.byref(d), C.c_void_p(x.ptr), C.c_void_p(dy.ptr), C.c_void_p(dws[0].ptr),
+                                              C.c_void_p(dbs[0].ptr) if dbs[0] else None, 1, ws, wsb))
+    n = len(items)
+    descs = (L.ConvDesc * n)(*[it[0] for it in items])
+    arr = lambda f: (C.c_void_p * n)(*[f(it) for it in items])
+    ctx.check(lib.rcgan_conv2d_bwd_weight_group(h, n, descs, arr(lambda it: it[1].ptr), arr(lambda it: it[2].ptr),
+                                                arr(lambda it: it[3][1].ptr), arr(lambda it: it[4][1].ptr if it[4][1] else None),
+                                                1, ws, wsb))
+    for i, (d, x, dy, dws, dbs) in enumerate(items):
+        a, b = ctx.download(dws[0]), ctx.download(dws[1])
+        assert np.abs(a).max() > 0
+        own = (d.kh != 3 and d.cin % 128 == 0) or d.cout == 3 or (d.w & (d.w - 1)) != 0
+        print("layer %d: grouped - single max %.3e of %.3e" % (i, np.abs(a - b).max(), np.abs(a).max()))
+        if own:
+            assert np.array_equal(a, b), "layer %d filter gradient" % i
+        else:
+            assert_close(b, a, 2e-6, "layer %d filter gradient" % i)
+        if dbs[0] is not None:
+            print("layer %d: bias, grouped - single max %.3e" % (i, np.abs(ctx.download(dbs[1]) - ctx.download(dbs[0])).max()))
+            if (d.w & (d.w - 1)) != 0:
+                assert np.array_equal(ctx.download(dbs[1]), ctx.download(dbs[0])), "layer %d bias gradient" % i
+            assert_close(ctx.download(dbs[1]), ctx.download(dbs[0]), 2e-6, "layer %d bias gradient" % i)
+    return items
 
 
 @pytest.mark.parametrize("case", [
