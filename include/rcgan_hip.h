@@ -636,6 +636,30 @@ int rcgan_diffaugment_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int po
 size_t rcgan_class_moments_bytes(int d, int n_classes);
 int rcgan_class_moments_accum(rcgan_ctx* ctx, int n, int d, int n_classes, const float* feat, const int32_t* labels, void* state);
 
+/* ---- k-nearest-neighbour radii and ball queries on feature rows (csrc/knn.hip; precision / recall / density / coverage of manifold.py)
+ * Rows [n][d] (fp32) are grouped into n_seg contiguous segments by an int32 DEVICE array off[n_seg + 1] (off[0] = 0, off[n_seg] = n,
+ * non-decreasing): one segment for a pooled metric, one per class for a per-class one.  Segment s of the queries only ever meets
+ * segment s of the references.  The kernel does not trust the array: every offset is clamped to [0, n] and off[s + 1] < off[s] is an
+ * empty segment, so a bad array gives wrong numbers (and rows outside every segment are not written) but never an access outside the
+ * tensors.  With a well-formed array every output row is written on every call.
+ * A squared distance is the fp32 sum of (a_i - b_i)^2 over ascending i, every term non-negative -- not |a|^2 + |b|^2 - 2 a.b, which
+ * loses a threshold comparison to cancellation: |computed - exact| <= (d + 3) 2^-24 exact.  (Hence vector fp32, not the matrix cores.)
+ * One launch each on the context's stream, no workspace, no host synchronisation, legal inside a captured graph; an order statistic,
+ * an integer count and a minimum do not depend on the merge order (no floating-point atomics): the same bits on every run.
+ * 1 <= d <= 256, 1 <= k <= 16, n, nq, nr >= 1, 1 <= n_seg <= 1024, required pointers non-NULL: anything else is RCGAN_EINVALID_ARG
+ * before any launch (a NULL context included, so the checks need no device).
+ *
+ * radius2[i] = the (k+1)-th smallest of { ||x_i - x_j||^2 : j in the segment of i, j = i included }
+ *            = squared distance to the k-th nearest OTHER row, duplicates counted;
+ *              -1.0f for every row of a segment with <= k rows. */
+int rcgan_knn_radius(rcgan_ctx* ctx, int n, int d, int k, int n_seg, const float* x, const int32_t* off, float* radius2);
+/* For query row i of segment s, over the reference rows j of segment s:
+ *   count[i]    = #{ j : ||q_i - r_j||^2 <= r_radius2[j] }   (a negative radius never matches)
+ *   nearest2[i] = min_j ||q_i - r_j||^2                      (+inf for an empty reference segment)
+ * count and nearest2 may each be NULL; r_radius2 may be NULL only when count is. */
+int rcgan_ball_query(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const float* q, const int32_t* q_off, const float* r,
+                     const int32_t* r_off, const float* r_radius2, int32_t* count, float* nearest2);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

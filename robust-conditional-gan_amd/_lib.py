@@ -231,6 +231,8 @@ SIGNATURES = {
     "rcgan_diffaugment_bwd": (I, [P, I, I, I, I, I, P, P, P, I]),
     "rcgan_class_moments_bytes": (SZ, [I, I]),
     "rcgan_class_moments_accum": (I, [P, I, I, I, P, P, P]),
+    "rcgan_knn_radius": (I, [P, I, I, I, I, P, P, P]),
+    "rcgan_ball_query": (I, [P, I, I, I, I, P, P, P, P, P, P, P]),
     "rcgan_sgd_momentum": (I, [P, SZ, SZ, P, P, P, P, F, F, I, F]),
     "rcgan_augment_cifar": (I, [P, I, I, P, P, P, P, I, I, P, P]),
     "rcgan_adam_tf": (I, [P, SZ, P, P, P, P, P, F, F, F, F, F]),

@@ -71,6 +71,11 @@ def define_flags():
                      "per class against the clean training set; also taken at the end of training (0: off)")
     f.DEFINE_integer("frechet_samples", 10000, "generated samples per Frechet evaluation (hundreds), balanced over the classes")
     f.DEFINE_integer("frechet_real_samples", 0, "real images behind the real-set statistics (0: the whole training set)")
+    f.DEFINE_integer("prdc_freq", 0, "period (iterations) of k-NN precision / recall / density / coverage on the label classifier's "
+                     "features, pooled and per class against the clean training set; also taken at the end of training (0: off)")
+    f.DEFINE_integer("prdc_samples", 10000, "generated samples per precision / recall evaluation (hundreds), balanced over the classes")
+    f.DEFINE_integer("prdc_real_samples", 0, "real images behind the real manifold (0: the whole training set)")
+    f.DEFINE_integer("prdc_k", 5, "the k of the k-nearest-neighbour radii (1..16)")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -118,6 +123,8 @@ def main(argv=None):
         raise ValueError('flag log_file is required')                         # gan_resnet.py:81-82
     if FLAGS.frechet_freq < 0 or FLAGS.frechet_real_samples < 0 or (FLAGS.frechet_freq > 0 and FLAGS.frechet_samples < 100):
         raise ValueError('--frechet_freq and --frechet_real_samples must not be negative, --frechet_samples at least 100')
+    if FLAGS.prdc_freq < 0 or FLAGS.prdc_real_samples < 0 or (FLAGS.prdc_freq > 0 and (FLAGS.prdc_samples < 100 or not 1 <= FLAGS.prdc_k <= 16)):
+        raise ValueError('--prdc_freq and --prdc_real_samples must not be negative, --prdc_samples at least 100, --prdc_k in 1..16')
     N_CLASSES, DATA = dataset_setup(FLAGS)
     if FLAGS.label_classifier is not None:
         # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
@@ -184,7 +191,7 @@ def main(argv=None):
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
-    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq
+    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq
     if FLAGS.synthetic:
         tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
         clean_train = (tx, np.array(ty))
@@ -250,7 +257,7 @@ def main(argv=None):
     FRECHET_FREQ = FLAGS.frechet_freq
     frechet_state = {"ev": None}
 
-    def frechet_distances(confusion_matrix=None):
+    def frechet_evaluator():
         from . import frechet as FR
         ev = frechet_state["ev"]
         if ev is None:
@@ -260,17 +267,53 @@ def main(argv=None):
             ev.prepare_real(rx[:n_real], ry[:n_real], cache_path=os.path.join(DIR, FR.CACHE_NAME))
             logging.info('frechet real statistics: {} images, {}'.format(
                 min(n_real, len(rx)), 'reused from ' + FR.CACHE_NAME if ev.reused else 'computed'))
+        return ev
+
+    def balanced_samples(n, confusion_matrix=None):
+        """n generated images (NHWC, as save_samples) with their conditioning labels balanced over the classes; rcgan-u: the labels
+        mapped through the learned matrix."""
+        from . import frechet as FR
         balanced = gen_acc_label_lists(N_CLASSES, balanced=True)
-        calls = [balanced[j % len(balanced)] for j in range(FLAGS.frechet_samples // 100)]
+        calls = [balanced[j % len(balanced)] for j in range(n // 100)]
         samples = [m.sample(labels, is_rs.normal(size=(100, Z_DIM)).astype('float32')) for labels in calls]
-        samples = ((np.concatenate(samples, axis=0) + 1.) * (255.99 / 2)).astype('int32').reshape((-1, 32, 32, 3))   # (NHWC, as save_samples)
+        samples = ((np.concatenate(samples, axis=0) + 1.) * (255.99 / 2)).astype('int32').reshape((-1, 32, 32, 3))
         labels = np.concatenate(calls, axis=0)
         if confusion_matrix is not None:
             labels = FR.permuted_labels(labels, confusion_matrix)
-        r = ev.evaluate(samples, labels)
+        return samples, labels
+
+    def frechet_distances(confusion_matrix=None):
+        ev = frechet_evaluator()
+        r = ev.evaluate(*balanced_samples(FLAGS.frechet_samples, confusion_matrix))
         logging.info('frechet_distance: {}'.format(r["frechet_distance"]))
         logging.info('intra_class_frechet_distance: {} ({} of {} classes)'.format(
             r["intra_class_frechet_distance"], r["classes_used"], N_CLASSES))
+        return r
+
+    # k-NN precision / recall / density / coverage on the same features (manifold.py), pooled and per class against the CLEAN training set
+    PRDC_FREQ = FLAGS.prdc_freq
+    manifold_state = {"ev": None}
+
+    def manifold_metrics(confusion_matrix=None):
+        from . import manifold as MF
+        ev = manifold_state["ev"]
+        if ev is None:
+            # both metrics on: one classifier, the one the other evaluator has calibrated
+            shared = frechet_evaluator().clf if FRECHET_FREQ > 0 else None
+            ev = manifold_state["ev"] = MF.ManifoldEvaluator(N_CLASSES, k=FLAGS.prdc_k, asset=FLAGS.label_classifier, device=local, clf=shared)
+            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
+            n_real = FLAGS.prdc_real_samples if FLAGS.prdc_real_samples > 0 else len(rx)
+            ev.prepare_real(rx[:n_real], ry[:n_real])
+            logging.info('manifold real set: {} images, k = {}, label classifier {}'.format(
+                min(n_real, len(rx)), FLAGS.prdc_k, 'shared' if shared is not None else 'of its own'))
+        r = ev.evaluate(*balanced_samples(FLAGS.prdc_samples, confusion_matrix))
+        for name in MF.METRICS:
+            logging.info('manifold_{}: {}'.format(name, r[name]))
+        for name in MF.METRICS:
+            logging.info('intra_class_manifold_{}: {} ({} of {} classes)'.format(name, r["intra_class_" + name], r["classes_used"], N_CLASSES))
+        for name in MF.METRICS:
+            plot.plot('manifold_' + name, r[name])
+            plot.plot('intra_class_manifold_' + name, r["intra_class_" + name])
         return r
 
     def inception_score(n):
@@ -367,6 +410,10 @@ def main(argv=None):
             plot.plot('frechet_distance', r["frechet_distance"])
             plot.plot('intra_class_frechet_distance', r["intra_class_frechet_distance"])
             logging.info('finished calculating frechet distance.')
+        if rank == 0 and PRDC_FREQ > 0 and iteration % PRDC_FREQ == PRDC_FREQ - 1:
+            logging.info('starting calculating manifold precision and recall.')
+            manifold_metrics()
+            logging.info('finished calculating manifold precision and recall.')
         ECE = max(FLAGS.early_checkpoint_every, 1)
         if rank == 0 and ((iteration < 500 and iteration % ECE == ECE - 1) or (iteration % 1000 == 999)):      # :1007-1014
             drain_losses()
@@ -385,12 +432,19 @@ def main(argv=None):
         plot.plot('frechet_distance', r["frechet_distance"])
         plot.plot('intra_class_frechet_distance', r["intra_class_frechet_distance"])
         logging.info('finished calculating frechet distance.')
+    if rank == 0 and PRDC_FREQ > 0:
+        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
+        logging.info('starting calculating %smanifold precision and recall.' % ('min. permuted ' if cm is not None else ''))
+        manifold_metrics(cm)
+        logging.info('finished calculating manifold precision and recall.')
     drain_losses()
     if rank == 0 and ITERS:
         plot.dir_flush(DIR)
         saver.save(m.state_dict(), CHECKPOINT_DIR, 'model.ckpt', max(ITERS - 1, 0))
     if acc_state["clf"] is not None:
         acc_state["clf"].close()
+    if manifold_state["ev"] is not None:
+        manifold_state["ev"].close()
     if frechet_state["ev"] is not None:
         frechet_state["ev"].close()
     m.ctx.close()
