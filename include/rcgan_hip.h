@@ -341,7 +341,9 @@ int rcgan_bn_infer(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, co
                    const float* beta, const float* moving_mean, const float* moving_var, float eps,
                    int act, void* y);
 /* Its adjoint w.r.t. x: dx (= or +=) dy * act'(y) * gamma / sqrt(moving_var + eps).  Used by recover_labels
- * (mnist/model.py:494-640), which differentiates the frozen sampler w.r.t. its latent input. */
+ * (mnist/model.py:494-640), which differentiates the frozen sampler w.r.t. its latent input.  act' is taken from the OUTPUT y for
+ * every activation (ReLU / leaky ReLU: its sign, y = 0 counting as the negative side); y may be NULL for RCGAN_ACT_NONE.
+ * Both calls return RCGAN_EINVALID_ARG, before they launch anything, for a non-positive shape or a NULL tensor they would touch. */
 int rcgan_bn_infer_bwd(rcgan_ctx* ctx, int rows, int c, int dtype, const void* y, const void* dy, const float* gamma,
                        const float* moving_var, float eps, int act, void* dx, int accumulate);
 
@@ -428,6 +430,8 @@ int rcgan_rng_fill(rcgan_ctx* ctx, size_t count, int dtype, int kind, float lo, 
                    void* state, void* y);
 
 /* ---- discriminator head + losses -------------------------------------------------------------------- */
+/* Every entry point of this section returns RCGAN_EINVALID_ARG, before it launches anything, for a non-positive dimension or a
+ * NULL tensor it would read or write (the optional ones are named at each call). */
 /* feat[n][c] = mean_hw(relu(x)) (gan_resnet.py:405-407; act = RCGAN_ACT_NONE gives the plain spatial
  * mean of mnist/model.py:679) and its adjoint. */
 int rcgan_act_meanhw_fwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int act, const void* x, float* feat);
@@ -437,24 +441,30 @@ int rcgan_act_meanhw_bwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int ac
 int rcgan_gather_rows(rcgan_ctx* ctx, int n, int d, const float* table, const int32_t* idx, float* out);
 int rcgan_scatter_add_rows(rcgan_ctx* ctx, int n, int d, int v, const float* src, const int32_t* idx,
                            float* table_grad, int accumulate);
-/* logit[n] = psi[n] + <feat[n,:], emb[n,:]>  (gan_resnet.py:588,763; mnist/model.py:685) + adjoint. */
+/* logit[n] = psi[n] + <feat[n,:], emb[n,:]>  (gan_resnet.py:588,763; mnist/model.py:685) + adjoint.  psi may be NULL (no offset).
+ * Adjoint: dfeat (= or += by acc_feat) dlogit * emb, dpsi = dlogit, demb = dlogit * feat; each of the three may be NULL (skipped);
+ * emb is read only for dfeat, feat only for demb. */
 int rcgan_proj_logit_fwd(rcgan_ctx* ctx, int n, int d, const float* feat, const float* psi, const float* emb,
                          float* logit);
 int rcgan_proj_logit_bwd(rcgan_ctx* ctx, int n, int d, const float* feat, const float* emb, const float* dlogit,
                          float* dfeat, float* dpsi, float* demb, int acc_feat);
 /* logits[n][v] = psi[n] + <feat[n,:], E[v,:]> for every label v (rcgan-u: gan_resnet.py:654-660, 737-740;
  * the reference re-runs the projection for all 10 labels -- features are computed once here) + adjoint.  No bound on v: a wavefront
- * per logit, a thread per output of the adjoint (v <= 1024 in the models). */
+ * per logit, a thread per output of the adjoint (v <= 1024 in the models).  psi and all three outputs of the adjoint (dfeat = or += by
+ * acc_feat; dpsi, dE written) are required. */
 int rcgan_proj_logit_all_fwd(rcgan_ctx* ctx, int n, int d, int v, const float* feat, const float* psi,
                              const float* E, float* logits);
 int rcgan_proj_logit_all_bwd(rcgan_ctx* ctx, int n, int d, int v, const float* feat, const float* E,
                              const float* dlogits, float* dfeat, float* dpsi, float* dE, int acc_feat);
 /* Loss terms.  Each adds weight*L to *loss_acc (device scalar) and WRITES dlogit = weight * dL/dlogit.
  *   kind HINGE_REAL: mean relu(1-x)   HINGE_FAKE: mean relu(1+x)   NEG_MEAN: -mean x  (gan_resnet.py:604-605,773)
- *   CE_ONES / CE_ZEROS: mean sigmoid_ce(x, 1|0) (mnist/model.py:139-145)
+ *   CE_ONES / CE_ZEROS: mean sigmoid_ce(x, 1|0) (mnist/model.py:139-145).  Their gradients are evaluated as -1 / (1 + e^x) (in the form
+ *   -e^-x / (1 + e^-x) for x > 0, which shares the forward value's exponential) and 1 / (1 + e^-x), never as sigmoid(x) - 1: they keep their relative precision for saturated logits (as do those of
+ *   rcgan_bce_onehot_fwd_bwd and rcgan_proj_head_fwd_bwd, which share the term)
  * x: [rows][cols]; optional row weights wts[rows][cols] turn the inner mean into
  * mean_rows( sum_cols( term * wts ) )  (unbiased :647, rcgan-u :684,759; mnist/model.py:201-204);
- * dwts (may be NULL) receives weight * dL/dwts (needed for the learned confusion matrix).  One workgroup: any rows x cols
+ * dwts (may be NULL) receives weight * dL/dwts (needed for the learned confusion matrix); wts, loss_acc and dlogit may be NULL too
+ * (no weights; no value; evaluation).  One workgroup: any rows x cols
  * (the [B, K] weight rows of the K-class models included). */
 #define RCGAN_LOSS_HINGE_REAL 0
 #define RCGAN_LOSS_HINGE_FAKE 1
@@ -544,7 +554,7 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
                             float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
                             float* db_e, void* ws, size_t ws_bytes);
 int rcgan_head_flush(rcgan_ctx* ctx);
-/* (bce_onehot: one workgroup, any rows x cols, labels in [0, cols).) */
+/* (bce_onehot: one workgroup, any rows x cols, labels in [0, cols); loss_acc and dx may be NULL.) */
 int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x, const int32_t* labels,
                              float weight, float* loss_acc, float* dx);
 /* recover_labels objective (mnist/model.py:533-537): gen [r*ydim, pix] = one generated image per (real sample r, label y),

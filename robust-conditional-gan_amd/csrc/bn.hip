@@ -1363,6 +1363,8 @@ int rcgan_bn_bwd2(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_label
 
 int rcgan_bn_infer(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, const float* gamma, const float* beta,
                    const float* mm, const float* mv, float eps, int act, void* y) {
+  RC_REQUIRE(ctx, rows >= 1 && c >= 1, "bad shape: %d rows x %d channels", rows, c);
+  RC_REQUIRE(ctx, x && gamma && beta && mm && mv && y, "null tensor");
   long total = (long)rows * c;
   RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_kernel<T>, dim3(bn_apply_grid(total, 0)), dim3(256), 0, ctx->stream, total, c,
                                                    (const T*)x, gamma, beta, mm, mv, eps, act, (T*)y));
@@ -1372,8 +1374,10 @@ int rcgan_bn_infer(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, co
 
 int rcgan_bn_infer_bwd(rcgan_ctx* ctx, int rows, int c, int dtype, const void* y, const void* dy, const float* gamma,
                        const float* mv, float eps, int act, void* dx, int accumulate) {
-  RC_REQUIRE(ctx, act == RCGAN_ACT_NONE || act == RCGAN_ACT_RELU || act == RCGAN_ACT_TANH || act == RCGAN_ACT_SIGMOID,
-             "activation %d has no output-side derivative", act);
+  // (every activation's derivative is taken from the OUTPUT: leaky ReLU keeps the sign, so y > 0 <=> x > 0 as for ReLU)
+  RC_REQUIRE(ctx, act >= RCGAN_ACT_NONE && act <= RCGAN_ACT_SIGMOID, "activation %d", act);
+  RC_REQUIRE(ctx, rows >= 1 && c >= 1, "bad shape: %d rows x %d channels", rows, c);
+  RC_REQUIRE(ctx, dy && gamma && mv && dx && (y || act == RCGAN_ACT_NONE), "null tensor");
   long total = (long)rows * c;
   RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_bwd_kernel<T>, dim3(bn_apply_grid(total, 0)), dim3(256), 0, ctx->stream, total, c,
                                                    (const T*)y, (const T*)dy, gamma, mv, eps, act, (T*)dx, accumulate));

@@ -109,12 +109,17 @@ __global__ void proj_all_bwd_kernel(int n, int d, int v, const float* feat, cons
   }
 }
 
+// The sigmoid cross-entropy derivatives are written without a difference of numbers near 1: d/dx of CE(x, 1) = sigmoid(x) - 1 =
+// -1 / (1 + e^x), evaluated with the e = e^-|x| the softplus term needs anyway as -e / (1 + e) for x > 0 and -1 / (1 + e) otherwise
+// (what autodiff of the reference's relu(x) - x z + log1p(exp(-|x|)) gives; the same denominator as the subtracted form, so
+// unsaturated logits keep their values to the last bits), and d/dx of CE(x, 0) = 1 / (1 + e^-x): both keep their relative precision
+// for a saturated logit (sigmoid(x) - 1 in fp32 has lost 0.9 % at x = 12 and is exactly 0 from x = 17 up).
 __device__ __forceinline__ void loss_term(int kind, float x, float* t, float* d) {
   switch (kind) {
     case RCGAN_LOSS_HINGE_REAL: { float z = 1.f - x; *t = z > 0.f ? z : 0.f; *d = z > 0.f ? -1.f : 0.f; break; }
     case RCGAN_LOSS_HINGE_FAKE: { float z = 1.f + x; *t = z > 0.f ? z : 0.f; *d = z > 0.f ? 1.f : 0.f; break; }
     case RCGAN_LOSS_NEG_MEAN: *t = -x; *d = -1.f; break;
-    case RCGAN_LOSS_CE_ONES: { float sp = log1pf(expf(-fabsf(x))); *t = fmaxf(x, 0.f) - x + sp; *d = 1.f / (1.f + expf(-x)) - 1.f; break; }
+    case RCGAN_LOSS_CE_ONES: { float e = expf(-fabsf(x)); *t = fmaxf(x, 0.f) - x + log1pf(e); *d = -(x > 0.f ? e : 1.f) / (1.f + e); break; }
     default: { float sp = log1pf(expf(-fabsf(x))); *t = fmaxf(x, 0.f) + sp; *d = 1.f / (1.f + expf(-x)); break; }
   }
 }
@@ -153,8 +158,9 @@ __global__ __launch_bounds__(256) void bce_onehot_kernel(int rows, int cols, con
     int r = (int)(i / cols), cidx = (int)(i % cols);
     float z = labels[r] == cidx ? 1.f : 0.f;
     float v = x[i];
-    acc += (fmaxf(v, 0.f) - v * z + log1pf(expf(-fabsf(v)))) * inv_all;
-    if (dx) dx[i] = gw * (1.f / (1.f + expf(-v)) - z) * inv_all;
+    const float e = expf(-fabsf(v));
+    acc += (fmaxf(v, 0.f) - v * z + log1pf(e)) * inv_all;
+    if (dx) dx[i] = gw * (z != 0.f ? -(v > 0.f ? e : 1.f) / (1.f + e) : 1.f / (1.f + expf(-v))) * inv_all;      // (no cancellation: loss_term)
   }
   acc = block_sum256(acc, red);
   if (threadIdx.x == 0 && loss_acc) *loss_acc += weight * acc;
@@ -163,22 +169,35 @@ __global__ __launch_bounds__(256) void bce_onehot_kernel(int rows, int cols, con
 __global__ void softmax_rows_fwd_kernel(int rows, int cols, const float* l, float* p) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
+  l += (long)r * cols;
+  p += (long)r * cols;
   float m = -INFINITY;
-  for (int j = 0; j < cols; ++j) m = fmaxf(m, l[r * cols + j]);
+  for (int j = 0; j < cols; ++j) m = fmaxf(m, l[j]);
   float s = 0.f;
-  for (int j = 0; j < cols; ++j) s += expf(l[r * cols + j] - m);
-  for (int j = 0; j < cols; ++j) p[r * cols + j] = expf(l[r * cols + j] - m) / s;
+  for (int j = 0; j < cols; ++j) s += expf(l[j] - m);
+  for (int j = 0; j < cols; ++j) p[j] = expf(l[j] - m) / s;
 }
 
 __global__ void softmax_rows_bwd_kernel(int rows, int cols, const float* p, const float* dp, float* dl, int accumulate) {
   int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= rows) return;
-  float dot = 0.f;
-  for (int j = 0; j < cols; ++j) dot += dp[r * cols + j] * p[r * cols + j];
+  p += (long)r * cols;
+  dp += (long)r * cols;
+  dl += (long)r * cols;
+  // dp[j] - dot cancels wherever dp[j] is close to the row's p-weighted mean -- always at the dominant entry of a saturated row (p = 1
+  // in fp32, dp[j] - dot = minus the other entries' e-20-sized share).  The products are exact in fp64; their sum is kept as hi + lo by
+  // an error-free two-sum, so the difference keeps fp32 relative precision per element.  A few KB of work per call.
+  double hi = 0.0, lo = 0.0;
   for (int j = 0; j < cols; ++j) {
-    float v = p[r * cols + j] * (dp[r * cols + j] - dot);
-    if (accumulate) v += dl[r * cols + j];
-    dl[r * cols + j] = v;
+    const double a = (double)dp[j] * (double)p[j];
+    const double t = hi + a, b = t - hi;
+    lo += (hi - (t - b)) + (a - b);
+    hi = t;
+  }
+  for (int j = 0; j < cols; ++j) {
+    float v = (float)((double)p[j] * (((double)dp[j] - hi) - lo));
+    if (accumulate) v += dl[j];
+    dl[j] = v;
   }
 }
 
@@ -599,9 +618,15 @@ __global__ __launch_bounds__(256) void recover_sum_kernel(int n, const float* te
   if (threadIdx.x == 0) *loss = s;
 }
 
+// What the unfused head / loss entry points refuse before they launch anything: a non-positive dimension, a NULL tensor they would touch.
+#define HL_SHAPE(ctx, ok, ...) RC_REQUIRE(ctx, ok, "bad shape: " __VA_ARGS__)
+#define HL_TENSORS(ctx, ok) RC_REQUIRE(ctx, ok, "null tensor")
+
 extern "C" {
 
 int rcgan_act_meanhw_fwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int act, const void* x, float* feat) {
+  HL_SHAPE(ctx, n >= 1 && n <= 65535 && hw >= 1 && c >= 1, "n %d (1 .. 65535) hw %d c %d", n, hw, c);
+  HL_TENSORS(ctx, x && feat);
   dim3 grid(cdiv(c, 64), n);
   RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(act_meanhw_fwd_kernel<T>, grid, dim3(256), 0, ctx->stream, hw, c, act, (const T*)x, feat));
   RC_LAUNCH_CHECK(ctx);
@@ -609,6 +634,8 @@ int rcgan_act_meanhw_fwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int ac
 }
 
 int rcgan_act_meanhw_bwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int act, const void* x, const float* dfeat, void* dx) {
+  HL_SHAPE(ctx, n >= 1 && hw >= 1 && c >= 1, "n %d hw %d c %d", n, hw, c);
+  HL_TENSORS(ctx, x && dfeat && dx);
   long total = (long)n * hw * c;
   RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(act_meanhw_bwd_kernel<T>, dim3(g1(total)), dim3(256), 0, ctx->stream, total, hw, c, act, (const T*)x, dfeat, (T*)dx));
   RC_LAUNCH_CHECK(ctx);
@@ -616,18 +643,24 @@ int rcgan_act_meanhw_bwd(rcgan_ctx* ctx, int n, int hw, int c, int dtype, int ac
 }
 
 int rcgan_gather_rows(rcgan_ctx* ctx, int n, int d, const float* table, const int32_t* idx, float* out) {
+  HL_SHAPE(ctx, n >= 1 && d >= 1, "n %d d %d", n, d);
+  HL_TENSORS(ctx, table && idx && out);
   hipLaunchKernelGGL(gather_rows_kernel, dim3(g1((long)n * d)), dim3(256), 0, ctx->stream, n, d, table, idx, out);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }
 
 int rcgan_scatter_add_rows(rcgan_ctx* ctx, int n, int d, int v, const float* src, const int32_t* idx, float* tg, int accumulate) {
+  HL_SHAPE(ctx, n >= 1 && d >= 1 && v >= 1, "n %d d %d v %d", n, d, v);
+  HL_TENSORS(ctx, src && idx && tg);
   hipLaunchKernelGGL(scatter_add_rows_kernel, dim3(g1((long)v * d)), dim3(256), 0, ctx->stream, n, d, v, src, idx, tg, accumulate);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }
 
 int rcgan_proj_logit_fwd(rcgan_ctx* ctx, int n, int d, const float* feat, const float* psi, const float* emb, float* logit) {
+  HL_SHAPE(ctx, n >= 1 && d >= 1, "n %d d %d", n, d);
+  HL_TENSORS(ctx, feat && emb && logit);          // (psi may be NULL)
   hipLaunchKernelGGL(proj_logit_fwd_kernel, dim3(cdiv(n, 4)), dim3(256), 0, ctx->stream, n, d, feat, psi, emb, logit);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
@@ -635,12 +668,16 @@ int rcgan_proj_logit_fwd(rcgan_ctx* ctx, int n, int d, const float* feat, const 
 
 int rcgan_proj_logit_bwd(rcgan_ctx* ctx, int n, int d, const float* feat, const float* emb, const float* dlogit, float* dfeat,
                          float* dpsi, float* demb, int acc_feat) {
+  HL_SHAPE(ctx, n >= 1 && d >= 1, "n %d d %d", n, d);
+  HL_TENSORS(ctx, dlogit && (emb || !dfeat) && (feat || !demb));
   hipLaunchKernelGGL(proj_logit_bwd_kernel, dim3(g1((long)n * d)), dim3(256), 0, ctx->stream, n, d, feat, emb, dlogit, dfeat, dpsi, demb, acc_feat);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }
 
 int rcgan_proj_logit_all_fwd(rcgan_ctx* ctx, int n, int d, int v, const float* feat, const float* psi, const float* E, float* logits) {
+  HL_SHAPE(ctx, n >= 1 && d >= 1 && v >= 1, "n %d d %d v %d", n, d, v);
+  HL_TENSORS(ctx, feat && psi && E && logits);
   hipLaunchKernelGGL(proj_all_fwd_kernel, dim3(cdiv((long)n * v, 4)), dim3(256), 0, ctx->stream, n, d, v, feat, psi, E, logits);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
@@ -648,6 +685,8 @@ int rcgan_proj_logit_all_fwd(rcgan_ctx* ctx, int n, int d, int v, const float* f
 
 int rcgan_proj_logit_all_bwd(rcgan_ctx* ctx, int n, int d, int v, const float* feat, const float* E, const float* dlogits,
                              float* dfeat, float* dpsi, float* dE, int acc_feat) {
+  HL_SHAPE(ctx, n >= 1 && d >= 1 && v >= 1, "n %d d %d v %d", n, d, v);
+  HL_TENSORS(ctx, feat && E && dlogits && dfeat && dpsi && dE);
   long total = (long)n * d + (long)v * d + n;
   hipLaunchKernelGGL(proj_all_bwd_kernel, dim3(g1(total)), dim3(256), 0, ctx->stream, n, d, v, feat, E, dlogits, dfeat, dpsi, dE, acc_feat);
   RC_LAUNCH_CHECK(ctx);
@@ -657,6 +696,8 @@ int rcgan_proj_logit_all_bwd(rcgan_ctx* ctx, int n, int d, int v, const float* f
 int rcgan_loss_fwd_bwd(rcgan_ctx* ctx, int kind, int rows, int cols, const float* x, const float* wts, float weight,
                        float* loss_acc, float* dlogit, float* dwts) {
   RC_REQUIRE(ctx, kind >= 0 && kind <= RCGAN_LOSS_CE_ZEROS, "kind %d", kind);
+  HL_SHAPE(ctx, rows >= 1 && cols >= 1, "rows %d cols %d", rows, cols);
+  HL_TENSORS(ctx, x != nullptr);
   hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, ctx->stream, kind, rows, cols, x, wts, weight, loss_acc, dlogit, dwts, ctx->gscale_host,
                      ctx->gscale_dev);
   RC_LAUNCH_CHECK(ctx);
@@ -837,6 +878,8 @@ int rcgan_head_flush(rcgan_ctx* ctx) {
 
 int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x, const int32_t* labels, float weight,
                              float* loss_acc, float* dx) {
+  HL_SHAPE(ctx, rows >= 1 && cols >= 1, "rows %d cols %d", rows, cols);
+  HL_TENSORS(ctx, x && labels);
   hipLaunchKernelGGL(bce_onehot_kernel, dim3(1), dim3(256), 0, ctx->stream, rows, cols, x, labels, weight, loss_acc, dx, ctx->gscale_host,
                      ctx->gscale_dev);
   RC_LAUNCH_CHECK(ctx);
@@ -844,12 +887,16 @@ int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x,
 }
 
 int rcgan_softmax_rows_fwd(rcgan_ctx* ctx, int rows, int cols, const float* l, float* p) {
+  HL_SHAPE(ctx, rows >= 1 && cols >= 1, "rows %d cols %d", rows, cols);
+  HL_TENSORS(ctx, l && p);
   hipLaunchKernelGGL(softmax_rows_fwd_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, ctx->stream, rows, cols, l, p);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }
 
 int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, const float* dp, float* dl, int accumulate) {
+  HL_SHAPE(ctx, rows >= 1 && cols >= 1, "rows %d cols %d", rows, cols);
+  HL_TENSORS(ctx, p && dp && dl);
   hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, ctx->stream, rows, cols, p, dp, dl, accumulate);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;

@@ -98,6 +98,8 @@ Why each case reaches its route (line numbers: robust-conditional-gan_amd/csrc a
   inference                              test_batch_norm_infer                             rcgan_bn_infer
   head                                   HEAD_CASES n = 12 and n = 16; pooled (16,8,64,    rcgan_proj_head_fwd_bwd; v = 17 > HEAD_MAX_V -> head_wide
                                          128); test_head_and_losses; v = 17                (loss.hip:783)
+  unfused head, losses, softmax rows,    tests/test_gpu_head_loss_edges.py (runs guarded   the C entry points of loss.hip outside the fused head and
+  inference batch norm and its adjoint   itself: its own module fixtures and case lists)   rcgan_bn_infer / rcgan_bn_infer_bwd, called directly
 
 fp32, bf16 and fp16 contexts; the chip-filling convolution cases and the grouped filter gradients (bf16 descriptors) run on bf16 only, the
 head cases that are fp32 whatever the activation type on the fp32 context only.
