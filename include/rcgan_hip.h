@@ -581,6 +581,20 @@ int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, c
 size_t rcgan_softmax_xent_workspace_bytes(int rows);
 int rcgan_softmax_xent_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* logits, const int32_t* labels, float weight,
                                float* loss_acc, float* n_correct_acc, float* dlogits, void* ws, size_t ws_bytes);
+/* Forward-corrected cross-entropy for NOISY labels (Patrini et al. 2017), the same launch shape, workspace and determinism:
+ *   *loss_acc      += weight * mean_rows(-log((softmax(logits) . C)[label]))
+ *   *n_correct_acc += the number of rows whose arg-max (lowest index on ties) equals the (noisy) label          (may be NULL)
+ *   posterior[r][y] = softmax(logits[r])[y] * C[y][label_r] / (softmax(logits[r]) . C)[label_r]    [rows, cols] (may be NULL)
+ *   recovered[r]    = arg-max_y posterior[r][y], lowest index on ties                              [rows] int32 (may be NULL)
+ *   dlogits         = weight * (softmax - posterior) / rows, times the scale of rcgan_set_grad_scale            (may be NULL)
+ * ct: [cols, cols] fp32, the TRANSPOSE of the confusion matrix: ct[noisy][clean] = C[clean][noisy] = P(noisy | clean).  Max-subtracted
+ * twice (over the row, and over the support of ct[label]), so nothing underflows to log 0; with C = I every output that
+ * rcgan_softmax_xent_fwd_bwd has is that entry's, bit for bit, for in-range labels.  A row whose label is outside [0, cols) or whose
+ * ct row has no positive entry contributes nothing to the loss (still divided by ALL rows) and gets a zero gradient row, a zero
+ * posterior row and recovered = -1. */
+int rcgan_softmax_xent_forward_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* logits, const int32_t* labels, const float* ct,
+                                       float weight, float* loss_acc, float* n_correct_acc, float* dlogits, float* posterior,
+                                       int32_t* recovered, void* ws, size_t ws_bytes);
 /* The option-A shortcut of the classifier's down-sampling blocks as one launch each way: y[n, h/2, w/2, 2c] = the 2x2 mean of
  * x[n, h, w, c] in channels [c/2, c/2 + c), zeros elsewhere -- the bits of rcgan_meanpool2_fwd followed by rcgan_pad_channels
  * without the intermediate tensor.  Backward: dx (=|+=) the middle channels of dy, a quarter to each of the four pixels.

@@ -23,7 +23,7 @@ F32_PRECISION_HIGHEST, F32_PRECISION_HIGH = 0, 1     # rcgan_set_f32_matmul_prec
 F32_PRECISIONS = {"highest": F32_PRECISION_HIGHEST, "high": F32_PRECISION_HIGH}
 
 RCGAN_EHIP, RCGAN_ERCCL = -4, -5
-EINVALID_ARG, EUNSUPPORTED_SHAPE = -1, -2
+EINVALID_ARG, EUNSUPPORTED_SHAPE, EWORKSPACE_TOO_SMALL = -1, -2, -3
 ERRORS = {-1: "RCGAN_EINVALID_ARG", -2: "RCGAN_EUNSUPPORTED_SHAPE", -3: "RCGAN_EWORKSPACE_TOO_SMALL",
           -4: "RCGAN_EHIP", -5: "RCGAN_ERCCL"}
 
@@ -225,6 +225,7 @@ SIGNATURES = {
     "rcgan_softmax_rows_bwd": (I, [P, I, I, P, P, P, I]),
     "rcgan_softmax_xent_workspace_bytes": (SZ, [I]),
     "rcgan_softmax_xent_fwd_bwd": (I, [P, I, I, P, P, F, P, P, P, P, SZ]),
+    "rcgan_softmax_xent_forward_fwd_bwd": (I, [P, I, I, P, P, P, F, P, P, P, P, P, P, SZ]),
     "rcgan_shortcut_a_fwd": (I, [P, I, I, I, I, I, P, P]),
     "rcgan_shortcut_a_bwd": (I, [P, I, I, I, I, I, P, P, I]),
     "rcgan_diffaugment_fwd": (I, [P, I, I, I, I, I, P, P, P, P]),

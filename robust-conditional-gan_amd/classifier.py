@@ -15,6 +15,7 @@ import torch
 
 from . import _lib as L
 from . import ops as O
+from .data import check_confusion_matrix
 from .eval_cifar import BLOCKS, BN_EPS, STAGES, check_images, classifier_logits
 from .runtime import Context, ParamGroup, check_f32_matmul_precision
 
@@ -61,7 +62,10 @@ N_DECAYED = 32      # the first variables of create_classifier_variables: 31 fil
 
 class LabelClassifierTrainer:
     def __init__(self, n_classes, batch_size=128, momentum=0.9, weight_decay=1e-4, nesterov=False, pad=4, device=0, seed=0,
-                 use_graphs=True, variables=None, f32_matmul_precision="highest", arena_bytes=6 << 30):
+                 use_graphs=True, variables=None, f32_matmul_precision="highest", arena_bytes=6 << 30, confusion_matrix=None):
+        """confusion_matrix: None trains on the labels as they are (sparse softmax cross-entropy).  A [K,K] row-stochastic matrix
+        C[clean, noisy] declares the labels NOISY: the step then uses the forward-corrected loss -log((softmax(z) . C)[label]) (Patrini
+        et al. 2017), under which the soft-max estimates the CLEAN posterior, and ``recover_labels`` becomes available."""
         self.f32_matmul_precision = check_f32_matmul_precision(f32_matmul_precision, "f32")
         specs = variables if variables is not None else create_classifier_variables(seed, n_classes)
         shapes = {n: tuple(s) for n, s, _ in specs}
@@ -87,6 +91,11 @@ class LabelClassifierTrainer:
         with torch.cuda.stream(ctx.stream):
             self.hyper = torch.zeros(2, dtype=torch.float32, device=ctx.device)      # {lr, step}: the update reads lr
         self.loss_acc, self.n_correct = self.P.scalar(0), self.P.scalar(1)
+        # the transposed confusion matrix (ct[noisy, clean]: the layout the loss kernel reads) in a buffer a captured step keeps addressing
+        self.ct = self.confusion_matrix = None
+        if confusion_matrix is not None:
+            self.ct = ctx.persistent((self.K, self.K), L.F32, fill=0.0)
+            self.set_confusion_matrix(confusion_matrix)
         self.images = self.labels_all = None
         self.n_images = 0
         self.rs = np.random.RandomState(seed + 1)                # the draws of the input pipeline
@@ -94,6 +103,15 @@ class LabelClassifierTrainer:
         self.steps = 0
         self._graph, self._rehearsed = None, False
         ctx.sync()
+
+    def set_confusion_matrix(self, C_matrix):
+        """Overwrite the confusion matrix in place (validated on the host: entries >= 0, rows summing to 1 within 1e-6); a captured step
+        reads the new one from its next launch on.  Only for a trainer that was built with one."""
+        if self.ct is None:
+            raise RuntimeError("this trainer was built without a confusion matrix (plain cross-entropy)")
+        Cm = check_confusion_matrix(C_matrix, self.K)
+        self.ctx.upload(np.ascontiguousarray(Cm.T), L.F32, out=self.ct)
+        self.confusion_matrix = Cm
 
     # ------------------------------------------------------------------------------------ data
     def load_data(self, images_chw_u8, labels):
@@ -139,7 +157,10 @@ class LabelClassifierTrainer:
                                               C.c_void_p(self.draws.ptr), C.c_void_p(self.draws.ptr + 4 * B), self.pad, L.F32,
                                               C.c_void_p(self.x.ptr), C.c_void_p(self.labels.ptr)))
         logits = classifier_logits(ctx, self.w, self.x)
-        O.softmax_xent(ctx, logits, self.labels, 1.0, self.loss_acc, self.n_correct)
+        if self.ct is None:
+            O.softmax_xent(ctx, logits, self.labels, 1.0, self.loss_acc, self.n_correct)
+        else:
+            O.softmax_xent_forward(ctx, logits, self.labels, self.ct, 1.0, self.loss_acc, self.n_correct)
         ctx.backward()
         ctx.check(ctx.lib.rcgan_sgd_momentum(ctx.h, self.P.count, self.decay_count, self.P.value.data_ptr(), self.P.grad.data_ptr(),
                                              self.P.m.data_ptr(), self.hyper.data_ptr(), self.momentum, self.weight_decay,
@@ -208,6 +229,33 @@ class LabelClassifierTrainer:
             ctx.recording = rec
         p = np.concatenate(out, axis=0)
         return float((np.argmax(p, axis=1) == np.asarray(labels)).mean()), p
+
+    def recover_labels(self, images, noisy_labels, batch=1000):
+        """Label recovery: the posterior over the CLEAN label of each image given its noisy one, post[y] ~ softmax(z)[y] C[y, noisy], and
+        its arg-max (lowest index on ties) -> (recovered [n] int32, posterior [n,K] fp32).  Images as ``evaluate`` takes them, under the
+        same protocol: ``batch`` at a time, each batch on its own batch-norm moments, recording off.  A label outside [0, K), or one no
+        class can emit under C, gives recovered = -1 and a zero posterior row."""
+        if self.ct is None:
+            raise RuntimeError("recover_labels needs the confusion matrix the trainer was built with")
+        ctx = self.ctx
+        x = check_images(images)
+        noisy = np.ascontiguousarray(np.asarray(noisy_labels).reshape(-1).astype(np.int32))
+        if len(noisy) != len(x):
+            raise ValueError("%d labels for %d images" % (len(noisy), len(x)))
+        rec_out, post_out = [], []
+        rec, ctx.recording = ctx.recording, False
+        try:
+            for lo in range(0, len(x), batch):
+                ctx.new_step()
+                n = len(x[lo:lo + batch])
+                logits = classifier_logits(ctx, self.w, ctx.upload(x[lo:lo + batch], L.F32))
+                post, got = ctx.empty((n, self.K), L.F32), ctx.empty((n,), "i32")
+                O.softmax_xent_forward(ctx, logits, ctx.upload(noisy[lo:lo + batch]), self.ct, 1.0, None, None, post, got)
+                rec_out.append(ctx.download(got).copy())
+                post_out.append(ctx.download(post).copy())
+        finally:
+            ctx.recording = rec
+        return np.concatenate(rec_out, axis=0), np.concatenate(post_out, axis=0)
 
     # ------------------------------------------------------------------------------------ io
     def state_dict(self):

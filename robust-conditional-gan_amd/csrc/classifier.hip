@@ -89,6 +89,122 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(int rows, int cols, c
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// forward-corrected cross-entropy (Patrini et al. 2017) on noisy labels: L = -log((softmax(z) . C)[noisy]); same skeleton as above.
+// ct[noisy][y] = C[y][noisy], so the lanes of a row read one contiguous row of ct.  With m = max z, s = sum exp(z - m), and over the
+// SUPPORT { y : ct[noisy][y] > 0 }  m2 = max z, a = sum ct exp(z - m2)  (its largest term is ct at the arg-max: a > 0, no log 0):
+//   loss row = (m + logf(s)) - (m2 + logf(a)),   post = ct exp(z - m2) / a,   dlogits = gw (exp(z - m) / s - post).
+// C = I: m2 = z[label], a = 1, logf(a) = 0, post = onehot -- the arithmetic of softmax_xent_kernel, operation for operation.
+// A row whose label is outside [0, cols) or whose ct row has no positive entry: no loss, zero gradient and posterior rows, recovered -1.
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void softmax_xent_forward_kernel(int rows, int cols, const float* __restrict__ logits,
+                                                                    const int32_t* __restrict__ labels, const float* __restrict__ ct, float weight,
+                                                                    float* loss_acc, float* n_correct_acc, float* __restrict__ dlogits,
+                                                                    float* __restrict__ posterior, int32_t* __restrict__ recovered, float gs_host,
+                                                                    const float* gs_dev, float* partials, unsigned* counter) {
+  __shared__ float red_l[4], red_c[4], red[4];
+  __shared__ int is_last;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float inv_rows = 1.f / (float)rows;
+  const float gw = dlogits ? weight * xent_grad_scale(gs_host, gs_dev) * inv_rows : 0.f;
+  float lsum = 0.f, csum = 0.f;
+  for (long r = (long)blockIdx.x * 4 + wave; r < rows; r += (long)gridDim.x * 4) {
+    const float* x = logits + r * cols;
+    const int lab = labels[r];
+    const bool lab_ok = (unsigned)lab < (unsigned)cols;
+    const float* crow = ct + (size_t)(lab_ok ? lab : 0) * cols;
+    float v[XENT_PER_LANE], u[XENT_PER_LANE];
+    float m = -INFINITY, m2 = -INFINITY;
+    int mi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < XENT_PER_LANE; ++q) {
+      const int j = q * 64 + lane;
+      v[q] = j < cols ? x[j] : -INFINITY;
+      u[q] = (lab_ok && j < cols) ? crow[j] : 0.f;
+      if (v[q] > m) { m = v[q]; mi = j; }           // strictly greater: the lowest index of this lane's maxima
+      if (u[q] > 0.f && v[q] > m2) m2 = v[q];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float om = __shfl_xor(m, o, 64);
+      const int oi = __shfl_xor(mi, o, 64);
+      if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
+      m2 = fmaxf(m2, __shfl_xor(m2, o, 64));
+    }
+    const bool valid = lab_ok && m2 > -INFINITY;     // (wave-uniform)
+    float s = 0.f, a = 0.f;
+#pragma unroll
+    for (int q = 0; q < XENT_PER_LANE; ++q) {
+      u[q] = (valid && u[q] > 0.f) ? u[q] * expf(v[q] - m2) : 0.f;
+      a += u[q];
+      v[q] = expf(v[q] - m);                       // (-inf - m -> 0 in the columns past the end)
+      s += v[q];
+    }
+    s = wave_sum(s);
+    a = wave_sum(a);
+    if (valid) lsum += (m + logf(s)) - (m2 + logf(a));
+    csum += (lab_ok && mi == lab) ? 1.f : 0.f;
+    const float inv_s = 1.f / s, inv_a = valid ? 1.f / a : 0.f;
+    float pm = -INFINITY;
+    int pi = 0x7fffffff;
+#pragma unroll
+    for (int q = 0; q < XENT_PER_LANE; ++q) {
+      const int j = q * 64 + lane;
+      u[q] = __fmul_rn(u[q], inv_a);                 // the posterior, rounded here whatever the gradient's expression contracts to
+      if (j < cols && u[q] > pm) { pm = u[q]; pi = j; }
+    }
+    if (recovered) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const float om = __shfl_xor(pm, o, 64);
+        const int oi = __shfl_xor(pi, o, 64);
+        if (om > pm || (om == pm && oi < pi)) { pm = om; pi = oi; }
+      }
+      if (lane == 0) recovered[r] = valid ? pi : -1;
+    }
+    if (posterior) {
+      float* p = posterior + r * cols;
+#pragma unroll
+      for (int q = 0; q < XENT_PER_LANE; ++q) {
+        const int j = q * 64 + lane;
+        if (j < cols) p[j] = u[q];
+      }
+    }
+    if (dlogits) {
+      float* d = dlogits + r * cols;
+#pragma unroll
+      for (int q = 0; q < XENT_PER_LANE; ++q) {
+        const int j = q * 64 + lane;
+        if (j < cols) d[j] = valid ? gw * (v[q] * inv_s - u[q]) : 0.f;
+      }
+    }
+  }
+  // ---- the sums over rows: per-workgroup partials, finished in workgroup order by the last workgroup to arrive ----
+  if (lane == 0) { red_l[wave] = lsum; red_c[wave] = csum; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = (red_l[0] + red_l[1]) + (red_l[2] + red_l[3]);
+    partials[gridDim.x + blockIdx.x] = (red_c[0] + red_c[1]) + (red_c[2] + red_c[3]);
+    // release: the two stores above are visible to whoever reads the counter after this increment
+    const unsigned prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
+    is_last = prev == gridDim.x - 1u ? 1 : 0;
+    if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // ready for the next launch
+  }
+  __syncthreads();
+  if (!is_last) return;
+  float tl = 0.f, tc = 0.f;
+  for (unsigned w = threadIdx.x; w < gridDim.x; w += 256) {
+    tl += __hip_atomic_load(partials + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    tc += __hip_atomic_load(partials + gridDim.x + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  tl = block_sum256(tl, red);
+  tc = block_sum256(tc, red);
+  if (threadIdx.x == 0) {
+    if (loss_acc) *loss_acc += weight * (tl * inv_rows);
+    if (n_correct_acc) *n_correct_acc += tc;
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // option-A shortcut: y[n][h/2][w/2][2c] = 2x2 mean of x[n][h][w][c] in channels [c/2, c/2 + c), zeros elsewhere.
 // The mean is formed exactly as meanpool2_fwd_kernel / resample2_vec_kernel form it: (((x00 + x10) + x01) + x11) * 0.25.
 // ---------------------------------------------------------------------------------------------------------
@@ -251,6 +367,21 @@ int rcgan_softmax_xent_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* 
   const int nwg = (int)(need / (2 * sizeof(float)));
   hipLaunchKernelGGL(softmax_xent_kernel, dim3(nwg), dim3(256), 0, ctx->stream, rows, cols, logits, labels, weight, loss_acc, n_correct_acc, dlogits,
                      ctx->gscale_host, ctx->gscale_dev, (float*)ws, ctx->counters() + RC_COUNTER_XENT);
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_softmax_xent_forward_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* logits, const int32_t* labels, const float* ct, float weight,
+                                       float* loss_acc, float* n_correct_acc, float* dlogits, float* posterior, int32_t* recovered, void* ws,
+                                       size_t ws_bytes) {
+  RC_REQUIRE(ctx, rows >= 1 && logits && labels && ct, "bad arguments (rows %d)", rows);
+  if (cols < 2 || cols > XENT_MAX_COLS) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "%d classes (2..%d)", cols, XENT_MAX_COLS);
+  const size_t need = rcgan_softmax_xent_workspace_bytes(rows);
+  if (!ws || ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
+  const int nwg = (int)(need / (2 * sizeof(float)));
+  // (the counter of softmax_xent_kernel: launches of one stream, and each leaves it at zero)
+  hipLaunchKernelGGL(softmax_xent_forward_kernel, dim3(nwg), dim3(256), 0, ctx->stream, rows, cols, logits, labels, ct, weight, loss_acc,
+                     n_correct_acc, dlogits, posterior, recovered, ctx->gscale_host, ctx->gscale_dev, (float*)ws, ctx->counters() + RC_COUNTER_XENT);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }

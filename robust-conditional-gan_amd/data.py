@@ -41,6 +41,56 @@ def corrupt_labels(labels, C, rng=np.random, n_classes=None):
     return labels, labels_random, labels_biased, labels_inv_weights
 
 
+def check_confusion_matrix(C, n_classes=None):
+    """C as a float64 [K,K] row-stochastic matrix (C[y, y~] = P(noisy y~ | clean y)): entries >= 0, rows summing to 1 within 1e-6."""
+    C = np.asarray(C, np.float64)
+    K = int(n_classes) if n_classes is not None else len(C)
+    if C.shape != (K, K):
+        raise ValueError("confusion matrix has shape %s, expected (%d, %d)" % (C.shape, K, K))
+    if not np.isfinite(C).all() or C.min() < 0:
+        raise ValueError("confusion matrix has negative or non-finite entries")
+    if np.abs(C.sum(1) - 1.0).max() > 1e-6:
+        raise ValueError("confusion matrix rows do not sum to 1 (worst %.3e off)" % np.abs(C.sum(1) - 1.0).max())
+    return C
+
+
+def noisy_labels(labels, C, rs):
+    """The noisy channel on a label array, vectorised: one uniform draw per label from ``rs`` (a numpy RandomState), pushed through the
+    inverse CDF of C[label].  An entry of probability zero is never drawn.  (``corrupt_labels`` keeps the reference's draw order for
+    the GAN trainers; this one serves the label classifier, which has no stream to stay compatible with.)"""
+    labels = np.asarray(labels, np.int64)
+    C = check_confusion_matrix(C)
+    if labels.size and (labels.min() < 0 or labels.max() >= len(C)):
+        raise ValueError("labels outside [0, %d)" % len(C))
+    cdf = np.cumsum(C, axis=1)
+    cdf /= cdf[:, -1:]                                   # the last entry exactly 1: a draw u < 1 never runs off the end
+    u = rs.random_sample(labels.shape[0])
+    return (u[:, None] >= cdf[labels]).sum(axis=1).astype(np.int64)
+
+
+def estimate_confusion_anchor(probs, quantile=0.97):
+    """Patrini et al. 2017, eq. 12-13: row i of the estimate is the noisy-label posterior ``probs`` [N,K] at the sample that sits at
+    ``quantile`` of column i (the sample the classifier is surest belongs to class i; a quantile below 1 guards against outliers).
+    quantile = 1.0 takes the arg-max sample, the lowest index on ties.  The rows are the samples' own probabilities, untouched: they
+    sum to 1 as well as ``probs`` does."""
+    probs = np.asarray(probs, np.float64)
+    if probs.ndim != 2 or probs.shape[0] < 1:
+        raise ValueError("probs has shape %s, expected [N, K]" % (probs.shape,))
+    if not 0.0 < quantile <= 1.0:
+        raise ValueError("quantile %r outside (0, 1]" % (quantile,))
+    n, K = probs.shape
+    C = np.zeros((K, K))
+    for i in range(K):
+        if quantile >= 1.0:
+            at = int(np.argmax(probs[:, i]))
+        else:
+            # the sample whose column-i probability is nearest the quantile from below (numpy's "lower" rule), lowest index on ties
+            order = np.argsort(probs[:, i], kind="stable")
+            at = int(order[int(np.floor(quantile * (n - 1)))])
+        C[i] = probs[at]
+    return C
+
+
 def cifar_generator(images, labels, batch_size, C, rng=np.random):
     """cifar10.py:19-45 on in-memory arrays: fixed order, no shuffling, tail dropped.  The class count is C's size."""
     labels, labels_random, labels_biased, labels_inv_weights = corrupt_labels(labels, C, rng)

@@ -1305,6 +1305,22 @@ def softmax_xent(ctx, logits, labels, weight, loss_acc, n_correct=None):
                                                  C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
 
 
+def softmax_xent_forward(ctx, logits, labels, ct, weight, loss_acc, n_correct=None, posterior=None, recovered=None):
+    """The forward-corrected term for noisy labels: weight * reduce_mean(-log((softmax(logits) . C)[label])) added to loss_acc, with
+    ct [K,K] fp32 the TRANSPOSED confusion matrix (ct[noisy, clean] = C[clean, noisy]).  Optional outputs: n_correct as in softmax_xent
+    (against the noisy labels), posterior [rows,K] fp32 = the clean-label posterior given the noisy label, recovered [rows] int32 = its
+    arg-max.  The same contract as softmax_xent: the gradient is written in the same launch, logits must have this term as their only
+    consumer."""
+    r, c = logits.shape
+    if tuple(ct.shape) != (c, c):
+        raise ValueError("ct has shape %s, expected (%d, %d)" % (tuple(ct.shape), c, c))
+    dl = None
+    if logits.req and ctx.recording:
+        dl, _ = grad_of(ctx, logits)
+    ctx.check(ctx.lib.rcgan_softmax_xent_forward_fwd_bwd(ctx.h, r, c, _p(logits), _p(labels), _p(ct), float(weight), _p(loss_acc), _p(n_correct),
+                                                         _p(dl), _p(posterior), _p(recovered), C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
+
+
 def softmax_rows(ctx, logits):
     r, c = logits.shape
     p = ctx.empty((r, c), L.F32)

@@ -3,6 +3,14 @@ that ``train_cifar.py --label_classifier PATH`` scores generated samples with.
 
 Trains on the CLEAN training labels: a classifier trained on the corrupted ones would measure the label noise, not the generator.
 The held-out set is scored under the evaluator's protocol (batches of 1000, every batch norm on the moments of its batch).
+
+With only NOISY labels and a confusion matrix C (``cifar10/run_label_recovery.sh``): ``--loss forward`` trains on them with the
+forward-corrected loss -log((softmax(z) . C)[label]) (Patrini et al. 2017), under which the soft-max estimates the clean posterior, so
+the asset is still a drop-in for ``--label_classifier``; ``--recover_out`` then writes the recovered training labels.  The matrix is
+``known`` (the one-coin matrix of ``--alpha``), a ``.npy`` file (for instance the matrix an RCGAN-U run learned), or ``estimate``:
+a plain cross-entropy stage on the noisy labels, Patrini's anchor estimate from its soft-max over the training set, then the
+forward-corrected run from a fresh initialisation.  ``--alpha`` below 1 corrupts the training labels once (a stand-in for labels
+that arrive noisy); the clean ones are then kept for reporting only.
 """
 import logging
 import os
@@ -34,6 +42,14 @@ def define_flags():
     f.DEFINE_boolean("no_augment", False, "no random translation / mirror")
     f.DEFINE_integer("seed", 0, "seed of the initialisation and of the input pipeline")
     f.DEFINE_string("f32_matmul_precision", 'highest', "fp32 GEMMs [highest: fp32 matrix cores, high: split-bf16 matrix cores]")
+    f.DEFINE_float("alpha", 1.0, "< 1: corrupt the training labels once through the one-coin matrix C_ALPHA(alpha, K); 1.0: clean labels")
+    f.DEFINE_integer("label_seed", 0, "seed of the label corruption")
+    f.DEFINE_string("loss", 'ce', "[ce] sparse softmax cross-entropy, [forward] forward-corrected for noisy labels (needs --confusion_matrix)")
+    f.DEFINE_string("confusion_matrix", None, "with --loss forward: [known] C_ALPHA(alpha, K), [estimate] anchor estimate after a plain "
+                    "cross-entropy stage, or PATH.npy holding a [K,K] matrix C[clean, noisy]")
+    f.DEFINE_integer("estimate_steps", 0, "--confusion_matrix estimate: steps of the plain cross-entropy stage (0: as many as the main run)")
+    f.DEFINE_float("anchor_quantile", 0.97, "--confusion_matrix estimate: the quantile of estimate_confusion_anchor (1.0: the arg-max sample)")
+    f.DEFINE_string("recover_out", None, "with --loss forward: where the recovered training labels (.npz) are written")
     f.DEFINE_string("out", None, "where the weight asset (.npz) is written")
     f.DEFINE_string("log_file", None, "logging file")
     return f
@@ -60,6 +76,43 @@ def lr_at(step, total, lr):
     return lr * (0.01 if 4 * step >= 3 * total else 0.1 if 2 * step >= total else 1.0)
 
 
+def check_noise_flags(FLAGS):
+    """The label-noise flags against each other, before anything is loaded.  -> the matrix source: None, 'known', 'estimate' or a path."""
+    if not 0.0 < FLAGS.alpha <= 1.0:
+        raise ValueError('flag alpha = %r: (0, 1]' % (FLAGS.alpha,))
+    if FLAGS.loss not in ('ce', 'forward'):
+        raise ValueError('flag loss = %r: ce or forward' % (FLAGS.loss,))
+    src = FLAGS.confusion_matrix
+    if FLAGS.loss == 'forward' and src is None:
+        raise ValueError('--loss forward needs --confusion_matrix [known, estimate, PATH.npy]')
+    if FLAGS.loss == 'ce' and src is not None:
+        raise ValueError('--confusion_matrix is read by --loss forward only')
+    if FLAGS.loss == 'ce' and FLAGS.recover_out is not None:
+        raise ValueError('--recover_out needs --loss forward')
+    if src is not None and src not in ('known', 'estimate') and not src.endswith('.npy'):
+        raise ValueError('flag confusion_matrix = %r: known, estimate or PATH.npy' % (src,))
+    if FLAGS.estimate_steps < 0:
+        raise ValueError('flag estimate_steps = %r' % (FLAGS.estimate_steps,))
+    if not 0.0 < FLAGS.anchor_quantile <= 1.0:
+        raise ValueError('flag anchor_quantile = %r: (0, 1]' % (FLAGS.anchor_quantile,))
+    return src
+
+
+def _row_normalised(C):
+    """A matrix that was stored or computed in float32: rows brought to sum 1 in float64 (the trainer asks for 1e-6)."""
+    C = np.asarray(C, np.float64)
+    return C / C.sum(axis=1, keepdims=True)
+
+
+def _in_chunks(fn, images_chw_u8, *rest, chunk=10000):
+    """fn(NHWC images, *rest) over the set ``chunk`` images at a time (a multiple of the evaluation batch): host memory stays small."""
+    outs = []
+    for lo in range(0, len(images_chw_u8), chunk):
+        x = images_chw_u8[lo:lo + chunk].reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
+        outs.append(fn(x, *[r[lo:lo + chunk] for r in rest]))
+    return outs
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     FLAGS = define_flags().parse(argv)
@@ -67,31 +120,78 @@ def main(argv=None):
         raise ValueError('flag log_file is required')
     if FLAGS.out is None:
         raise ValueError('flag out is required')
+    source = check_noise_flags(FLAGS)
     n_classes, data_dir = dataset_setup(FLAGS)
     logging.basicConfig(filename=FLAGS.log_file, level=logging.INFO, format='%(asctime)s %(levelname)-8s %(message)s')
     logging.info('dataset = {} ({} classes)'.format(FLAGS.dataset, n_classes))
     tx, ty, vx, vy = load_clean(FLAGS, n_classes, data_dir)
     held = vx.reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
+    ty_clean = None
+    if FLAGS.alpha < 1.0:
+        # the training labels arrive noisy: corrupted once, the clean ones kept for reporting only (the held-out labels stay clean)
+        ty_clean = ty
+        ty = D.noisy_labels(ty_clean, D.C_ALPHA(FLAGS.alpha, n_classes), np.random.RandomState(FLAGS.label_seed))
+        logging.info('alpha = {}: training labels corrupted (label_seed {}), {:.4f} of them still agree with the clean ones'.format(
+            FLAGS.alpha, FLAGS.label_seed, float((ty == ty_clean).mean())))
     from .classifier import LabelClassifierTrainer
     B = FLAGS.batch_size
-    t = LabelClassifierTrainer(n_classes, batch_size=B, momentum=FLAGS.momentum, weight_decay=FLAGS.weight_decay, nesterov=FLAGS.nesterov,
-                               pad=0 if FLAGS.no_augment else 4, seed=FLAGS.seed, f32_matmul_precision=FLAGS.f32_matmul_precision,
-                               device=int(os.environ.get("LOCAL_RANK", "0")))
-    t.load_data(tx, ty)
     per_epoch = max(len(ty) // B, 1)
     total = FLAGS.max_steps if FLAGS.max_steps > 0 else FLAGS.epochs * per_epoch
     no_flip = np.zeros((B, 3), np.int32) if FLAGS.no_augment else None
-    t0 = time.time()
-    acc = None
-    for step in range(total):
-        t.step(lr_at(step, total, FLAGS.lr), shift_flip=no_flip)
-        if (step + 1) % per_epoch == 0 or step + 1 == total:
-            loss, batch_acc = t.losses()
-            acc, _ = t.evaluate(held, vy)
-            logging.info('epoch {} step {} lr {:g} loss {:.4f} batch accuracy {:.4f} held-out accuracy {:.4f} ({:.0f} s)'.format(
-                (step + 1) // per_epoch, step + 1, lr_at(step, total, FLAGS.lr), loss, batch_acc, acc, time.time() - t0))
+
+    def run(n_steps, confusion_matrix):
+        """A trainer from the flags' initialisation, trained for n_steps on the schedule that spans them.  -> (trainer, held-out accuracy)"""
+        t = LabelClassifierTrainer(n_classes, batch_size=B, momentum=FLAGS.momentum, weight_decay=FLAGS.weight_decay, nesterov=FLAGS.nesterov,
+                                   pad=0 if FLAGS.no_augment else 4, seed=FLAGS.seed, f32_matmul_precision=FLAGS.f32_matmul_precision,
+                                   device=int(os.environ.get("LOCAL_RANK", "0")), confusion_matrix=confusion_matrix)
+        t.load_data(tx, ty)
+        t0 = time.time()
+        acc = None
+        for step in range(n_steps):
+            t.step(lr_at(step, n_steps, FLAGS.lr), shift_flip=no_flip)
+            if (step + 1) % per_epoch == 0 or step + 1 == n_steps:
+                loss, batch_acc = t.losses()
+                acc, _ = t.evaluate(held, vy)
+                logging.info('epoch {} step {} lr {:g} loss {:.4f} batch accuracy {:.4f} held-out accuracy {:.4f} ({:.0f} s)'.format(
+                    (step + 1) // per_epoch, step + 1, lr_at(step, n_steps, FLAGS.lr), loss, batch_acc, acc, time.time() - t0))
+        return t, acc
+
+    Cm = None
+    if source == 'known':
+        Cm = D.C_ALPHA(FLAGS.alpha, n_classes)
+    elif source == 'estimate':
+        n_est = FLAGS.estimate_steps if FLAGS.estimate_steps > 0 else total
+        logging.info('confusion matrix: {} steps of plain cross-entropy on the noisy labels, then the anchor estimate'.format(n_est))
+        t, _ = run(n_est, None)
+        probs = np.concatenate(_in_chunks(lambda x: t.evaluate(x, np.zeros(len(x), np.int64))[1], tx), axis=0)
+        t.close()
+        Cm = _row_normalised(D.estimate_confusion_anchor(probs, FLAGS.anchor_quantile))
+        logging.info('estimated confusion matrix (quantile {:g}): diagonal mean {:.4f}, min {:.4f}'.format(
+            FLAGS.anchor_quantile, float(np.diag(Cm).mean()), float(np.diag(Cm).min())))
+        if ty_clean is not None:
+            logging.info('estimate against C_ALPHA({}): largest entry error {:.4f}'.format(
+                FLAGS.alpha, float(np.abs(Cm - D.C_ALPHA(FLAGS.alpha, n_classes)).max())))
+    elif source is not None:
+        Cm = D.check_confusion_matrix(_row_normalised(np.load(source)), n_classes)
+    if Cm is not None:
+        logging.info('loss = forward, confusion matrix from {}'.format(source))
+    t, acc = run(total, Cm)
     t.save_asset(FLAGS.out)
     logging.info('wrote {} ({} classes, held-out accuracy {})'.format(FLAGS.out, n_classes, acc))
+    if FLAGS.recover_out is not None:
+        parts = _in_chunks(t.recover_labels, tx, ty)
+        y_rec, post = np.concatenate([p[0] for p in parts], axis=0), np.concatenate([p[1] for p in parts], axis=0)
+        fields = dict(y_noisy=np.asarray(ty, np.int64), y_recover=y_rec.astype(np.int64), posterior=post, confusion_matrix=Cm)
+        if ty_clean is not None:
+            fields.update(recovery_accuracy=float((y_rec == ty_clean).mean()), noisy_agreement=float((ty == ty_clean).mean()))
+            logging.info('label recovery accuracy {:.4f} (noisy labels agree with clean: {:.4f})'.format(
+                fields['recovery_accuracy'], fields['noisy_agreement']))
+        else:
+            logging.info('label recovery: {:.4f} of the recovered labels differ from the given ones (no clean labels to score against)'.format(
+                float((y_rec != ty).mean())))
+        with open(FLAGS.recover_out, 'wb') as f:
+            np.savez(f, **fields)
+        logging.info('wrote {}'.format(FLAGS.recover_out))
     t.close()
     return acc
 
