@@ -250,7 +250,9 @@ int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void
  * the discriminator's 8x8 / 16x16 layers are launch-latency-bound one by one.  dbiases[i] may be NULL.
  * ws: rcgan_conv2d_bwd_weight_group_workspace_bytes(n, descs) suffices.  The call splits ws in two halves: the first holds the slabs of
  * the grouped launches, the second serves every layer computed by a call of its own -- a layer whose slabs do not fit the first half is
- * one of those (same values), so any ws of at least twice the largest rcgan_conv_workspace_bytes of the layers is enough to be correct. */
+ * one of those (same values), so any ws of at least twice the largest rcgan_conv_workspace_bytes of the layers is enough to be correct.
+ * The call plans all its launches before the first of them: a failure while planning (a bad descriptor, a shape no kernel takes) returns
+ * with nothing of this call launched. */
 size_t rcgan_conv2d_bwd_weight_group_workspace_bytes(int n, const rcgan_conv_desc* descs);
 int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* descs, const void* const* xs, const void* const* dys,
                                   float* const* dws, float* const* dbiases, int accumulate, void* ws, size_t ws_bytes);

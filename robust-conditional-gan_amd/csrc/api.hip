@@ -1,5 +1,6 @@
-// extern "C" entry points: context, conv / dense dispatch (MFMA vs direct), optimiser, graphs.
-#include "conv_mfma.h"
+// extern "C" entry points: context, graphs, forward / data-gradient convolution and dense dispatch (MFMA vs direct), optimiser.
+// (The filter gradient's entry points: conv_wgrad.hip.)
+#include "conv_wgrad.h"
 #include "small_gemm.h"
 #include "step_inputs.h"
 #include "conv_image.h"
@@ -25,152 +26,6 @@ size_t small_wgrad_ws_bytes(const rcgan_conv_desc* d);
 template <typename T> int small_fwd(rcgan_ctx*, const rcgan_conv_desc*, int, const T*, const float*, const float*, T*);
 template <typename T> int small_dgrad(rcgan_ctx*, const rcgan_conv_desc*, int, const T*, const float*, T*, int);
 template <typename T> int small_wgrad(rcgan_ctx*, const rcgan_conv_desc*, int, const T*, const T*, float*, float*, int, void*, size_t);
-
-// out[i] (= or +=) sum_z slab[z][i]; the slabs may carry a bias-gradient tail of `nbias` floats after `count`
-__global__ void slab_reduce2_kernel(const float* slab, long stride, float* out, long count, float* bias_out, int nbias, int nz,
-                                    int accumulate) {
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count + nbias) return;
-  float s = 0.f;
-#pragma unroll 4
-  for (int z = 0; z < nz; ++z) s += slab[(long)z * stride + i];
-  float* o = i < count ? out + i : bias_out + (i - count);
-  if (accumulate) s += *o;
-  *o = s;
-}
-
-// the same reduction for several filter gradients in one launch (blockIdx.y = problem).  Slabs of the image-end kernels
-// (conv_image.h: [32][Cb] + 32 floats per workgroup) are described by bias_off / orient: the bias sums sit at bias_off instead of
-// behind the filter elements, and with orient 1 (the small side is dy) slab element k*Cb + n goes to dW[(t*Cb + n)*Cs + c],
-// k = t*Cs + c.
-#define REDUCE_GROUP_MAX 16
-struct SlabReduceGroup {
-  struct Item {
-    const float* slab; long stride; float* out; long count; float* bias_out; int nbias, nz, accumulate;
-    long bias_off;          // slab index of the first bias sum (= count for the three-tap / per-tap slabs)
-    int orient, Cb, Cs;     // orient 1: transposed image-end mapping
-    int sub;                // 1 / 2: the slab holds the 16 cells of the sub-pixel form (MfmaWgradArgs::sub), folded into the 9 taps here
-    long cc;                // Cin * Cout (sub only)
-    int bias_parts;         // 2: two bias partials per slab, nbias floats apart (the nine-tap kernel's upsample form); 0 / 1: one
-    int vec4;               // a thread sums FOUR consecutive filter elements with 16-byte loads (count, cc, stride multiples of 4, orient 0)
-  } it[REDUCE_GROUP_MAX];
-};
-__device__ __forceinline__ float4 f4add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-__global__ void slab_reduce2_group_kernel(SlabReduceGroup g) {
-  const SlabReduceGroup::Item& r = g.it[blockIdx.y];
-  long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r.vec4) {
-    // threads [0, count / 4): four elements each, the same per-element order of additions as the scalar form below (bit-identical sums);
-    // threads behind them: the bias tail, one element each, through the scalar form
-    const long nv = r.count >> 2;
-    if (i < nv) {
-      const long e = i << 2;
-      float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (r.sub) {
-        const int tap = (int)(e / r.cc), kh = tap / 3, kw = tap - kh * 3;
-        const long rem = e - (long)tap * r.cc;
-        long c4[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int pa = q >> 1, pb = q & 1;
-          const int sa = ((r.sub == 1) == (pa == 0)) ? (kh >= 1) : (kh >= 2);
-          const int sb = ((r.sub == 1) == (pb == 0)) ? (kw >= 1) : (kw >= 2);
-          c4[q] = (long)(q * 4 + sa * 2 + sb) * r.cc + rem;
-        }
-        int z = 0;
-        for (; z + 2 <= r.nz; z += 2) {
-          float4 v[2][4];
-#pragma unroll
-          for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) v[u][q] = *(const float4*)(r.slab + (long)(z + u) * r.stride + c4[q]);
-#pragma unroll
-          for (int u = 0; u < 2; ++u) s = f4add(s, f4add(f4add(v[u][0], v[u][1]), f4add(v[u][2], v[u][3])));
-        }
-        for (; z < r.nz; ++z) {
-          const float* sl = r.slab + (long)z * r.stride;
-          s = f4add(s, f4add(f4add(*(const float4*)(sl + c4[0]), *(const float4*)(sl + c4[1])), f4add(*(const float4*)(sl + c4[2]), *(const float4*)(sl + c4[3]))));
-        }
-        if (r.sub == 2) { s.x *= 0.25f; s.y *= 0.25f; s.z *= 0.25f; s.w *= 0.25f; }
-      } else {
-        int z = 0;
-        for (; z + 8 <= r.nz; z += 8) {
-          float4 v[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) v[u] = *(const float4*)(r.slab + (long)(z + u) * r.stride + e);
-#pragma unroll
-          for (int u = 0; u < 8; ++u) s = f4add(s, v[u]);
-        }
-#pragma unroll 4
-        for (; z < r.nz; ++z) s = f4add(s, *(const float4*)(r.slab + (long)z * r.stride + e));
-      }
-      float4* o = (float4*)(r.out + e);
-      if (r.accumulate) s = f4add(s, *o);
-      *o = s;
-      return;
-    }
-    i = r.count + (i - nv);       // a bias element (or past the end)
-  }
-  if (i >= r.count + r.nbias) return;
-  const long si = i < r.count ? i : r.bias_off + (i - r.count);
-  float s = 0.f;
-  if (r.sub && i < r.count) {
-    // dW[kh][kw] = scale * sum over the parities (pa, pb) of G[pa][pb][S(pa, kh)][S(pb, kw)]
-    const int tap = (int)(i / r.cc), kh = tap / 3, kw = tap - kh * 3;
-    const long rem = i - (long)tap * r.cc;
-    long c4[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int pa = q >> 1, pb = q & 1;
-      // S(sub 1): parity 0 -> 0,1,1; parity 1 -> 0,0,1.  S(sub 2): the other way round
-      const int sa = ((r.sub == 1) == (pa == 0)) ? (kh >= 1) : (kh >= 2);
-      const int sb = ((r.sub == 1) == (pb == 0)) ? (kw >= 1) : (kw >= 2);
-      c4[q] = (long)(q * 4 + sa * 2 + sb) * r.cc + rem;
-    }
-    // (the loads of four slabs -- sixteen values -- are requested before the first of them is added: the loop is a chain of
-    // memory round trips, not of additions)
-    int z = 0;
-    for (; z + 4 <= r.nz; z += 4) {
-      float v[4][4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[u][q] = r.slab[(long)(z + u) * r.stride + c4[q]];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) s += (v[u][0] + v[u][1]) + (v[u][2] + v[u][3]);
-    }
-    for (; z < r.nz; ++z) {
-      const float* sl = r.slab + (long)z * r.stride;
-      s += (sl[c4[0]] + sl[c4[1]]) + (sl[c4[2]] + sl[c4[3]]);
-    }
-    if (r.sub == 2) s *= 0.25f;
-  } else {
-    int z = 0;
-    for (; z + 16 <= r.nz; z += 16) {
-      float v[16];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) v[u] = r.slab[(long)(z + u) * r.stride + si];
-#pragma unroll
-      for (int u = 0; u < 16; ++u) s += v[u];
-    }
-#pragma unroll 4
-    for (; z < r.nz; ++z) s += r.slab[(long)z * r.stride + si];
-    if (i >= r.count && r.bias_parts == 2) {
-#pragma unroll 4
-      for (z = 0; z < r.nz; ++z) s += r.slab[(long)z * r.stride + si + r.nbias];
-    }
-  }
-  float* o;
-  if (i >= r.count) o = r.bias_out + (i - r.count);
-  else if (r.orient == 0) o = r.out + i;
-  else {
-    const int k = (int)(i / r.Cb), n = (int)(i - (long)k * r.Cb);
-    const int t = k / r.Cs, c = k - t * r.Cs;
-    o = r.out + ((long)t * r.Cb + n) * r.Cs + c;
-  }
-  if (r.accumulate) s += *o;
-  *o = s;
-}
 
 // Dynamic loss scaling (fp16 activations).  ls: DEVICE float[4] = {scale, good steps since the last change, non-finite flag, skipped steps}.
 // With ls the optimiser kernels (a) return without touching anything when the flag is set -- the step is skipped, (b) divide the
@@ -277,9 +132,9 @@ static void adam_launch(rcgan_ctx* ctx, size_t count, float* w, const float* g, 
   }
 }
 
-static int g_use_tr = -1;   // -1 unknown, 0 no, 1 yes (decided by the self test)
+int g_use_tr = -1;   // -1 unknown, 0 no, 1 yes (decided by the self test)
 
-static int ensure_selftest(rcgan_ctx* ctx) {
+int ensure_selftest(rcgan_ctx* ctx) {
   if (g_use_tr >= 0) return RCGAN_OK;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(ctx->stream, &st);
@@ -291,6 +146,28 @@ static int ensure_selftest(rcgan_ctx* ctx) {
   g_use_tr = (res[1] == 0) ? 1 : 0;
   const char* e = getenv("RCGAN_NO_TR");
   if (e && e[0] == '1') g_use_tr = 0;
+  return RCGAN_OK;
+}
+
+int check_desc(rcgan_ctx* ctx, const rcgan_conv_desc* d) {
+  RC_REQUIRE(ctx, d != nullptr, "null desc");
+  RC_REQUIRE(ctx, d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "bad dims");
+  RC_REQUIRE(ctx, d->kh > 0 && d->kw > 0 && d->stride > 0, "bad kernel/stride");
+  RC_REQUIRE(ctx, d->dtype == RCGAN_F32 || d->dtype == RCGAN_H16, "bad dtype");
+  if (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) RC_REQUIRE(ctx, d->h % 2 == 0 && d->w % 2 == 0, "upsampled size must be even");
+  if (d->flags & RCGAN_CONV_OUT_MEANPOOL2)
+    RC_REQUIRE(ctx, !(d->flags & RCGAN_CONV_IN_UPSAMPLE2X) && d->h % 2 == 0 && d->w % 2 == 0, "fused mean pool: even size, no upsampled input");
+  return RCGAN_OK;
+}
+
+// The filter gradient of a layer the matrix cores do not take (rcgan_conv2d_bwd_weight, conv_wgrad.hip): image-end, small or direct kernel
+int conv_wgrad_off_mfma(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias, int accumulate,
+                        void* ws, size_t ws_bytes) {
+  if (img_side(d)) return img_wgrad(ctx, d, x, dy, dw, dbias, accumulate, ws, ws_bytes);
+  if (int kind = small_wgrad_kind(d)) {
+    RC_DISPATCH_DTYPE(ctx, d->dtype, return small_wgrad<T>(ctx, d, kind, (const T*)x, (const T*)dy, dw, dbias, accumulate, ws, ws_bytes));
+  }
+  RC_DISPATCH_DTYPE(ctx, d->dtype, return direct_wgrad<T>(ctx, d, (const T*)x, (const T*)dy, dw, dbias, accumulate, ws, ws_bytes));
   return RCGAN_OK;
 }
 
@@ -576,17 +453,6 @@ int rcgan_query(rcgan_ctx* ctx, int what) {
 // ------------------------------------------------------------------------------------------------
 // convolution
 // ------------------------------------------------------------------------------------------------
-static int check_desc(rcgan_ctx* ctx, const rcgan_conv_desc* d) {
-  RC_REQUIRE(ctx, d != nullptr, "null desc");
-  RC_REQUIRE(ctx, d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0, "bad dims");
-  RC_REQUIRE(ctx, d->kh > 0 && d->kw > 0 && d->stride > 0, "bad kernel/stride");
-  RC_REQUIRE(ctx, d->dtype == RCGAN_F32 || d->dtype == RCGAN_H16, "bad dtype");
-  if (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) RC_REQUIRE(ctx, d->h % 2 == 0 && d->w % 2 == 0, "upsampled size must be even");
-  if (d->flags & RCGAN_CONV_OUT_MEANPOOL2)
-    RC_REQUIRE(ctx, !(d->flags & RCGAN_CONV_IN_UPSAMPLE2X) && d->h % 2 == 0 && d->w % 2 == 0, "fused mean pool: even size, no upsampled input");
-  return RCGAN_OK;
-}
-
 int rcgan_conv_fused_pool_ok(const rcgan_conv_desc* d) { return d && mfma_pool_ok(d) ? 1 : 0; }
 
 size_t rcgan_conv_prepared_bytes(const rcgan_conv_desc* d) {
@@ -963,304 +829,6 @@ int rcgan_conv2d_bwd_data_residual(rcgan_ctx* ctx, const rcgan_conv_desc* d, con
     if (rc) return rc;
   }
   return RCGAN_OK;
-}
-
-// The matrix-core filter-gradient problem of a layer (everything but the slab) and the number of pixel chunks its slabs are sized for.
-// Upsample-3x3 and ConvMeanPool layers the three-tap kernel takes are posed in their sub-pixel form (MfmaWgradArgs::sub): reduction over
-// the low-resolution grid.
-static int wgrad_pose(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy, bool want_bias, MfmaWgradArgs& a, int* nz) {
-  int oh, ow, pt, pl;
-  same_pad(d->h, d->kh, 1, &oh, &pt);
-  same_pad(d->w, d->kw, 1, &ow, &pl);
-  a.x = (const bf16_t*)x; a.dy = (const bf16_t*)dy; a.slab = nullptr;
-  a.zero = (const bf16_t*)ctx->zero_page;
-  a.N = d->n; a.H = d->h; a.W = d->w; a.Cin = d->cin; a.Cout = d->cout; a.KH = d->kh; a.KW = d->kw; a.PT = pt; a.PL = pl;
-  a.up = (d->flags & RCGAN_CONV_IN_UPSAMPLE2X) ? 1 : 0;
-  a.relu_in = (d->flags & RCGAN_CONV_IN_RELU) ? 1 : 0;
-  a.use_tr = g_use_tr;
-  a.sub = mfma_wgrad_sub_kind(d, g_use_tr);
-  if ((d->flags & RCGAN_CONV_OUT_MEANPOOL2) && a.sub != 2)
-    RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "filter gradient from the pooled dy needs the sub-pixel three-tap kernel (rcgan_conv_wgrad_pool_ok)");
-  if (a.sub == 1 || a.sub == 2) { a.H >>= 1; a.W >>= 1; a.up = 0; }
-  a.cells = (a.sub == 1 || a.sub == 2) ? 16 : d->kh * d->kw;
-  a.M = (long)d->n * a.H * a.W;
-  a.lw = ilog2_exact(a.W); a.lh = ilog2_exact(a.H);
-  if (a.lw < 0 || a.lh < 0) { a.lw = -1; a.lh = -1; }
-  a.slab_stride = wgrad_slab_floats(a, 1);
-  a.want_bias = want_bias ? 1 : 0;
-  a.m_chunk = 0;
-  *nz = mfma_wgrad_splits(d, a.M, a.sub);
-  return RCGAN_OK;
-}
-
-static SlabReduceGroup::Item wgrad_reduce_item(const rcgan_conv_desc* d, const MfmaWgradArgs& a, float* dw, float* dbias, int nbias, int nz, int accumulate) {
-  SlabReduceGroup::Item it = {};
-  it.slab = a.slab; it.stride = a.slab_stride; it.out = dw; it.count = (long)d->kh * d->kw * d->cin * d->cout;
-  it.bias_out = dbias; it.nbias = nbias; it.nz = nz; it.accumulate = accumulate;
-  it.bias_off = (long)a.cells * d->cin * d->cout;
-  it.sub = a.sub == 3 ? 0 : a.sub; it.cc = (long)d->cin * d->cout;
-  it.bias_parts = a.slab_stride == it.bias_off + 2L * d->cout ? 2 : 1;       // (mfma_wgrad9_plan's upsample form)
-  static const int vec4_on = [] { const char* e = getenv("RCGAN_SLAB_REDUCE_VEC4"); return e ? atoi(e) : 1; }();
-  it.vec4 = vec4_on && it.count % 4 == 0 && it.cc % 4 == 0 && a.slab_stride % 4 == 0 && ((size_t)a.slab & 15) == 0 && ((size_t)dw & 15) == 0;
-  return it;
-}
-
-int rcgan_conv_wgrad_pool_ok(const rcgan_conv_desc* d) {
-  // (before the self test has run the transposing LDS read counts as available; rcgan_conv2d_bwd_weight re-checks)
-  return d && (d->flags & RCGAN_CONV_OUT_MEANPOOL2) && mfma_wgrad_sub_kind(d, g_use_tr < 0 ? 1 : g_use_tr) == 2 ? 1 : 0;
-}
-
-int rcgan_conv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy, float* dw, float* dbias,
-                            int accumulate, void* ws, size_t ws_bytes) {
-  int rc = check_desc(ctx, d);
-  if (rc) return rc;
-  if (mfma_wgrad_eligible(d)) {
-    rc = ensure_selftest(ctx);
-    if (rc) return rc;
-    MfmaWgradArgs a;
-    int nz = 0;
-    rc = wgrad_pose(ctx, d, x, dy, dbias != nullptr, a, &nz);
-    if (rc) return rc;
-    a.slab = (float*)ws;
-    long cnt = (long)d->kh * d->kw * d->cin * d->cout;
-    size_t need = mfma_wgrad_ws_need(nz, a.slab_stride, a.M, d->cout);
-    if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
-    bool bias_done = false;
-    int nzz = mfma_wgrad_launch(ctx, a, nz, &bias_done, ws_bytes);
-    if (nzz < 0) return nzz;
-    const int nb = bias_done ? d->cout : 0;
-    if (a.sub == 1 || a.sub == 2) {
-      SlabReduceGroup g;
-      for (int q = 0; q < REDUCE_GROUP_MAX; ++q) g.it[q] = wgrad_reduce_item(d, a, dw, dbias, nb, nzz, accumulate);
-      hipLaunchKernelGGL(slab_reduce2_group_kernel, dim3(cdiv(cnt + nb, 256), 1), dim3(256), 0, ctx->stream, g);
-    } else {
-      hipLaunchKernelGGL(slab_reduce2_kernel, dim3(cdiv(cnt + nb, 256)), dim3(256), 0, ctx->stream, (const float*)a.slab, a.slab_stride, dw, cnt,
-                         dbias, nb, nzz, accumulate);
-    }
-    RC_LAUNCH_CHECK(ctx);
-    if (dbias && !bias_done) {
-      float* part = (float*)((char*)ws + (size_t)nz * a.slab_stride * sizeof(float));
-      rc = colsum_launch<bf16_t>(ctx, (const bf16_t*)dy, a.M, d->cout, dbias, accumulate, part);
-      if (rc) return rc;
-    }
-    return RCGAN_OK;
-  }
-  if (img_side(d)) return img_wgrad(ctx, d, x, dy, dw, dbias, accumulate, ws, ws_bytes);
-  if (int kind = small_wgrad_kind(d)) {
-    RC_DISPATCH_DTYPE(ctx, d->dtype, return small_wgrad<T>(ctx, d, kind, (const T*)x, (const T*)dy, dw, dbias, accumulate, ws, ws_bytes));
-  }
-  RC_DISPATCH_DTYPE(ctx, d->dtype, return direct_wgrad<T>(ctx, d, (const T*)x, (const T*)dy, dw, dbias, accumulate, ws, ws_bytes));
-  return RCGAN_OK;
-}
-
-// The family (vector of planned problems) among fam[0, nfam) whose launch has the most workgroups; -1 if none qualifies.  Only the first
-// `counted` problems of a family count; skip_empty: a family without problems is no candidate; later_wins_ties: >= instead of >.
-static int wgrad_busiest_family(const std::vector<MfmaWgradPlanned>* fam, int nfam, size_t counted, bool skip_empty, bool later_wins_ties) {
-  int best_f = -1;
-  unsigned best = 0;
-  for (int f = 0; f < nfam; ++f) {
-    if (skip_empty && fam[f].empty()) continue;
-    unsigned tot = 0;
-    for (size_t q = 0; q < fam[f].size() && q < counted; ++q) tot += fam[f][q].gx * fam[f][q].gy;
-    if (best_f < 0 || (later_wins_ties ? tot >= best : tot > best)) { best = tot; best_f = f; }
-  }
-  return best_f;
-}
-
-// Filter gradients of several layers whose x / dy are all available (the end of a backward pass): the layers the
-// three-tap matrix-core kernel takes run as ONE grouped launch per input-ReLU flavour + ONE grouped slab reduction; every
-// other layer goes through rcgan_conv2d_bwd_weight as usual.
-int rcgan_conv2d_bwd_weight_group(rcgan_ctx* ctx, int n, const rcgan_conv_desc* descs, const void* const* xs, const void* const* dys,
-                                  float* const* dws, float* const* dbiases, int accumulate, void* ws, size_t ws_bytes) {
-  RC_REQUIRE(ctx, n >= 0 && (n == 0 || (descs && xs && dys && dws && dbiases)), "null argument");
-  static const int target_blocks = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_BLOCKS"); return e ? atoi(e) : 448; }();      // (512 before the sub-pixel forms: 6.67 -> 6.64 ms with 384; round 4, the critic step's launch with its chunks' workgroups on one XCD and the generator step's big layers gone to the nine-tap kernel, same box: 384 5.65 ms, 448 5.59, 512 5.60, 576 5.75)
-  struct Cand { MfmaWgradArgs a = {}; int nz = 0; WgradKernel k = WK_TAP_REG; };      // (WK_TAP_REG: not grouped -- no matrix-core layer, or that kernel)
-  std::vector<Cand> cand(n);
-  // The nine-tap kernel (conv_wgrad9.hip) takes the group's 3x3 layers when they are big: its one workgroup per CU writes a slab of ALL nine
-  // (sixteen) cells, and the riders of the three-tap launch (image-end layers, 1x1 shortcuts, the head) lose the workgroups they hid under.
-  // Measured on the bench iteration: the critic step's layers (n = 128, 128 channels: 1152 pixels per workgroup) 120 -> 172 us with it, the
-  // generator step's (256 channels: 12032 / 2560 pixels per workgroup) 478 -> 425 us.
-  const long w9_minwork = [] { const char* e = getenv("RCGAN_WGRAD9_GROUP_MINWORK"); return e ? atol(e) : 1000000L; }();      // (per call: the tests force it; the critic step's group is 0.52 M, the generator step's 2.75 M, one 256-channel 32x32 layer 1.05 M)
-  bool wgrad9_group_on = false;
-  {
-    double w9 = 0;
-    for (int i = 0; i < n; ++i) {
-      const rcgan_conv_desc* d = descs + i;
-      if (check_desc(ctx, d) || !mfma_wgrad_eligible(d) || d->kh != 3) continue;
-      w9 += (double)d->n * d->h * d->w * (d->cin / 64) * (d->cout / 128);       // (full-resolution pixels x channel tiles)
-    }
-    wgrad9_group_on = w9 >= (double)w9_minwork;
-  }
-  // pass 1: which layers the grouped kernel takes, and the pixels per workgroup that gives ~target_blocks workgroups in all
-  double work = 0, work9[2] = {0, 0};        // (work9: the nine-tap kernel's plain / sub-pixel layers, one workgroup per CU each)
-  for (int i = 0; i < n; ++i) {
-    const rcgan_conv_desc* d = descs + i;
-    int rc = check_desc(ctx, d);
-    if (rc) return rc;
-    if (!mfma_wgrad_eligible(d)) continue;
-    rc = ensure_selftest(ctx);
-    if (rc) return rc;
-    MfmaWgradArgs& a = cand[i].a;
-    rc = wgrad_pose(ctx, d, xs[i], dys[i], dbiases[i] != nullptr, a, &cand[i].nz);
-    if (rc) return rc;
-    rc = mfma_wgrad_choose(ctx, a, wgrad9_group_on ? WGRAD9_ON : WGRAD9_OFF, &cand[i].k);
-    if (rc) return rc;
-    if (cand[i].k == WK_NINE) {
-      work9[a.sub ? 1 : 0] += (double)a.M * (a.Cin / 64) * (a.Cout / 128) * (a.sub ? 2 : 1);
-    } else if (cand[i].k == WK_THREE) {
-      // workgroup-passes over a pixel: 3 filter rows of three taps, or 8 (parity, row shift) tiles of two taps
-      work += (double)a.M * (a.sub == 3 ? 1.0 / 3.0 : (a.sub ? 8 * 2.0 / 3.0 : a.KH)) * (a.Cin / 64) * (a.Cout / 128);
-    }
-  }
-  static const int px_max = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_PXMAX"); return e ? atoi(e) : 6144; }();
-  long px = (long)(work / target_blocks);
-  px = (px + 63) / 64 * 64;
-  if (px < 256) px = 256;
-  if (px > px_max) px = px_max;      // big groups (the generator step): more workgroups rather than ever longer ones
-  static const int target9 = [] { const char* e = getenv("RCGAN_WGRAD9_BLOCKS"); return e ? atoi(e) : 256; }();
-  // one workgroup per CU and equal pixels per workgroup: the smallest chunk with which the layers' tiles x chunks fit ONE round of target9
-  // workgroups (a 257th workgroup would double the launch's time); the plain and the sub-pixel layers are a launch each
-  long px9[2] = {0, 0};
-  for (int f = 0; f < 2; ++f) {
-    px9[f] = ((long)(work9[f] / target9) + 127) / 128 * 128;
-    if (px9[f] < 512) px9[f] = 512;
-    for (int it = 0; it < 4096 && work9[f] > 0; ++it, px9[f] += 128) {
-      long tot = 0;
-      for (int i = 0; i < n; ++i)
-        if (cand[i].k == WK_NINE && (cand[i].a.sub != 0) == (f != 0)) {
-          MfmaWgradPlanned b = {cand[i].a, 0, 0};
-          mfma_wgrad_plan(b, WK_NINE, 1 << 20, px9[f]);
-          tot += (long)b.gx * b.gy;
-        }
-      if (tot <= target9) break;
-    }
-  }
-  std::vector<MfmaWgradPlanned> fam9[4];         // nine-tap kernel: plain without / with input ReLU, sub-pixel forms without / with
-  // pass 2: slabs, grouped launches per input-ReLU flavour, everything else on its own
-  std::vector<MfmaWgradPlanned> fam[3];          // three-tap kernel without / with input ReLU, per-tap kernel
-  std::vector<MfmaWgradPlanned> late;            // small 1x1 layers on the two-tap body: join one of the first two
-  std::vector<SlabReduceGroup::Item> red;
-  size_t used = 0;
-  // image-end layers ride in the first grouped launch (if there is one) and in the grouped reduction
-  ImgWGroup img;
-  img.n = 0;
-  for (int q = 0; q <= IMG_GROUP_MAX; ++q) img.first[q] = 0;
-  static const int img_group = [] { const char* e = getenv("RCGAN_WGRAD_GROUP_IMG"); return e ? atoi(e) : 1; }();
-  bool any_group = false;
-  for (int i = 0; i < n && img_group; ++i) any_group = any_group || cand[i].k == WK_THREE;
-  for (int i = 0; i < n; ++i) {
-    const rcgan_conv_desc* d = descs + i;
-    bool grouped = false;
-    if (any_group && img.n < IMG_GROUP_MAX && img_side(d) && (d->cin <= 3 ? d->cout : d->cin) == 128) {
-      ImgWArgs ia;
-      int cb = 0, nwg = 0;
-      static const int img_wgs = [] { const char* e = getenv("RCGAN_WGRAD_IMG_WGS"); return e ? atoi(e) : 128; }();       // (with 384 three-tap workgroups: 6.64 -> 6.62 ms with 96; round 5, the three-tap workgroups a quarter faster: 96 5.36 ms, 128 5.34, 160 5.40, 256 5.36)
-      int rc = img_wgrad_plan(ctx, d, xs[i], dys[i], img_wgs, &ia, &cb, &nwg);
-      if (rc) return rc;
-      const long per = 32L * cb + 32;
-      const size_t need = ((size_t)nwg * per * sizeof(float) + 255) / 256 * 256;
-      if (used + need <= ws_bytes / 2) {
-        ia.slab = (float*)((char*)ws + used);
-        used += need;
-        const int q = img.n++;
-        img.a[q] = ia;
-        for (int r = q + 1; r <= IMG_GROUP_MAX; ++r) img.first[r] = img.first[q] + (unsigned)nwg;
-        const int side = img_side(d), cs = side == 1 ? d->cin : d->cout, T = d->kh * d->kw;
-        SlabReduceGroup::Item it = {};
-        it.slab = ia.slab; it.stride = per; it.out = dws[i]; it.count = (long)T * cs * cb; it.nz = nwg; it.accumulate = accumulate;
-        it.Cb = cb; it.Cs = cs;
-        if (side == 1) {           // small = conv input: slab order is dW order; bias gradient = the ones row (31)
-          it.orient = 0; it.bias_out = dbiases[i]; it.nbias = dbiases[i] ? cb : 0; it.bias_off = 31L * cb;
-        } else {                   // small = dy: transposed; bias gradient = column sums of the centre tap
-          it.orient = 1; it.bias_out = dbiases[i]; it.nbias = dbiases[i] ? cs : 0; it.bias_off = 32L * cb + (T == 9 ? 4 : 0) * cs;
-        }
-        red.push_back(it);
-        grouped = true;
-      }
-    }
-    const WgradKernel k = cand[i].k;
-    if (!grouped && k != WK_TAP_REG) {
-      MfmaWgradPlanned p = {cand[i].a, 0, 0};
-      MfmaWgradArgs& a = p.a;
-      // (the grouped slabs are fitted into the workspace below: no a-priori bound on the nine-tap kernel's pixel chunks)
-      if (k == WK_NINE) mfma_wgrad_plan(p, k, 1 << 20, px9[a.sub ? 1 : 0]);
-      else mfma_wgrad_plan(p, k, cand[i].nz, px);
-      const size_t need = ((size_t)p.gy * a.slab_stride * sizeof(float) + 255) / 256 * 256;
-      if (used + need <= ws_bytes / 2) {
-        a.slab = (float*)((char*)ws + used);
-        used += need;
-        if (k == WK_NINE) fam9[(a.sub ? 2 : 0) + (a.relu_in ? 1 : 0)].push_back(p);
-        else if (k == WK_THREE && a.sub == 3 && !a.relu_in) late.push_back(p);       // placed below
-        else fam[k == WK_THREE ? (a.relu_in ? 1 : 0) : 2].push_back(p);
-        red.push_back(wgrad_reduce_item(d, a, dws[i], dbiases[i], dbiases[i] ? d->cout : 0, (int)p.gy, accumulate));
-        grouped = true;
-      }
-    }
-    if (!grouped) {          // its own launches, with the workspace half the grouped slabs do not use
-      int rc = rcgan_conv2d_bwd_weight(ctx, d, xs[i], dys[i], dws[i], dbiases[i], accumulate, (char*)ws + ws_bytes / 2, ws_bytes - ws_bytes / 2);
-      if (rc) return rc;
-    }
-  }
-  // Three riders each hide under the family of grouped launches with the most workgroups.  Their rules differ, and the differences decide
-  // which launch a rider lengthens (the bench iteration's timings were taken with exactly these): do not unify them.
-  // * a riding 1x1 without input ReLU runs on either flavour of the three-tap kernel (the ReLU is a per-problem switch in the two-tap
-  //   body): every planned problem counts, it may open a family of its own (an empty one is a candidate), and a tie stays with family 0
-  if (!late.empty()) {
-    const int f = wgrad_busiest_family(fam, 2, (size_t)-1, false, false);
-    fam[f].insert(fam[f].end(), late.begin(), late.end());
-  }
-  // * the image-end workgroups ride in a family's FIRST launch (mfma_wgrad3_group_launch: WGRAD_GROUP_MAX problems) -- deliberately only
-  //   those count and the family must exist; a tie goes to the later one, and the per-tap family (2) is a candidate
-  int img_f = -1;
-  if (img.n) {
-    img_f = wgrad_busiest_family(fam, 3, WGRAD_GROUP_MAX, true, true);
-    RC_REQUIRE(ctx, img_f >= 0, "image-end filter gradients planned without a grouped launch");
-  }
-  // * the projection head's deferred parameter sums (head_rider.h) need a three-tap launch (families 0, 1): they follow the image-end
-  //   workgroups there, else the same rule over those two
-  int head_f = -1;
-  if (ctx->head_stage == 2) head_f = (img_f == 0 || img_f == 1) ? img_f : wgrad_busiest_family(fam, 2, WGRAD_GROUP_MAX, true, true);
-  for (int f = 0; f < 4; ++f)
-    if (!fam9[f].empty()) {
-      int rc = mfma_wgrad9_group_launch(ctx, (int)fam9[f].size(), fam9[f].data());
-      if (rc) return rc;
-    }
-  for (int f = 0; f < 3; ++f)
-    if (!fam[f].empty()) {
-      int rc = mfma_wgrad3_group_launch(ctx, (int)fam[f].size(), fam[f].data(), f == 2 ? 1 : 0, f == img_f ? &img : nullptr, f == head_f);
-      if (rc) return rc;
-    }
-  for (size_t i0 = 0; i0 < red.size(); i0 += REDUCE_GROUP_MAX) {
-    SlabReduceGroup g;
-    const int m = (int)((red.size() - i0 < REDUCE_GROUP_MAX) ? red.size() - i0 : REDUCE_GROUP_MAX);
-    long maxc = 0;
-    for (int q = 0; q < m; ++q) {
-      g.it[q] = red[i0 + q];
-      const long threads = (g.it[q].vec4 ? g.it[q].count / 4 : g.it[q].count) + g.it[q].nbias;
-      if (threads > maxc) maxc = threads;
-    }
-    for (int q = m; q < REDUCE_GROUP_MAX; ++q) g.it[q] = red[i0];
-    hipLaunchKernelGGL(slab_reduce2_group_kernel, dim3(cdiv(maxc, 256), m), dim3(256), 0, ctx->stream, g);
-    RC_LAUNCH_CHECK(ctx);
-  }
-  return RCGAN_OK;
-}
-
-// What rcgan_conv2d_bwd_weight_group needs at most: the call splits ws in two halves -- the second serves every layer that is computed by a
-// call of its own (rcgan_conv_workspace_bytes of the largest), the first holds the slabs of the grouped launches (a layer whose slabs do
-// not fit there is computed on its own instead: same values).  Each half: the largest single need plus the single needs of the layers
-// that can be grouped (matrix-core and image-end layers), every term rounded up to 256 bytes.
-size_t rcgan_conv2d_bwd_weight_group_workspace_bytes(int n, const rcgan_conv_desc* descs) {
-  if (n <= 0 || descs == nullptr) return 0;
-  size_t largest = 0, slabs = 0;
-  for (int i = 0; i < n; ++i) {
-    const rcgan_conv_desc* d = descs + i;
-    if (d->n < 1 || d->h < 1 || d->w < 1 || d->cin < 1 || d->cout < 1 || d->kh < 1 || d->kw < 1 || d->stride < 1) return 0;
-    const size_t one = (rcgan_conv_workspace_bytes(d) + 255) / 256 * 256;
-    largest = std::max(largest, one);
-    if (mfma_wgrad_eligible(d) || img_side(d)) slabs += one;
-  }
-  return 2 * (largest + slabs);
 }
 
 // transposed conv: d describes the forward conv whose data-gradient it is (see header)

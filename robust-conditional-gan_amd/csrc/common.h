@@ -242,6 +242,12 @@ __device__ __forceinline__ float act_grad(int act, float s) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// an integer switch of the environment (callers keep it in a function-local static where it is read once)
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
 // TF SAME padding (tf.nn.conv2d padding='SAME')
 static inline void same_pad(int in, int k, int s, int* out, int* before) {
   int o = (in + s - 1) / s;

@@ -1,4 +1,4 @@
-// Device code of the image-end filter gradient shared by conv_image.hip (its own launch) and conv_mfma.hip (as extra
+// Device code of the image-end filter gradient shared by conv_image.hip (its own launch) and conv_wgrad.hip (as extra
 // workgroups of the grouped filter-gradient launches): im2col geometry of the <= 3-channel tensor and the workgroup body.
 #pragma once
 #include "mfma_util.h"

@@ -1,6 +1,6 @@
 // Filter gradient of a plain 3x3 stride-1 SAME convolution with ALL NINE taps in one workgroup (round 4).
 //
-// What round 4 measured on the three-tap kernel (conv_mfma.hip wgrad3_body; scripts/exp_wgrad_ablation.sh, profiles/r04_exp_wgrad_ablation.txt),
+// What round 4 measured on the three-tap kernel (conv_wgrad.hip wgrad3_body; scripts/exp_wgrad_ablation.sh, profiles/r04_exp_wgrad_ablation.txt),
 // 256-channel 32x32 layer at n = 128: 254 us as built, 192 us with the MFMAs removed, 193 us with MFMAs AND fragment reads removed, 97 us
 // with the LDS-DMA stream removed -- the kernel is bound by the bytes its workgroups pull from L2 into LDS (13 KB per 32-pixel stage for
 // 96 MFMAs, three workgroups per CU each streaming its own copy: 1.3 GB per launch), not by its matrix or LDS-read schedule.  The three
@@ -25,7 +25,7 @@
 //                    (kh = 2) wavefronts clear that row's part of their dy fragments (wave-uniform branch)
 //   bias gradient  : workgroups of input-channel tile 0, one extra MFMA against a ones fragment in 8 of the 12 wavefronts
 // The slab layout is the three-tap kernel's (cell kh * 3 + kw, [ci][co]; bias tail), reduced by slab_reduce2_group_kernel.
-#include "conv_mfma.h"
+#include "conv_wgrad.h"
 #include "mfma_util.h"
 
 #ifndef WG9_ABLATE
@@ -334,7 +334,7 @@ __device__ __forceinline__ void wgrad9_body(const MfmaWgradArgs& a, unsigned bx,
 
 }  // namespace
 
-// several layers in one launch (the grouping of conv_mfma.hip's three-tap kernel): workgroup b -> problem p with first[p] <= b < first[p + 1],
+// several layers in one launch (the grouping of conv_wgrad.hip's three-tap kernel): workgroup b -> problem p with first[p] <= b < first[p + 1],
 // tile (b - first[p]) % gx[p], pixel chunk (b - first[p]) / gx[p]
 struct Wgrad9Group {
   int n;

@@ -1,7 +1,22 @@
-// Device helpers shared by the MFMA kernels (conv_mfma.hip, conv_image.hip): vector types, the packed-max ReLU,
+// Device helpers shared by the MFMA kernels (conv_mfma.hip, conv_wgrad.hip, conv_image.hip): vector types, the packed-max ReLU,
 // asm-issued LDS-DMA with hand-placed waits, the gfx950 LDS transpose read.
 #pragma once
 #include "common.h"
+
+// pixel index -> (n, oh, ow); shifts when H and W are powers of two (every layer of both nets), else divisions
+__device__ __forceinline__ void decode_pix(long m, int H, int W, int lh, int lw, int& n, int& oh, int& ow) {
+  if (lw >= 0 && lh >= 0) {
+    const unsigned mm = (unsigned)m;
+    ow = (int)(mm & (unsigned)(W - 1));
+    oh = (int)((mm >> lw) & (unsigned)(H - 1));
+    n = (int)(mm >> (lw + lh));
+  } else {
+    ow = (int)(m % W);
+    long t = m / W;
+    oh = (int)(t % H);
+    n = (int)(t / H);
+  }
+}
 
 // 16-lane (one DPP row) all-reduce in a fixed order: pairs, quads, half rows, rows
 __device__ __forceinline__ float row16_sum(float v) {

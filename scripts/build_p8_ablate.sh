@@ -10,10 +10,10 @@ for k in "$@"; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DWG9_ABLATE=${k#n} -c conv_wgrad9.hip -o _obj_probe/conv_wgrad9_abl$k.o
     objs=$(ls _obj/*.o | grep -v "conv_wgrad9.o")
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs _obj_probe/conv_wgrad9_abl$k.o -o $OUT/librcgan_abl$k.so
-  elif [ "${k#w}" != "$k" ]; then      # w<k>: the three-tap filter-gradient kernel (conv_mfma.hip, -DWG3_ABLATE)
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DWG3_ABLATE=${k#w} -c conv_mfma.hip -o _obj_probe/conv_mfma_abl$k.o
-    objs=$(ls _obj/*.o | grep -v "conv_mfma.o")
-    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs _obj_probe/conv_mfma_abl$k.o -o $OUT/librcgan_abl$k.so
+  elif [ "${k#w}" != "$k" ]; then      # w<k>: the three-tap filter-gradient kernel (conv_wgrad.hip, -DWG3_ABLATE)
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DWG3_ABLATE=${k#w} -c conv_wgrad.hip -o _obj_probe/conv_wgrad_abl$k.o
+    objs=$(ls _obj/*.o | grep -v "conv_wgrad.o")
+    /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC $objs _obj_probe/conv_wgrad_abl$k.o -o $OUT/librcgan_abl$k.so
   elif [ "${k#h}" != "$k" ]; then      # h<k>: the halo-patch kernel (conv_mfma8h.hip, -DH8_ABLATE)
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -DH8_ABLATE=${k#h} -c conv_mfma8h.hip -o _obj_probe/conv_mfma8h_abl$k.o
     objs=$(ls _obj/*.o | grep -v conv_mfma8h.o)

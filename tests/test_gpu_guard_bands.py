@@ -11,7 +11,8 @@ After each pass: ctx.sync(), then Guard.check() -- every byte outside the bodies
 read outside an input or of an unwritten output brings a NaN into a result the oracle comparison rejects (assert_close refuses non-finite
 values); the direct ABI cases count the output elements that still hold the fill (Guard.unwritten).
 
-Why each case reaches its route (line numbers: robust-conditional-gan_amd/csrc at the commit that added this file):
+Why each case reaches its route (line numbers: robust-conditional-gan_amd/csrc at the commit that added this file; those of the
+filter gradient -- conv_wgrad.hip, conv_wgrad.h, api.hip:166-170 -- at the commit that gave it its own translation unit):
 
   route                                  case (field order of the list it comes from)      reached because
   -------------------------------------  ------------------------------------------------  ------------------------------------------------
@@ -20,49 +21,49 @@ Why each case reaches its route (line numbers: robust-conditional-gan_amd/csrc a
                                                                                            small_*_kind 0 (conv_small.hip:325-342: no 128- / 256-channel
                                                                                            side) -> direct_fwd / direct_dgrad / direct_wgrad, the last
                                                                                            branches of rcgan_conv2d_fwd_residual (api.hip:907),
-                                                                                           _bwd_data_residual (:958) and _bwd_weight (:1052), any dtype
+                                                                                           _bwd_data_residual (:958) and conv_wgrad_off_mfma (:170), any dtype
   conv, 64x64 matrix-core tiles          (3,5,5,64,128,3,1,relu) (3,5,5,128,64,1,1)        16-bit, channels % 64 == 0 -> mfma_eligible; M = 75 pixels = one
                                          (3,5,5,128,128,3,1,relu): not in CONV_CASES       256-pixel tile, far below the 190 / 200 / 384 workgroups the
                                                                                            larger tiles ask for: mfma_conv_route returns CR_64
                                                                                            (conv_mfma.hip:1818), whose second tile has an 11-pixel tail,
                                                                                            forward and data gradient.  Filter gradient: the first two are
-                                                                                           not mfma_wgrad_eligible (:1634: cin % 128, cout % 128) and take
-                                                                                           direct_wgrad (api.hip:1052); the 128 -> 128 sibling is, and with
-                                                                                           M % 32 != 0 wgrad3_geom refuses it (:1863): mfma_wgrad_choose
-                                                                                           (:1986) returns the per-tap kernel, 75-pixel tail included
+                                                                                           not mfma_wgrad_eligible (conv_wgrad.hip:810: cin, cout % 128) and take
+                                                                                           direct_wgrad (api.hip:170); the 128 -> 128 sibling is, and with
+                                                                                           M % 32 != 0 wgrad3_geom refuses it (:820): mfma_wgrad_choose
+                                                                                           (:943) returns the per-tap kernel, 75-pixel tail included
   conv, folded upsample / sub-pixel      (1,8,8,128,256,3,1,up) (32,8,8,256,128,3,1,up,    IN_UPSAMPLE2X: rcgan_conv2d_bwd_data_residual (api.hip:933)
                                          relu)                                             needs the full-resolution scratch unless posed in gather form;
-                                                                                           wgrad_pose (:981) takes mfma_wgrad_sub_kind = 1 for the second
+                                                                                           wgrad_pose (conv_wgrad.hip:1076) takes mfma_wgrad_sub_kind = 1 for the second
                                                                                            (n*4*4 % 32 == 0) and 0 for the first (16 pixels): the plain
                                                                                            pose rcgan_conv_workspace_bytes promises and the sub-pixel one
   conv, image end (conv_image.hip)       (4,32,32,3,128,3,1) (3,16,16,256,3,3,1)           16-bit, W in {8,16,32}, h*w >= 256, <= 3 channels on one side and
                                          (2,32,8,3,256,3,1) (5,16,32,128,2,3,1,relu)       128 / 256 on the other: img_side != 0 (conv_image.hip:19-27) ->
-                                                                                           img_fwd (api.hip:903), img_dgrad (:951), img_wgrad (:1048); the
+                                                                                           img_fwd (api.hip:903), img_dgrad (:951), img_wgrad (:166); the
                                                                                            IN_RELU case's data gradient has a mask and no small kind:
                                                                                            direct_dgrad (:958)
   conv, small side (conv_small.hip)      the four above in fp32, and                       img_side needs 16-bit, so in fp32 small_fwd_kind /
                                          (3,10,6,128,3,3,1,relu) in every dtype            small_dgrad_kind / small_wgrad_kind (conv_small.hip:325-342: <= 4
                                                                                            channels against 128 / 256, 1x1 / 3x3, stride 1) send them to
-                                                                                           small_fwd (api.hip:904), small_dgrad (:954), small_wgrad (:1049);
+                                                                                           small_fwd (api.hip:904), small_dgrad (:954), small_wgrad (:168);
                                                                                            W = 6 is no power of two (conv_image.hip:23), so that case takes
                                                                                            small_fwd kind 2 and small_wgrad kind 2 in 16-bit too; IN_RELU
                                                                                            rules out small_dgrad (conv_small.hip:332): direct_dgrad
   conv, nine-tap filter gradient         (3,16,8,128,128,3,1) (40,8,8,128,128,3,1,relu)    mfma_wgrad_eligible (cin, cout % 128 == 0); RCGAN_WGRAD9_MINWORK =
                                          (2,16,16,128,128,3,1,relu)                        RCGAN_WGRAD9_GROUP_MINWORK = 0 (the switches of
                                          (6,16,16,256,256,3,1,up): its sub-pixel form      test_conv2d_fwd_bwd_nine_tap_forced) put the nine-tap kernel on
-                                         grouped and single                                offer: mfma_wgrad_choose (conv_mfma.hip:1978-1986) returns WK_NINE
+                                         grouped and single                                offer: mfma_wgrad_choose (conv_wgrad.hip:935-943) returns WK_NINE
                                                                                            where mfma_wgrad9_takes (conv_wgrad9.hip:385: 3x3, W 8 / 16 / 32,
                                                                                            M % 128 == 0, sub-pixel forms M % 64 == 0) -- single through
-                                                                                           mfma_wgrad_launch (:2011), grouped through the planner
-                                                                                           (api.hip:1106, :1186, mfma_wgrad9_group_launch :1225).  The
-                                                                                           fallback at conv_mfma.hip:2019 cannot be reached from
-                                                                                           rcgan_conv2d_bwd_weight: the entry check (api.hip:1027) asks for
-                                                                                           mfma_wgrad_ws_need, whose 1024 * cout spare floats (conv_mfma.h:106)
+                                                                                           mfma_wgrad_launch (:968), grouped through the planner
+                                                                                           (:1216, :1295, mfma_wgrad9_group_launch :1341).  The
+                                                                                           fallback at conv_wgrad.hip:976 cannot be reached from
+                                                                                           rcgan_conv2d_bwd_weight: the entry check (:1132) asks for
+                                                                                           mfma_wgrad_ws_need, whose 1024 * cout spare floats (conv_wgrad.h:50)
                                                                                            exceed the second bias tail of at most 128 chunks x cout, so at
                                                                                            or above the call's own need the nine-tap slabs always fit and
                                                                                            both passes run the nine-tap kernel
   direct filter gradient of 64-channel   (6,8,8,64,128,3,1,relu) (8,4,8,64,128,3,1)        cin = 64: not mfma_wgrad_eligible, whatever the switches say ->
-  layers (forward, dgrad: CR_64)         (4,2,16,64,256,3,1,relu), grouped and single      direct_wgrad alone (api.hip:1052) and from the group (:1200)
+  layers (forward, dgrad: CR_64)         (4,2,16,64,256,3,1,relu), grouped and single      direct_wgrad alone (api.hip:170) and from the group (conv_wgrad.hip:1336)
   conv, 256x256 eight-wave kernels       (52,32,32,64,256,3,1,relu)                        Cout % 256 == 0 and 208 / 200 tiles of 256 pixels >= p8_min = 200
                                          (50,32,32,256,256,1,1): both directions           (conv_mfma.hip:1813): CR_H8 / CR_P8 (the halo form takes 3x3 only);
                                                                                            the smallest entries of CONV_CASES past that count

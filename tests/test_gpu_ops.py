@@ -4,6 +4,7 @@ noise only).  bf16 activations: inputs are rounded to bf16 on the host first, so
 accumulation order + one bf16 rounding of the stored result: tolerance 1e-2 (bf16 has 8 mantissa bits,
 half-ulp 2^-9 = 0.2 %; sums of a few roundings stay well under 1 %)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -1541,36 +1542,53 @@ def grouped_filter_gradient_descs():
     return [L.ConvDesc(n, hh, ww, cin, cout, k, k, 1, L.BF16, fl) for n, hh, ww, cin, cout, k, fl in shapes]
 
 
-def grouped_filter_gradients_case(ctx):
+def grouped_filter_gradients_case(ctx, descs=None, ws_bytes=None, env=None, exact=None):
     """The body of test_grouped_filter_gradients_equal_single_calls on a bf16 context; -> its (desc, x, dy, [dw single, dw grouped],
-    [dbias single, dbias grouped] or [None, None]) per layer."""
+    [dbias single, dbias grouped] or [None, None]) per layer.  descs: another list of layers (x / dy on the grids the header prescribes
+    for their flags); ws_bytes: the workspace the GROUPED call is given (the single calls keep the context's); env: switches of the
+    library that both kinds of call run under; exact: True / False = every layer bit-identical / to 2e-6, None = the rule below."""
     import ctypes as C
     from rcgan_amd import _lib as L
     lib, h = ctx.lib, ctx.h
     ctx.new_step()
     items = []
-    for i, d0 in enumerate(grouped_filter_gradient_descs()):
+    for i, d0 in enumerate(grouped_filter_gradient_descs() if descs is None else descs):
         n, hh, ww, cin, cout, k = d0.n, d0.h, d0.w, d0.cin, d0.cout, d0.kh
-        x, dy = ctx.empty((n, hh, ww, cin)), ctx.empty((n, hh, ww, cout))
+        ux, uy = (2 if d0.flags & L.CONV_IN_UPSAMPLE2X else 1), (2 if d0.flags & L.CONV_OUT_MEANPOOL2 else 1)
+        x, dy = ctx.empty((n, hh // ux, ww // ux, cin)), ctx.empty((n, hh // uy, ww // uy, cout))
         ctx.check(lib.rcgan_rng_fill(h, x.size, x.dtype, 1, 0.0, 1.0, 100 + i, None, C.c_void_p(x.ptr)))
         ctx.check(lib.rcgan_rng_fill(h, dy.size, dy.dtype, 1, 0.0, 1.0, 200 + i, None, C.c_void_p(dy.ptr)))
         dws = [ctx.zeros((k, k, cin, cout), L.F32) for _ in range(2)]
         dbs = [ctx.zeros((cout,), L.F32) for _ in range(2)] if i % 2 == 0 else [None, None]
         items.append((d0, x, dy, dws, dbs))
     ws, wsb = C.c_void_p(ctx.ws_ptr), ctx.ws_bytes
-    for d, x, dy, dws, dbs in items:
-        ctx.check(lib.rcgan_conv2d_bwd_weight(h, C.byref(d), C.c_void_p(x.ptr), C.c_void_p(dy.ptr), C.c_void_p(dws[0].ptr),
-                                              C.c_void_p(dbs[0].ptr) if dbs[0] else None, 1, ws, wsb))
-    n = len(items)
-    descs = (L.ConvDesc * n)(*[it[0] for it in items])
-    arr = lambda f: (C.c_void_p * n)(*[f(it) for it in items])
-    ctx.check(lib.rcgan_conv2d_bwd_weight_group(h, n, descs, arr(lambda it: it[1].ptr), arr(lambda it: it[2].ptr),
-                                                arr(lambda it: it[3][1].ptr), arr(lambda it: it[4][1].ptr if it[4][1] else None),
-                                                1, ws, wsb))
+    assert ws_bytes is None or ws_bytes <= wsb
+    keep = {k: os.environ.get(k) for k in (env or {})}
+    os.environ.update(env or {})
+    try:
+        for d, x, dy, dws, dbs in items:
+            ctx.check(lib.rcgan_conv2d_bwd_weight(h, C.byref(d), C.c_void_p(x.ptr), C.c_void_p(dy.ptr), C.c_void_p(dws[0].ptr),
+                                                  C.c_void_p(dbs[0].ptr) if dbs[0] else None, 1, ws, wsb))
+        n = len(items)
+        descs = (L.ConvDesc * n)(*[it[0] for it in items])
+        arr = lambda f: (C.c_void_p * n)(*[f(it) for it in items])
+        ctx.check(lib.rcgan_conv2d_bwd_weight_group(h, n, descs, arr(lambda it: it[1].ptr), arr(lambda it: it[2].ptr),
+                                                    arr(lambda it: it[3][1].ptr), arr(lambda it: it[4][1].ptr if it[4][1] else None),
+                                                    1, ws, wsb if ws_bytes is None else ws_bytes))
+    finally:
+        for k, v in keep.items():
+            if v is None:
+                del os.environ[k]
+            else:
+                os.environ[k] = v
     for i, (d, x, dy, dws, dbs) in enumerate(items):
         a, b = ctx.download(dws[0]), ctx.download(dws[1])
         assert np.abs(a).max() > 0
+        # the layers that keep the single call's chunking: 1x1 matrix-core layers, 256 -> 3 layers, widths that are no power of two
         own = (d.kh != 3 and d.cin % 128 == 0) or d.cout == 3 or (d.w & (d.w - 1)) != 0
+        own_bias = (d.w & (d.w - 1)) != 0
+        if exact is not None:
+            own = own_bias = exact
         print("layer %d: grouped - single max %.3e of %.3e" % (i, np.abs(a - b).max(), np.abs(a).max()))
         if own:
             assert np.array_equal(a, b), "layer %d filter gradient" % i
@@ -1578,10 +1596,71 @@ def grouped_filter_gradients_case(ctx):
             assert_close(b, a, 2e-6, "layer %d filter gradient" % i)
         if dbs[0] is not None:
             print("layer %d: bias, grouped - single max %.3e" % (i, np.abs(ctx.download(dbs[1]) - ctx.download(dbs[0])).max()))
-            if (d.w & (d.w - 1)) != 0:
+            if own_bias:
                 assert np.array_equal(ctx.download(dbs[1]), ctx.download(dbs[0])), "layer %d bias gradient" % i
             assert_close(ctx.download(dbs[1]), ctx.download(dbs[0]), 2e-6, "layer %d bias gradient" % i)
     return items
+
+
+# The branches of the group call's planner, each at the smallest shapes that reach it: (n, h, w, cin, cout, k, flags) per layer, the
+# switches both kinds of call run under, and `exact` of grouped_filter_gradients_case.  (The 13 layers of
+# test_grouped_filter_gradients_equal_single_calls are one more row: image-end riders, a 1x1 rider beside both three-tap flavours, the
+# per-tap family, own calls of the 256 -> 3 layers.  The head rider, ctx->head_stage == 2, is test_gpu_head_riders.py's.)
+_UP, _RELU, _POOL = 1, 2, 16        # CONV_IN_UPSAMPLE2X, CONV_IN_RELU, CONV_OUT_MEANPOOL2
+_SUBPIXEL_LAYERS = [(2, 16, 16, 128, 128, 3, _UP), (2, 16, 16, 128, 128, 3, _UP | _RELU), (2, 16, 16, 128, 128, 3, _POOL), (2, 8, 8, 128, 128, 3, 0)]
+_NINE_TAP_FORCED = {"RCGAN_WGRAD9_MINWORK": "0", "RCGAN_WGRAD9_GROUP_MINWORK": "0"}
+GROUP_PLANNER_CASES = {
+    # more problems in one family than a launch takes (WGRAD_GROUP_MAX 12), more reduction items than a reduction takes (REDUCE_GROUP_MAX 16)
+    "two_launches_two_reductions": ([(2, 8, 8, 128, 128, 3, _RELU)] * 18, {}, None),
+    "subpixel_forms_three_tap": (_SUBPIXEL_LAYERS, {}, None),
+    "subpixel_forms_nine_tap_families": (_SUBPIXEL_LAYERS, _NINE_TAP_FORCED, None),
+    "rider_1x1_joins_relu_family": ([(8, 8, 8, 128, 128, 1, 0), (2, 8, 8, 128, 128, 3, _RELU)], {}, None),
+    "rider_1x1_opens_a_family": ([(8, 8, 8, 128, 128, 1, 0)], {}, None),
+    # no three-tap launch to ride in: the image-end layer takes a call of its own, the 12-wide one the per-tap family -- both bit-identical
+    "image_end_without_three_tap_launch": ([(4, 12, 12, 128, 128, 3, 0), (4, 32, 32, 3, 128, 3, 0)], {}, True),
+    "one_layer": ([(2, 8, 8, 128, 128, 3, 0)], {}, None),
+}
+
+
+@pytest.fixture(scope="module")
+def group_ctx():
+    ctx = make_ctx("bf16")
+    yield ctx
+    ctx.close()
+
+
+@pytest.mark.parametrize("name", sorted(GROUP_PLANNER_CASES))
+def test_grouped_filter_gradients_planner_branches(group_ctx, name):
+    """rcgan_conv2d_bwd_weight_group == one rcgan_conv2d_bwd_weight per layer on every branch of its planner (GROUP_PLANNER_CASES)."""
+    from rcgan_amd import _lib as L
+    shapes, env, exact = GROUP_PLANNER_CASES[name]
+    descs = [L.ConvDesc(n, hh, ww, cin, cout, k, k, 1, L.BF16, fl) for n, hh, ww, cin, cout, k, fl in shapes]
+    grouped_filter_gradients_case(group_ctx, descs=descs, env=env, exact=exact)
+
+
+def test_grouped_filter_gradients_in_a_small_workspace(group_ctx):
+    """Twice the largest single need is a workspace the group call accepts: layers whose slabs do not fit its first half fall back to a
+    call of their own in the second.  Which ones is the planner's business, so every layer is held to 2e-6."""
+    descs = grouped_filter_gradient_descs()
+    largest = max(group_ctx.lib.rcgan_conv_workspace_bytes(C.byref(d)) for d in descs)
+    ws_bytes = (2 * largest + 255) // 256 * 256
+    arr = (type(descs[0]) * len(descs))(*descs)
+    assert ws_bytes < group_ctx.lib.rcgan_conv2d_bwd_weight_group_workspace_bytes(len(descs), arr)
+    grouped_filter_gradients_case(group_ctx, ws_bytes=ws_bytes, exact=False)
+
+
+def test_grouped_filter_gradients_of_no_layer(group_ctx):
+    """n = 0: RCGAN_OK, nothing written."""
+    from rcgan_amd import _lib as L
+    ctx = group_ctx
+    ctx.new_step()
+    dw = ctx.upload(np.full((3, 3, 128, 128), -7.25, np.float32), L.F32)
+    one = (C.c_void_p * 1)(dw.ptr)
+    desc = (L.ConvDesc * 1)(L.ConvDesc(2, 8, 8, 128, 128, 3, 3, 1, L.BF16, 0))
+    assert ctx.lib.rcgan_conv2d_bwd_weight_group(ctx.h, 0, desc, one, one, one, one, 1, C.c_void_p(ctx.ws_ptr), ctx.ws_bytes) == 0
+    assert ctx.lib.rcgan_conv2d_bwd_weight_group(ctx.h, 0, None, None, None, None, None, 0, C.c_void_p(ctx.ws_ptr), ctx.ws_bytes) == 0
+    ctx.sync()
+    assert np.all(ctx.download(dw) == np.float32(-7.25))
 
 
 @pytest.mark.parametrize("case", [
