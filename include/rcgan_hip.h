@@ -686,6 +686,22 @@ int rcgan_knn_radius(rcgan_ctx* ctx, int n, int d, int k, int n_seg, const float
 int rcgan_ball_query(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const float* q, const int32_t* q_off, const float* r,
                      const int32_t* r_off, const float* r_radius2, int32_t* count, float* nearest2);
 
+/* ---- row sums of the cubic polynomial kernel (csrc/ksum.hip; the unbiased MMD^2 "kernel distance" of kid.py)
+ * rowsum[i] = sum over the reference rows j of query row i's segment of (gamma * <q_i, r_j> + coef0)^3, fp64;
+ * exclude_same_row != 0 leaves out j == i (global row indices: meaningful when q and r are the same rows and offsets).
+ * Segments as above: int32 DEVICE arrays q_off / r_off [n_seg + 1], every offset clamped to [0, n], a decreasing pair an empty
+ * segment, segment s of the queries meets only segment s of the references, rows outside every segment are not written, an empty
+ * reference segment gives 0.0.
+ * Arithmetic: the inner product is fp32 on the matrix cores (v_mfma_f32_32x32x2_f32, a chain of fused multiply-adds in an order of
+ * the kernel's choosing): |dot_c - dot| <= g_d * sum_i |q_i r_i|, g_d = d u / (1 - d u), u = 2^-24.  Everything after it is fp64:
+ * t = gamma * (double)dot_c + coef0 (one fused multiply-add), then t * t * t, then the row sum.  No floating-point atomics: the order
+ * in which a row's terms are added is fixed by the launch geometry, so the same bits come out on every run, eager or replayed.
+ * One launch on the context's stream, no workspace, no host synchronisation, legal inside a captured graph.
+ * 1 <= d <= 256, nq, nr >= 1, 1 <= n_seg <= 1024, finite gamma and coef0, non-NULL pointers (rowsum 8-byte aligned): anything else
+ * is RCGAN_EINVALID_ARG before any launch (a NULL context included, so the checks need no device). */
+int rcgan_poly3_rowsum(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const float* q, const int32_t* q_off, const float* r,
+                       const int32_t* r_off, double gamma, double coef0, int exclude_same_row, double* rowsum);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

@@ -234,6 +234,7 @@ SIGNATURES = {
     "rcgan_class_moments_accum": (I, [P, I, I, I, P, P, P]),
     "rcgan_knn_radius": (I, [P, I, I, I, I, P, P, P]),
     "rcgan_ball_query": (I, [P, I, I, I, I, P, P, P, P, P, P, P]),
+    "rcgan_poly3_rowsum": (I, [P, I, I, I, I, P, P, P, P, C.c_double, C.c_double, I, P]),
     "rcgan_sgd_momentum": (I, [P, SZ, SZ, P, P, P, P, F, F, I, F]),
     "rcgan_augment_cifar": (I, [P, I, I, P, P, P, P, I, I, P, P]),
     "rcgan_adam_tf": (I, [P, SZ, P, P, P, P, P, F, F, F, F, F]),

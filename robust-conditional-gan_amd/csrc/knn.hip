@@ -12,11 +12,9 @@
 // then merge their sorted lists / counts / minima through LDS.  Reference rows are staged through LDS, double-buffered (the next
 // tile's global loads are in flight while this one is computed); every lane reads them at the same address (a broadcast).  d > 64
 // walks the features in chunks of 64 with the 8 partial sums kept in registers.
-#include "common.h"
+#include "seg_rows.h"
 
-#define KNN_MAX_D 256
 #define KNN_MAX_K 16
-#define KNN_MAX_SEG 1024
 #define KNN_QT 64                    // query rows per workgroup: one per lane
 #define KNN_WAVES 8
 #define KNN_THREADS (64 * KNN_WAVES)
@@ -24,26 +22,6 @@
 #define KNN_RW (KNN_TR / KNN_WAVES)  // ... of which a wavefront takes this many
 #define KNN_DC 64                    // features per chunk
 #define KNN_TILE (KNN_TR * KNN_DC)   // floats per LDS buffer
-
-// a segment's row range out of an offset array the kernel cannot trust: clamped to [0, n], a decreasing pair is an empty segment
-__device__ __forceinline__ void knn_segment(const int32_t* __restrict__ off, int s, int n, int* lo, int* hi) {
-  const int a = min(max(off[s], 0), n), b = min(max(off[s + 1], 0), n);
-  *lo = a;
-  *hi = b < a ? a : b;
-}
-
-// elements [c0, c0 + 4) of row `row` (d wide), zeros past d or when the row does not exist
-__device__ __forceinline__ float4 knn_load4(const float* __restrict__ x, size_t row, int d, int c0, bool exists, bool vec) {
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (!exists || c0 >= d) return v;
-  const float* p = x + row * (size_t)d + c0;
-  if (vec) return *(const float4*)p;           // (d a multiple of 4 and the base 16-byte aligned: c0 < d implies c0 + 3 < d)
-  v.x = p[0];
-  if (c0 + 1 < d) v.y = p[1];
-  if (c0 + 2 < d) v.z = p[2];
-  if (c0 + 3 < d) v.w = p[3];
-  return v;
-}
 
 // MODE 0: radius2[i] = the (k + 1)-th smallest squared distance within the row's own segment (L >= k + 1 list entries per lane)
 // MODE 1: count[i] = #{ j : dist(i, j) <= rad[j] }, nearest2[i] = min_j dist(i, j)
@@ -212,8 +190,6 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_kernel(int nq, int nr, int d,
     }
   }
 }
-
-static inline int knn_vec(const float* p, int d) { return (d & 3) == 0 && ((uintptr_t)p & 15) == 0; }
 
 extern "C" {
 

@@ -76,6 +76,11 @@ def define_flags():
     f.DEFINE_integer("prdc_samples", 10000, "generated samples per precision / recall evaluation (hundreds), balanced over the classes")
     f.DEFINE_integer("prdc_real_samples", 0, "real images behind the real manifold (0: the whole training set)")
     f.DEFINE_integer("prdc_k", 5, "the k of the k-nearest-neighbour radii (1..16)")
+    f.DEFINE_integer("kid_freq", 0, "period (iterations) of the kernel distance (unbiased cubic-kernel MMD^2) on the label classifier's "
+                     "features, pooled and per class against the clean training set; also taken at the end of training (0: off)")
+    f.DEFINE_integer("kid_samples", 10000, "generated samples per kernel-distance evaluation (hundreds), balanced over the classes")
+    f.DEFINE_integer("kid_real_samples", 0, "real images behind the kernel distance (0: the whole training set)")
+    f.DEFINE_integer("kid_subset_size", 1000, "rows per subset of the kernel distance's mean +- std over subsets (at least 2)")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -125,6 +130,8 @@ def main(argv=None):
         raise ValueError('--frechet_freq and --frechet_real_samples must not be negative, --frechet_samples at least 100')
     if FLAGS.prdc_freq < 0 or FLAGS.prdc_real_samples < 0 or (FLAGS.prdc_freq > 0 and (FLAGS.prdc_samples < 100 or not 1 <= FLAGS.prdc_k <= 16)):
         raise ValueError('--prdc_freq and --prdc_real_samples must not be negative, --prdc_samples at least 100, --prdc_k in 1..16')
+    if FLAGS.kid_freq < 0 or FLAGS.kid_real_samples < 0 or (FLAGS.kid_freq > 0 and (FLAGS.kid_samples < 100 or FLAGS.kid_subset_size < 2)):
+        raise ValueError('--kid_freq and --kid_real_samples must not be negative, --kid_samples at least 100, --kid_subset_size at least 2')
     N_CLASSES, DATA = dataset_setup(FLAGS)
     if FLAGS.label_classifier is not None:
         # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
@@ -191,7 +198,7 @@ def main(argv=None):
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
-    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq
+    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq / --kid_freq
     if FLAGS.synthetic:
         tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
         clean_train = (tx, np.array(ty))
@@ -294,7 +301,7 @@ def main(argv=None):
     PRDC_FREQ = FLAGS.prdc_freq
     manifold_state = {"ev": None}
 
-    def manifold_metrics(confusion_matrix=None):
+    def manifold_evaluator():
         from . import manifold as MF
         ev = manifold_state["ev"]
         if ev is None:
@@ -306,6 +313,11 @@ def main(argv=None):
             ev.prepare_real(rx[:n_real], ry[:n_real])
             logging.info('manifold real set: {} images, k = {}, label classifier {}'.format(
                 min(n_real, len(rx)), FLAGS.prdc_k, 'shared' if shared is not None else 'of its own'))
+        return ev
+
+    def manifold_metrics(confusion_matrix=None):
+        from . import manifold as MF
+        ev = manifold_evaluator()
         r = ev.evaluate(*balanced_samples(FLAGS.prdc_samples, confusion_matrix))
         for name in MF.METRICS:
             logging.info('manifold_{}: {}'.format(name, r[name]))
@@ -314,6 +326,34 @@ def main(argv=None):
         for name in MF.METRICS:
             plot.plot('manifold_' + name, r[name])
             plot.plot('intra_class_manifold_' + name, r["intra_class_" + name])
+        return r
+
+    # kernel distance (unbiased cubic-kernel MMD^2) on the same features (kid.py), pooled and per class against the CLEAN training set
+    KID_FREQ = FLAGS.kid_freq
+    kid_state = {"ev": None}
+
+    def kernel_distances(confusion_matrix=None):
+        from . import kid as KD
+        ev = kid_state["ev"]
+        if ev is None:
+            # several metrics on: one classifier, the one another evaluator has calibrated (and owns)
+            shared = frechet_evaluator().clf if FRECHET_FREQ > 0 else manifold_evaluator().clf if PRDC_FREQ > 0 else None
+            ev = kid_state["ev"] = KD.KernelDistanceEvaluator(N_CLASSES, subset_size=FLAGS.kid_subset_size, asset=FLAGS.label_classifier,
+                                                              device=local, clf=shared)
+            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
+            n_real = FLAGS.kid_real_samples if FLAGS.kid_real_samples > 0 else len(rx)
+            ev.prepare_real(rx[:n_real], ry[:n_real])
+            logging.info('kernel distance real set: {} images, label classifier {}'.format(
+                min(n_real, len(rx)), 'shared' if shared is not None else 'of its own'))
+        r = ev.evaluate(*balanced_samples(FLAGS.kid_samples, confusion_matrix))
+        logging.info('kernel_distance: {}'.format(r["kernel_distance"]))
+        logging.info('intra_class_kernel_distance: {} +- {} ({} of {} classes)'.format(
+            r["intra_class_kernel_distance"], r["intra_class_kernel_distance_se"], r["classes_used"], N_CLASSES))
+        logging.info('kernel_distance_subsets: {} +- {} ({} of size {})'.format(
+            r["subset_mean"], r["subset_std"], r["subsets"], FLAGS.kid_subset_size))
+        plot.plot('kernel_distance', r["kernel_distance"])
+        plot.plot('intra_class_kernel_distance', r["intra_class_kernel_distance"])
+        plot.plot('kernel_distance_subsets', r["subset_mean"])
         return r
 
     def inception_score(n):
@@ -414,6 +454,10 @@ def main(argv=None):
             logging.info('starting calculating manifold precision and recall.')
             manifold_metrics()
             logging.info('finished calculating manifold precision and recall.')
+        if rank == 0 and KID_FREQ > 0 and iteration % KID_FREQ == KID_FREQ - 1:
+            logging.info('starting calculating kernel distance.')
+            kernel_distances()
+            logging.info('finished calculating kernel distance.')
         ECE = max(FLAGS.early_checkpoint_every, 1)
         if rank == 0 and ((iteration < 500 and iteration % ECE == ECE - 1) or (iteration % 1000 == 999)):      # :1007-1014
             drain_losses()
@@ -437,12 +481,19 @@ def main(argv=None):
         logging.info('starting calculating %smanifold precision and recall.' % ('min. permuted ' if cm is not None else ''))
         manifold_metrics(cm)
         logging.info('finished calculating manifold precision and recall.')
+    if rank == 0 and KID_FREQ > 0:
+        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
+        logging.info('starting calculating %skernel distance.' % ('min. permuted ' if cm is not None else ''))
+        kernel_distances(cm)
+        logging.info('finished calculating kernel distance.')
     drain_losses()
     if rank == 0 and ITERS:
         plot.dir_flush(DIR)
         saver.save(m.state_dict(), CHECKPOINT_DIR, 'model.ckpt', max(ITERS - 1, 0))
     if acc_state["clf"] is not None:
         acc_state["clf"].close()
+    if kid_state["ev"] is not None:
+        kid_state["ev"].close()
     if manifold_state["ev"] is not None:
         manifold_state["ev"].close()
     if frechet_state["ev"] is not None:
