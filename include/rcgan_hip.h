@@ -615,6 +615,32 @@ int rcgan_sgd_momentum(rcgan_ctx* ctx, size_t count, size_t decay_count, float* 
  * `dtype`; labels_out[i] = labels_all[index[i]] (either may be NULL).  An index outside [0, n_images) gives a zero image, label -1. */
 int rcgan_augment_cifar(rcgan_ctx* ctx, int n, int n_images, const uint8_t* images_chw_u8, const int32_t* labels_all,
                         const int32_t* index, const int32_t* shift_flip, int pad, int dtype, void* y_nhwc, int32_t* labels_out);
+/* The MNIST label classifier (mnist_classifier.py) stands in for the reference's frozen mnist/mnist_dcnn/graph_optimized.pb
+ * (mnist/utils.py:276-298: input `x`, a dropout keep-probability placeholder, output `pred_class`): the "deep MNIST" convnet.  Its two
+ * memory-bound operators follow.  Each returns RCGAN_EINVALID_ARG, before it launches anything, for a non-positive dimension or count,
+ * odd h or w, a NULL tensor, a keep_prob outside (0, 1] or not finite, or an unknown dtype (RCGAN_F32 and the library's 16-bit type are
+ * taken).  Inputs are assumed finite; x and y must not alias. */
+/* y[n,h/2,w/2,c] = maxpool2x2_stride2(relu(x[n,h,w,c]))  -- the graph's tf.nn.relu + tf.nn.max_pool(ksize 2, strides 2, SAME) pair
+ * after each convolution, one launch; h, w even.  Pure selection: y holds the bits of an element of x, or +0. */
+int rcgan_relu_maxpool2_fwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* x, void* y);
+/* dx (= | +=): dy goes to the FIRST maximum of each window in the order (0,0),(0,1),(1,0),(1,1) if that maximum is > 0,
+ * nothing otherwise; every element of dx is written (zeros included) when accumulate == 0.  Recomputed from x: no saved index.
+ * The gradient tf.gradients forms through MaxPoolGrad + ReluGrad, except at ties, where this rule is the documented one.
+ * accumulate != 0: dx = old + contribution in fp32, rounded once to the stored type. */
+int rcgan_relu_maxpool2_bwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* x, const void* dy, void* dx,
+                            int accumulate);
+/* tf.nn.dropout(x, keep_prob) in front of the graph's last dense layer.
+ * Element i is kept iff u_i < keep_prob, u_i the i-th number of the stream rcgan_rng_fill(kind 0, lo 0, hi 1) draws from
+ * (seed, state): u = (r >> 8) * 2^-24 of word i.  y = x * scale if kept, else 0, with scale = 1.0f / keep_prob formed in fp32 on the
+ * host (the product in fp32, rounded once to the stored type); mask[i] = 1 / 0 (count bytes, caller-owned).  state: DEVICE
+ * uint64[1] stream offset, or NULL for offset 0.  The stream advances by ceil(count / 4) quads, on the stream, as rcgan_rng_fill
+ * does (a replayed graph draws a fresh mask).  keep_prob in (0, 1]; at 1.0 everything is kept and the stream still advances. */
+int rcgan_dropout_fwd(rcgan_ctx* ctx, size_t count, int dtype, float keep_prob, uint64_t seed, void* state, const void* x, void* y,
+                      uint8_t* mask);
+/* dx (= | +=) dy * scale where mask[i] != 0, 0 elsewhere: the product rounded to fp32, then (accumulate != 0) added to the old value in
+ * fp32, the result rounded once to the stored type. */
+int rcgan_dropout_bwd(rcgan_ctx* ctx, size_t count, int dtype, float keep_prob, const uint8_t* mask, const void* dy, void* dx,
+                      int accumulate);
 
 /* ---- differentiable augmentation of the critic's input (csrc/augment.hip; Zhao et al., "Differentiable Augmentation for
  * Data-Efficient GAN Training", NeurIPS 2020) --------------------------------------------------------------------------------

@@ -237,6 +237,10 @@ SIGNATURES = {
     "rcgan_poly3_rowsum": (I, [P, I, I, I, I, P, P, P, P, C.c_double, C.c_double, I, P]),
     "rcgan_sgd_momentum": (I, [P, SZ, SZ, P, P, P, P, F, F, I, F]),
     "rcgan_augment_cifar": (I, [P, I, I, P, P, P, P, I, I, P, P]),
+    "rcgan_relu_maxpool2_fwd": (I, [P, I, I, I, I, I, P, P]),
+    "rcgan_relu_maxpool2_bwd": (I, [P, I, I, I, I, I, P, P, P, I]),
+    "rcgan_dropout_fwd": (I, [P, SZ, I, F, C.c_uint64, P, P, P, P]),
+    "rcgan_dropout_bwd": (I, [P, SZ, I, F, P, P, P, I]),
     "rcgan_adam_tf": (I, [P, SZ, P, P, P, P, P, F, F, F, F, F]),
     "rcgan_adam_tf_host": (I, [P, SZ, P, P, P, P, F, F, F, F, F, F, F]),
     "rcgan_fill_f32": (I, [P, SZ, P, F]),

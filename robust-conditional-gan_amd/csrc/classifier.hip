@@ -1,7 +1,9 @@
 // Training the generated-label-accuracy classifier on the engine (classifier.py): the pieces of its step that the GAN steps never
 // needed -- sparse softmax cross-entropy, the option-A shortcut and its adjoint as one launch each, tf.train.MomentumOptimizer, and the
-// input pipeline (random translation + mirror) over a data set that lives on the device.  All plain vector loads and stores.
+// input pipeline (random translation + mirror) over a data set that lives on the device -- and, for the MNIST classifier
+// (mnist_classifier.py), relu + 2x2 max pooling and dropout with their adjoints.  All plain vector loads and stores.
 #include "common.h"
+#include "rng.h"
 
 // ---------------------------------------------------------------------------------------------------------
 // sparse softmax cross-entropy: a wavefront per row, lanes over the columns (<= 1024 = 16 per lane, held in registers)
@@ -343,6 +345,192 @@ __global__ void augment_cifar_kernel(int n, int n_images, const uint8_t* __restr
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// the MNIST label classifier's two memory-bound operators (mnist_classifier.py): relu + 2x2 max pool, dropout.
+// ClsVec<T, N>: N consecutive channels / elements as one access -- 16 bytes (float4, eight 16-bit values) on the vector routes,
+// 8 bytes (four 16-bit values: one Philox quad) in dropout, one element on the scalar routes.
+// ---------------------------------------------------------------------------------------------------------
+template <typename T, int N> struct ClsVec;
+template <typename T> struct ClsVec<T, 1> {
+  static __device__ __forceinline__ void ld(const T* p, float* v) { v[0] = Elem<T>::ld(p); }
+  static __device__ __forceinline__ void st(T* p, const float* v) { Elem<T>::st(p, v[0]); }
+};
+template <> struct ClsVec<float, 4> {
+  static __device__ __forceinline__ void ld(const float* p, float* v) {
+    const float4 a = *(const float4*)p;
+    v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+  }
+  static __device__ __forceinline__ void st(float* p, const float* v) { *(float4*)p = make_float4(v[0], v[1], v[2], v[3]); }
+};
+template <> struct ClsVec<bf16_t, 4> {
+  static __device__ __forceinline__ void ld(const bf16_t* p, float* v) {
+    const uint2 a = *(const uint2*)p;
+    v[0] = bf16_to_f32((bf16_t)(a.x & 0xffff)); v[1] = bf16_to_f32((bf16_t)(a.x >> 16));
+    v[2] = bf16_to_f32((bf16_t)(a.y & 0xffff)); v[3] = bf16_to_f32((bf16_t)(a.y >> 16));
+  }
+  static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
+    uint2 a;
+    a.x = (uint32_t)f32_to_bf16(v[0]) | ((uint32_t)f32_to_bf16(v[1]) << 16);
+    a.y = (uint32_t)f32_to_bf16(v[2]) | ((uint32_t)f32_to_bf16(v[3]) << 16);
+    *(uint2*)p = a;
+  }
+};
+template <> struct ClsVec<bf16_t, 8> {
+  static __device__ __forceinline__ void ld(const bf16_t* p, float* v) {
+    const uint4 a = *(const uint4*)p;
+    const uint32_t w[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { v[2 * j] = bf16_to_f32((bf16_t)(w[j] & 0xffff)); v[2 * j + 1] = bf16_to_f32((bf16_t)(w[j] >> 16)); }
+  }
+  static __device__ __forceinline__ void st(bf16_t* p, const float* v) {
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = (uint32_t)f32_to_bf16(v[2 * j]) | ((uint32_t)f32_to_bf16(v[2 * j + 1]) << 16);
+    *(uint4*)p = make_uint4(w[0], w[1], w[2], w[3]);
+  }
+};
+
+// y[n][h/2][w/2][c] = max(0, max of the 2x2 window).  A thread owns one output pixel x N channels (c % N == 0).
+template <typename T, int N>
+__global__ void relu_maxpool2_fwd_kernel(int n, int h, int w, int c, const T* __restrict__ x, T* __restrict__ y) {
+  const int oh = h >> 1, ow = w >> 1, cv = c / N;
+  const size_t total = (size_t)n * oh * ow * cv, rowpitch = (size_t)w * c;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % cv) * N;
+    size_t p = i / cv;
+    const int x2 = (int)(p % ow);
+    p /= ow;
+    const int y2 = (int)(p % oh);
+    const size_t b = p / oh;
+    const T* s = x + ((b * h + 2 * y2) * w + 2 * x2) * c + ch;
+    float a[N], q[N];
+    ClsVec<T, N>::ld(s, a);
+    ClsVec<T, N>::ld(s + c, q);
+#pragma unroll
+    for (int j = 0; j < N; ++j) a[j] = q[j] > a[j] ? q[j] : a[j];
+    ClsVec<T, N>::ld(s + rowpitch, q);
+#pragma unroll
+    for (int j = 0; j < N; ++j) a[j] = q[j] > a[j] ? q[j] : a[j];
+    ClsVec<T, N>::ld(s + rowpitch + c, q);
+#pragma unroll
+    for (int j = 0; j < N; ++j) {
+      a[j] = q[j] > a[j] ? q[j] : a[j];
+      a[j] = a[j] > 0.f ? a[j] : 0.f;
+    }
+    ClsVec<T, N>::st(y + i * N, a);
+  }
+}
+
+// The same thread layout over the OUTPUT pixels: a thread recomputes the first maximum of its window and writes the window's four
+// dx vectors itself -- no atomics, no pre-zeroing.
+template <typename T, int N>
+__global__ void relu_maxpool2_bwd_kernel(int n, int h, int w, int c, const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx,
+                                         int accumulate) {
+  const int oh = h >> 1, ow = w >> 1, cv = c / N;
+  const size_t total = (size_t)n * oh * ow * cv, rowpitch = (size_t)w * c;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int ch = (int)(i % cv) * N;
+    size_t p = i / cv;
+    const int x2 = (int)(p % ow);
+    p /= ow;
+    const int y2 = (int)(p % oh);
+    const size_t b = p / oh;
+    const size_t at = ((b * h + 2 * y2) * w + 2 * x2) * c + ch;
+    const size_t off[4] = {0, (size_t)c, rowpitch, rowpitch + c};          // (0,0), (0,1), (1,0), (1,1)
+    float m[N], q[N], g[N];
+    int k[N];
+    ClsVec<T, N>::ld(x + at, m);
+#pragma unroll
+    for (int j = 0; j < N; ++j) k[j] = 0;
+#pragma unroll
+    for (int t = 1; t < 4; ++t) {
+      ClsVec<T, N>::ld(x + at + off[t], q);
+#pragma unroll
+      for (int j = 0; j < N; ++j)
+        if (q[j] > m[j]) { m[j] = q[j]; k[j] = t; }                        // strictly greater: the first maximum keeps the gradient
+    }
+    ClsVec<T, N>::ld(dy + i * N, g);
+#pragma unroll
+    for (int j = 0; j < N; ++j) g[j] = m[j] > 0.f ? g[j] : 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      float o[N];
+      if (accumulate) {
+        ClsVec<T, N>::ld(dx + at + off[t], o);
+#pragma unroll
+        for (int j = 0; j < N; ++j) o[j] += k[j] == t ? g[j] : 0.f;
+      } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) o[j] = k[j] == t ? g[j] : 0.f;
+      }
+      ClsVec<T, N>::st(dx + at + off[t], o);
+    }
+  }
+}
+
+// Dropout: a thread per Philox quad = four consecutive elements; element i reads word i & 3 of quad base + i / 4 on either route.
+// vec: the bases are aligned for a 4-element access (16 bytes fp32, 8 bytes 16-bit, 4 mask bytes); the last, cut quad goes element by element.
+template <typename T>
+__global__ void dropout_fwd_kernel(size_t count, float keep_prob, float scale, uint64_t seed, const uint64_t* __restrict__ state,
+                                   const T* __restrict__ x, T* __restrict__ y, uint8_t* __restrict__ mask, int vec) {
+  const uint64_t base = state ? state[0] : 0;
+  const size_t nquad = (count + 3) / 4;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (size_t)gridDim.x * blockDim.x) {
+    uint32_t r[4];
+    philox4(base + q, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    bool keep[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) keep[j] = (float)(r[j] >> 8) * (1.0f / 16777216.0f) < keep_prob;
+    const size_t e = q * 4;
+    if (vec && e + 4 <= count) {
+      float v[4];
+      ClsVec<T, 4>::ld(x + e, v);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) v[j] = keep[j] ? v[j] * scale : 0.f;
+      ClsVec<T, 4>::st(y + e, v);
+      *(uchar4*)(mask + e) = make_uchar4(keep[0], keep[1], keep[2], keep[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e + j < count) {
+          Elem<T>::st(y + e + j, keep[j] ? Elem<T>::ld(x + e + j) * scale : 0.f);
+          mask[e + j] = keep[j] ? 1 : 0;
+        }
+    }
+  }
+}
+
+__global__ void dropout_advance_kernel(uint64_t* state, uint64_t n) { state[0] += n; }
+
+template <typename T>
+__global__ void dropout_bwd_kernel(size_t count, float scale, const uint8_t* __restrict__ mask, const T* __restrict__ dy, T* __restrict__ dx,
+                                   int accumulate, int vec) {
+  const size_t nquad = (count + 3) / 4;
+  for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (size_t)gridDim.x * blockDim.x) {
+    const size_t e = q * 4;
+    if (vec && e + 4 <= count) {
+      const uchar4 mk = *(const uchar4*)(mask + e);
+      const bool keep[4] = {mk.x != 0, mk.y != 0, mk.z != 0, mk.w != 0};
+      float g[4], o[4];
+      ClsVec<T, 4>::ld(dy + e, g);
+      if (accumulate) ClsVec<T, 4>::ld(dx + e, o);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float v = keep[j] ? __fmul_rn(g[j], scale) : 0.f;          // rounded here: never contracted into the sum below
+        o[j] = accumulate ? o[j] + v : v;
+      }
+      ClsVec<T, 4>::st(dx + e, o);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e + j < count) {
+          const float v = mask[e + j] ? __fmul_rn(Elem<T>::ld(dy + e + j), scale) : 0.f;
+          Elem<T>::st(dx + e + j, accumulate ? Elem<T>::ld(dx + e + j) + v : v);
+        }
+    }
+  }
+}
+
 static inline bool cls_aligned16(const void* a, const void* b) { return ((((size_t)a) | ((size_t)b)) & 15) == 0; }
 
 static inline int cls_grid(size_t count) {
@@ -429,6 +617,81 @@ int rcgan_augment_cifar(rcgan_ctx* ctx, int n, int n_images, const uint8_t* imag
   RC_REQUIRE(ctx, pad >= 0 && pad < 32, "pad %d", pad);
   RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(augment_cifar_kernel<T>, dim3(cls_grid((size_t)n * 3072)), dim3(256), 0, ctx->stream, n, n_images,
                                                    images_chw_u8, labels_all, index, shift_flip, pad, (T*)y_nhwc, labels_out));
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+// 16-byte accesses along the channel axis: c a multiple of 4 (fp32) / 8 (16-bit) keeps every pixel's vectors aligned when the bases are
+static inline bool cls_pool_vec(int dtype, int c, const void* a, const void* b, const void* d) {
+  return c % (dtype == RCGAN_F32 ? 4 : 8) == 0 && ((((size_t)a) | ((size_t)b) | ((size_t)d)) & 15) == 0;
+}
+
+int rcgan_relu_maxpool2_fwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* x, void* y) {
+  RC_REQUIRE(ctx, n >= 1 && h >= 1 && w >= 1 && c >= 1, "bad shape %dx%dx%dx%d", n, h, w, c);
+  RC_REQUIRE(ctx, h % 2 == 0 && w % 2 == 0, "odd spatial size %dx%d", h, w);
+  RC_REQUIRE(ctx, x && y, "null pointer");
+  RC_REQUIRE(ctx, dtype == RCGAN_F32 || dtype == RCGAN_H16, "bad dtype %d", dtype);
+  const size_t cnt = (size_t)n * (h / 2) * (w / 2) * c;
+  if (!cls_pool_vec(dtype, c, x, y, nullptr)) {
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((relu_maxpool2_fwd_kernel<T, 1>), dim3(cls_grid(cnt)), dim3(256), 0, ctx->stream, n, h, w, c, (const T*)x, (T*)y));
+  } else if (dtype == RCGAN_F32) {
+    hipLaunchKernelGGL((relu_maxpool2_fwd_kernel<float, 4>), dim3(cls_grid(cnt / 4)), dim3(256), 0, ctx->stream, n, h, w, c, (const float*)x, (float*)y);
+  } else {
+    hipLaunchKernelGGL((relu_maxpool2_fwd_kernel<bf16_t, 8>), dim3(cls_grid(cnt / 8)), dim3(256), 0, ctx->stream, n, h, w, c, (const bf16_t*)x, (bf16_t*)y);
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_relu_maxpool2_bwd(rcgan_ctx* ctx, int n, int h, int w, int c, int dtype, const void* x, const void* dy, void* dx, int accumulate) {
+  RC_REQUIRE(ctx, n >= 1 && h >= 1 && w >= 1 && c >= 1, "bad shape %dx%dx%dx%d", n, h, w, c);
+  RC_REQUIRE(ctx, h % 2 == 0 && w % 2 == 0, "odd spatial size %dx%d", h, w);
+  RC_REQUIRE(ctx, x && dy && dx, "null pointer");
+  RC_REQUIRE(ctx, dtype == RCGAN_F32 || dtype == RCGAN_H16, "bad dtype %d", dtype);
+  const size_t cnt = (size_t)n * (h / 2) * (w / 2) * c;
+  const int acc = accumulate ? 1 : 0;
+  if (!cls_pool_vec(dtype, c, x, dy, dx)) {
+    RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL((relu_maxpool2_bwd_kernel<T, 1>), dim3(cls_grid(cnt)), dim3(256), 0, ctx->stream, n, h, w, c, (const T*)x, (const T*)dy, (T*)dx, acc));
+  } else if (dtype == RCGAN_F32) {
+    hipLaunchKernelGGL((relu_maxpool2_bwd_kernel<float, 4>), dim3(cls_grid(cnt / 4)), dim3(256), 0, ctx->stream, n, h, w, c, (const float*)x, (const float*)dy, (float*)dx, acc);
+  } else {
+    hipLaunchKernelGGL((relu_maxpool2_bwd_kernel<bf16_t, 8>), dim3(cls_grid(cnt / 8)), dim3(256), 0, ctx->stream, n, h, w, c, (const bf16_t*)x, (const bf16_t*)dy, (bf16_t*)dx, acc);
+  }
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+// a 4-element access of every tensor of a dropout call: 16 bytes fp32, 8 bytes 16-bit, 4 mask bytes
+static inline int cls_dropout_vec(int dtype, const void* a, const void* b, const void* mask) {
+  const size_t m = dtype == RCGAN_F32 ? 15 : 7;
+  return ((((size_t)a) | ((size_t)b)) & m) == 0 && (((size_t)mask) & 3) == 0;
+}
+
+int rcgan_dropout_fwd(rcgan_ctx* ctx, size_t count, int dtype, float keep_prob, uint64_t seed, void* state, const void* x, void* y, uint8_t* mask) {
+  RC_REQUIRE(ctx, count >= 1, "empty tensor");
+  RC_REQUIRE(ctx, x && y && mask, "null pointer");
+  RC_REQUIRE(ctx, keep_prob > 0.f && keep_prob <= 1.f, "keep_prob %g outside (0, 1]", keep_prob);      // (a NaN fails both)
+  RC_REQUIRE(ctx, dtype == RCGAN_F32 || dtype == RCGAN_H16, "bad dtype %d", dtype);
+  const float scale = 1.0f / keep_prob;
+  const size_t nquad = (count + 3) / 4;
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(dropout_fwd_kernel<T>, dim3(cls_grid(nquad)), dim3(256), 0, ctx->stream, count, keep_prob, scale, seed,
+                                                   (const uint64_t*)state, (const T*)x, (T*)y, mask, cls_dropout_vec(dtype, x, y, mask)));
+  RC_LAUNCH_CHECK(ctx);
+  if (state) {
+    hipLaunchKernelGGL(dropout_advance_kernel, dim3(1), dim3(1), 0, ctx->stream, (uint64_t*)state, (uint64_t)nquad);
+    RC_LAUNCH_CHECK(ctx);
+  }
+  return RCGAN_OK;
+}
+
+int rcgan_dropout_bwd(rcgan_ctx* ctx, size_t count, int dtype, float keep_prob, const uint8_t* mask, const void* dy, void* dx, int accumulate) {
+  RC_REQUIRE(ctx, count >= 1, "empty tensor");
+  RC_REQUIRE(ctx, mask && dy && dx, "null pointer");
+  RC_REQUIRE(ctx, keep_prob > 0.f && keep_prob <= 1.f, "keep_prob %g outside (0, 1]", keep_prob);
+  RC_REQUIRE(ctx, dtype == RCGAN_F32 || dtype == RCGAN_H16, "bad dtype %d", dtype);
+  const float scale = 1.0f / keep_prob;
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(dropout_bwd_kernel<T>, dim3(cls_grid((count + 3) / 4)), dim3(256), 0, ctx->stream, count, scale, mask,
+                                                   (const T*)dy, (T*)dx, accumulate ? 1 : 0, cls_dropout_vec(dtype, dy, dx, mask)));
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }

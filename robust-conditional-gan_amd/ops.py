@@ -927,6 +927,41 @@ def shortcut_a(ctx, x):
     return y
 
 
+def relu_maxpool2(ctx, x):
+    """tf.nn.max_pool(tf.nn.relu(x), ksize 2, strides 2) of the MNIST label classifier, one launch: [n,h,w,c] -> [n,h/2,w/2,c].
+    Backward: the gradient goes to the first maximum of each window (row-major) when it is positive, recomputed from x."""
+    n, h, w, c = x.shape
+    y = ctx.empty((n, h // 2, w // 2, c), x.dtype)
+    ctx.check(ctx.lib.rcgan_relu_maxpool2_fwd(ctx.h, n, h, w, c, x.dtype, _p(x), _p(y)))
+    if _track(ctx, y, x):
+        def bw():
+            if y.grad is None:
+                return
+            dx, acc = grad_of(ctx, x)
+            ctx.check(ctx.lib.rcgan_relu_maxpool2_bwd(ctx.h, n, h, w, c, x.dtype, _p(x), _p(y.grad), _p(dx), acc))
+        ctx.record(bw)
+    return y
+
+
+def dropout(ctx, x, keep_prob, seed, state):
+    """tf.nn.dropout(x, keep_prob): element i is kept (and scaled by 1 / keep_prob) iff the i-th uniform number of the device
+    stream (seed, state) is below keep_prob (rcgan_dropout_fwd).  state: the stream offset on the device (a torch int64 tensor or a
+    DT; advanced by the call on the stream, so a replayed graph draws a fresh mask) or None for offset 0.  The byte mask lives in the
+    step's arena, where the backward closure reads it."""
+    y = ctx.empty(x.shape, x.dtype)
+    mask = DT(ctx.arena.alloc(x.size), (x.size,), "u8", ctx.arena.buf)
+    sp = None if state is None else C.c_void_p(state.data_ptr() if isinstance(state, torch.Tensor) else state.ptr)
+    ctx.check(ctx.lib.rcgan_dropout_fwd(ctx.h, x.size, x.dtype, float(keep_prob), int(seed), sp, _p(x), _p(y), _p(mask)))
+    if _track(ctx, y, x):
+        def bw():
+            if y.grad is None:
+                return
+            dx, acc = grad_of(ctx, x)
+            ctx.check(ctx.lib.rcgan_dropout_bwd(ctx.h, x.size, x.dtype, float(keep_prob), _p(mask), _p(y.grad), _p(dx), acc))
+        ctx.record(bw)
+    return y
+
+
 def diffaugment(ctx, x, u, policy, pool=False):
     """DiffAugment of NHWC images x [n, h, w, 3] (or their flattened rows [n, h*w*3] of square images) under the policy bits
     L.AUG_*: colour jitter, integer translation, cutout, each sample from its row of u [n, 8] (fp32 uniforms in [0, 1), drawn by the

@@ -9,7 +9,9 @@
 
 Per batch: one D update, two G (+ confusion-matrix) updates on the same z (model.py:347-372).  Deviations, all
 logging-only: the console metrics are evaluated only for the lines that are printed; the generated-label accuracy
-needs the frozen MNIST classifier graph, which the reference checkout does not contain, and is reported as skipped;
+needs the frozen MNIST classifier graph, which the reference checkout does not contain, and is reported as skipped
+unless --label_classifier names the asset of the classifier trained on the engine (train_mnist_classifier.py) or
+--label_classifier_fn a callable;
 recover_labels writes its result (recovered label distribution, loss history) as recover.npz into the reference's
 recover_bs<R>_epoch<E>_lr<lr>/<timestamp>/ directory instead of TF summaries.
 Multi-GPU: one rank per GPU under torch.distributed.run; every rank takes batch_size/world rows of each batch.
@@ -83,8 +85,22 @@ def define_flags():
     f.DEFINE_integer("save_every", 700, "checkpoint / sample-grid period in updates (the reference hard-codes 700)")
     f.DEFINE_string("label_classifier_fn", None, "package.module:callable -- the MNIST classifier of the generated-label accuracy "
                     "(float [100,28,28,1] -> 100 class indices); the reference reads ./mnist_dcnn/graph_optimized.pb")
+    f.DEFINE_string("label_classifier", None, "weight asset (.npz) of the MNIST label classifier trained on the engine "
+                    "(python -m rcgan_amd.train_mnist_classifier --out PATH): scores the generated-label accuracy")
     f.DEFINE_integer("sample_epochs", 5, "samples_<epoch>.npy period (the reference hard-codes 5)")
     return f
+
+
+def check_label_classifier_flags(FLAGS):
+    """--label_classifier against --label_classifier_fn, and the asset's class count: raised before any GPU work."""
+    if FLAGS.label_classifier is None:
+        return
+    if FLAGS.label_classifier_fn:
+        raise ValueError('--label_classifier and --label_classifier_fn both name a classifier: give one')
+    from .mnist_classifier import asset_n_classes
+    k = asset_n_classes(FLAGS.label_classifier)
+    if k != DM.Y_DIM:
+        raise ValueError('--label_classifier %s has %d classes, expected %d' % (FLAGS.label_classifier, k, DM.Y_DIM))
 
 
 def dump_script(dirname, script_file, src_dir, file_list):
@@ -107,6 +123,7 @@ def dump_script(dirname, script_file, src_dir, file_list):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     FLAGS = define_flags().parse(argv)
+    check_label_classifier_flags(FLAGS)
     layers = [int(x) for x in FLAGS.concat_y_layers]
     prefix = '' if FLAGS.dir_prefix is None else FLAGS.dir_prefix + '_'
     if FLAGS.checkpoint is None:                                               # main.py:74-80
@@ -181,6 +198,11 @@ def main(argv=None):
     if FLAGS.label_classifier_fn:
         from .inception_score import load_logits_fn
         label_classifier = load_logits_fn(FLAGS.label_classifier_fn)
+    mnist_classifier = None
+    if FLAGS.label_classifier is not None and rank == 0:
+        from .mnist_classifier import MnistLabelClassifier
+        mnist_classifier = MnistLabelClassifier(FLAGS.label_classifier, device=local)
+        label_classifier = mnist_classifier.predict
     start_time = time.time()
     for epoch in range(FLAGS.epoch if do_train else 0):
         batch_idxs = int(min(len(data_X), FLAGS.train_size)) // B
@@ -236,6 +258,8 @@ def main(argv=None):
         final_state = m.state_dict()
         if do_train:
             saver.save(final_state, model_dir, "DCGAN.model", counter)
+    if mnist_classifier is not None:
+        mnist_classifier.close()
     m.ctx.close()
 
     # ---- dcgan.recover_labels(FLAGS) (main.py:140, model.py:494-640): label recovery through the frozen sampler ------------
