@@ -728,6 +728,28 @@ int rcgan_ball_query(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const flo
 int rcgan_poly3_rowsum(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const float* q, const int32_t* q_off, const float* r,
                        const int32_t* r_off, double gamma, double coef0, int exclude_same_row, double* rowsum);
 
+/* ---- per-scale SSIM means of image pairs (csrc/msssim.hip; the intra-class MS-SSIM of msssim.py)
+ * x: n images [n][h][w][c], NHWC, raw pixels 0..255 (uint8, DEVICE); pairs: int32 DEVICE array [n_pairs][2] of image indices.
+ * For pair p = (i, j) and scale l = 0..4 (the image, then four times the 2 x 2 mean at stride 2 anchored at (0, 0), the last row /
+ * column averaged with itself where a size is odd: sizes ceil(h_l / 2)):
+ *   out[p][0][l] = the mean over positions and channels of the contrast-structure map v1 / v2,
+ *   out[p][1][l] = the mean of the full SSIM map (2 mu_i mu_j + c1) v1 / ((mu_i^2 + mu_j^2 + c1) v2),
+ * v1 = 2 sigma_ij + c2, v2 = sigma_ii + sigma_jj + c2, c1 = (0.01 * 255)^2, c2 = (0.03 * 255)^2, the local moments taken under a
+ * Gaussian window of s = min(11, h_l, w_l) taps per side with sigma = 1.5 s / 11 (centres k - (s - 1) / 2, normalised), 'valid'
+ * positions only: _SSIMForMultiScale of the reference's cifar10/common/msssim.py for a batch of one, level by level as its
+ * MultiScaleSSIM walks them.  The combination over scales and pairs is the host's (msssim.combine).
+ * A pair with an index outside [0, n) gets nan in its ten outputs and touches nothing else; there is never an access outside the
+ * tensors.
+ * Arithmetic: fp32, the taps computed in float64 on the host; variances and the covariance are sums of non-negative (for the
+ * covariance: Cauchy-Schwarz bounded) centred terms, never a difference of two second moments, and every sum is taken in an order
+ * fixed by the launch geometry (no floating-point atomics): the same bits on every run, eager or replayed.
+ * |out - exact| <= 1e-4 for every pair and scale (derivation: the header of csrc/msssim.hip); identical images give exactly 1.
+ * One launch on the context's stream (one workgroup per pair), no workspace, no host synchronisation, legal inside a captured graph.
+ * c 1 or 3, 16 <= h, w <= 32 (five levels exist from 16 on; both images, their pyramids and one channel's filtered fields stay in
+ * LDS up to 32), n, n_pairs >= 1, non-NULL pointers (pairs and out 4-byte aligned): anything else is RCGAN_EINVALID_ARG before any
+ * launch (a NULL context included, so the checks need no device). */
+int rcgan_msssim_pairs(rcgan_ctx* ctx, int n, int h, int w, int c, int n_pairs, const uint8_t* x, const int32_t* pairs, float* out);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

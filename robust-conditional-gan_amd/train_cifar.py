@@ -81,6 +81,11 @@ def define_flags():
     f.DEFINE_integer("kid_samples", 10000, "generated samples per kernel-distance evaluation (hundreds), balanced over the classes")
     f.DEFINE_integer("kid_real_samples", 0, "real images behind the kernel distance (0: the whole training set)")
     f.DEFINE_integer("kid_subset_size", 1000, "rows per subset of the kernel distance's mean +- std over subsets (at least 2)")
+    f.DEFINE_integer("msssim_freq", 0, "period (iterations) of the intra-class MS-SSIM of the generated IMAGES (random pairs per class, "
+                     "beside the same number on the clean training set); also taken at the end of training (0: off)")
+    f.DEFINE_integer("msssim_samples", 10000, "generated samples per MS-SSIM evaluation (hundreds), balanced over the classes")
+    f.DEFINE_integer("msssim_real_samples", 0, "real images behind the real MS-SSIM values (0: the whole training set)")
+    f.DEFINE_integer("msssim_pairs", 1000, "image pairs per class, and of the pooled value (at least 1)")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -132,6 +137,8 @@ def main(argv=None):
         raise ValueError('--prdc_freq and --prdc_real_samples must not be negative, --prdc_samples at least 100, --prdc_k in 1..16')
     if FLAGS.kid_freq < 0 or FLAGS.kid_real_samples < 0 or (FLAGS.kid_freq > 0 and (FLAGS.kid_samples < 100 or FLAGS.kid_subset_size < 2)):
         raise ValueError('--kid_freq and --kid_real_samples must not be negative, --kid_samples at least 100, --kid_subset_size at least 2')
+    if FLAGS.msssim_freq < 0 or FLAGS.msssim_real_samples < 0 or (FLAGS.msssim_freq > 0 and (FLAGS.msssim_samples < 100 or FLAGS.msssim_pairs < 1)):
+        raise ValueError('--msssim_freq and --msssim_real_samples must not be negative, --msssim_samples at least 100, --msssim_pairs at least 1')
     N_CLASSES, DATA = dataset_setup(FLAGS)
     if FLAGS.label_classifier is not None:
         # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
@@ -198,7 +205,7 @@ def main(argv=None):
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
-    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq / --kid_freq
+    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq / --kid_freq / --msssim_freq
     if FLAGS.synthetic:
         tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
         clean_train = (tx, np.array(ty))
@@ -356,6 +363,31 @@ def main(argv=None):
         plot.plot('kernel_distance_subsets', r["subset_mean"])
         return r
 
+    # intra-class MS-SSIM of the images themselves (msssim.py): random pairs per class, beside the same number on the CLEAN training set
+    MSSSIM_FREQ = FLAGS.msssim_freq
+    msssim_state = {"ev": None}
+
+    def msssim_values(confusion_matrix=None):
+        from . import msssim as MS
+        ev = msssim_state["ev"]
+        if ev is None:
+            ev = msssim_state["ev"] = MS.MsssimEvaluator(N_CLASSES, pairs=FLAGS.msssim_pairs, device=local)
+            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
+            n_real = FLAGS.msssim_real_samples if FLAGS.msssim_real_samples > 0 else len(rx)
+            real = ev.prepare_real(rx[:n_real], ry[:n_real])
+            logging.info('msssim real set: {} images, {} pairs per class, intra-class {}'.format(
+                min(n_real, len(rx)), FLAGS.msssim_pairs, real["intra_class_msssim"]))
+        r = ev.evaluate(*balanced_samples(FLAGS.msssim_samples, confusion_matrix))
+        used = N_CLASSES - len(r["left_out"]) - len(r["undefined"])
+        logging.info('msssim: {}'.format(r["msssim"]))
+        logging.info('intra_class_msssim: {} +- {} ({} of {} classes), real {}'.format(
+            r["intra_class_msssim"], r["intra_class_msssim_se"], used, N_CLASSES, r["intra_class_msssim_real"]))
+        logging.info('msssim_classes_above_real: {} of {}'.format(r["classes_above_real"], r["classes_compared"]))
+        plot.plot('msssim', r["msssim"])
+        plot.plot('intra_class_msssim', r["intra_class_msssim"])
+        plot.plot('msssim_classes_above_real', r["classes_above_real"])
+        return r
+
     def inception_score(n):
         # gan_resnet.py:836-845: 100 samples with uniformly random labels per Generator call, n / 100 calls
         from .inception_score import get_inception_score, samples_as_the_reference_feeds_them
@@ -458,6 +490,10 @@ def main(argv=None):
             logging.info('starting calculating kernel distance.')
             kernel_distances()
             logging.info('finished calculating kernel distance.')
+        if rank == 0 and MSSSIM_FREQ > 0 and iteration % MSSSIM_FREQ == MSSSIM_FREQ - 1:
+            logging.info('starting calculating intra-class msssim.')
+            msssim_values()
+            logging.info('finished calculating intra-class msssim.')
         ECE = max(FLAGS.early_checkpoint_every, 1)
         if rank == 0 and ((iteration < 500 and iteration % ECE == ECE - 1) or (iteration % 1000 == 999)):      # :1007-1014
             drain_losses()
@@ -486,12 +522,19 @@ def main(argv=None):
         logging.info('starting calculating %skernel distance.' % ('min. permuted ' if cm is not None else ''))
         kernel_distances(cm)
         logging.info('finished calculating kernel distance.')
+    if rank == 0 and MSSSIM_FREQ > 0:
+        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
+        logging.info('starting calculating %sintra-class msssim.' % ('min. permuted ' if cm is not None else ''))
+        msssim_values(cm)
+        logging.info('finished calculating intra-class msssim.')
     drain_losses()
     if rank == 0 and ITERS:
         plot.dir_flush(DIR)
         saver.save(m.state_dict(), CHECKPOINT_DIR, 'model.ckpt', max(ITERS - 1, 0))
     if acc_state["clf"] is not None:
         acc_state["clf"].close()
+    if msssim_state["ev"] is not None:
+        msssim_state["ev"].close()
     if kid_state["ev"] is not None:
         kid_state["ev"].close()
     if manifold_state["ev"] is not None:
