@@ -750,6 +750,29 @@ int rcgan_poly3_rowsum(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const f
  * launch (a NULL context included, so the checks need no device). */
 int rcgan_msssim_pairs(rcgan_ctx* ctx, int n, int h, int w, int c, int n_pairs, const uint8_t* x, const int32_t* pairs, float* out);
 
+/* ---- nearest reference image of every query image, in pixel space (csrc/nn_u8.hip; the memorisation metrics of neighbours.py)
+ * q[nq][d], r[nr][d]: raw pixels 0..255 (uint8, DEVICE), rows in any fixed pixel order that is the same on both sides.
+ *   best[i] = min over the reference rows j of query row i's segment of ((uint64)dist2(i, j) << 32 | (uint32)j),
+ *   dist2(i, j) = sum_k (q[i][k] - r[j][k])^2, EXACT (what int64 arithmetic gives), j the global reference row.
+ * The packing is the tie rule: among equally near rows the lowest index wins.  exclude_same_row != 0 leaves out j == i (global row
+ * indices: meaningful when q and r are the same rows and offsets).  0xFFFFFFFFFFFFFFFF where no candidate exists: an empty reference
+ * segment, a one-row segment with exclusion.
+ * Segments as above: int32 DEVICE arrays q_off / r_off [n_seg + 1], every offset clamped to [0, n], a decreasing pair an empty
+ * segment, segment s of the queries meets only segment s of the references, rows outside every segment are not written, and there is
+ * never an access outside the tensors.
+ * Arithmetic: both operands centred (x ^ 0x80 read as int8 is x - 128), dist2 = |a|^2 + |b|^2 - 2 a.b in int32 with the inner
+ * products on the integer matrix cores (v_mfma_i32_32x32x32_i8); no intermediate reaches 2^31 for d <= 12288 (derivation: the header
+ * of csrc/nn_u8.hip).  A minimum of integers does not depend on the merge order (the reference range of a query is split over
+ * workgroups that merge with one 64-bit integer atomic minimum per row; no floating-point atomics): the same bits on every run, eager
+ * or replayed, and for every way the work is split.
+ * Two launches (fill of the rows inside a segment, kernel) on the context's stream, no workspace, no host synchronisation, legal
+ * inside a captured graph.
+ * 16 <= d <= 12288 and d a multiple of 16, q and r 16-byte aligned (rows are 16-byte loads), nq, nr >= 1, 1 <= n_seg <= 1024,
+ * non-NULL pointers (offsets 4-byte, best 8-byte aligned): anything else is RCGAN_EINVALID_ARG before any launch (a NULL context
+ * included, so the checks need no device). */
+int rcgan_nn_u8(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const uint8_t* q, const int32_t* q_off, const uint8_t* r,
+                const int32_t* r_off, int exclude_same_row, uint64_t* best);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

@@ -86,6 +86,10 @@ def define_flags():
     f.DEFINE_integer("msssim_samples", 10000, "generated samples per MS-SSIM evaluation (hundreds), balanced over the classes")
     f.DEFINE_integer("msssim_real_samples", 0, "real images behind the real MS-SSIM values (0: the whole training set)")
     f.DEFINE_integer("msssim_pairs", 1000, "image pairs per class, and of the pooled value (at least 1)")
+    f.DEFINE_integer("neighbours_freq", 0, "period (iterations) of the pixel-space nearest-training-image metrics (copy rate, nearest-neighbour "
+                     "distance z, leave-one-out 1-NN accuracy: does the generator memorise?); also taken at the end of training (0: off)")
+    f.DEFINE_integer("neighbours_samples", 10000, "generated samples per nearest-neighbour evaluation (hundreds), balanced over the classes")
+    f.DEFINE_integer("neighbours_real_samples", 0, "training images the neighbours are searched in (0: the whole training set)")
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -126,6 +130,15 @@ def clean_training_set(FLAGS, data_dir):
     return np.concatenate([p[0] for p in parts], axis=0), np.concatenate([p[1] for p in parts], axis=0)
 
 
+def clean_heldout_set(FLAGS, data_dir):
+    """Real images the generator never sees, [N,3072] (CHW rows) with their CLEAN labels: the data set's test split."""
+    if FLAGS.dataset == "cifar100":
+        vx, vy = D.unpickle100(os.path.join(data_dir, 'test'), FLAGS.coarse_labels)
+    else:
+        vx, vy = D.unpickle(os.path.join(data_dir, 'test_batch'))
+    return np.asarray(vx), np.asarray(vy)
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     FLAGS = define_flags().parse(argv)
@@ -139,6 +152,8 @@ def main(argv=None):
         raise ValueError('--kid_freq and --kid_real_samples must not be negative, --kid_samples at least 100, --kid_subset_size at least 2')
     if FLAGS.msssim_freq < 0 or FLAGS.msssim_real_samples < 0 or (FLAGS.msssim_freq > 0 and (FLAGS.msssim_samples < 100 or FLAGS.msssim_pairs < 1)):
         raise ValueError('--msssim_freq and --msssim_real_samples must not be negative, --msssim_samples at least 100, --msssim_pairs at least 1')
+    if FLAGS.neighbours_freq < 0 or FLAGS.neighbours_real_samples < 0 or (FLAGS.neighbours_freq > 0 and FLAGS.neighbours_samples < 100):
+        raise ValueError('--neighbours_freq and --neighbours_real_samples must not be negative, --neighbours_samples at least 100')
     N_CLASSES, DATA = dataset_setup(FLAGS)
     if FLAGS.label_classifier is not None:
         # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
@@ -206,10 +221,12 @@ def main(argv=None):
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq / --kid_freq / --msssim_freq
+    clean_heldout = None               # (images, clean labels) of real images outside the training set: the held-out side of --neighbours_freq
     if FLAGS.synthetic:
         tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
         clean_train = (tx, np.array(ty))
         vx, vy = D.synthetic_cifar(10000, 1235, FLAGS.synthetic_kind, N_CLASSES)
+        clean_heldout = (vx, np.array(vy))
         train_gen = D.cifar_generator(tx, ty, BATCH_SIZE, C_ALPHA)
         dev_gen = D.cifar_generator(vx, vy, BATCH_SIZE, C_ALPHA)
     elif FLAGS.dataset == "cifar100":
@@ -388,6 +405,39 @@ def main(argv=None):
         plot.plot('msssim_classes_above_real', r["classes_above_real"])
         return r
 
+    # nearest training images in pixel space (neighbours.py): does the generator memorise?  Against the CLEAN training set, beside the
+    # same numbers of a held-out real set
+    NEIGHBOURS_FREQ = FLAGS.neighbours_freq
+    neighbours_state = {"ev": None}
+
+    def neighbour_metrics(iteration, confusion_matrix=None):
+        from . import neighbours as NB
+        ev = neighbours_state["ev"]
+        if ev is None:
+            ev = neighbours_state["ev"] = NB.NeighbourEvaluator(N_CLASSES, device=local)
+            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
+            hx, hy = clean_heldout if clean_heldout is not None else clean_heldout_set(FLAGS, DATA)
+            n_real = FLAGS.neighbours_real_samples if FLAGS.neighbours_real_samples > 0 else len(rx)
+            real = ev.prepare_real(rx[:n_real], ry[:n_real], hx, hy)
+            logging.info('neighbours real set: {} training images, {} held-out images, held-out copy rate {}'.format(
+                min(n_real, len(rx)), len(hx), real["copy_rate_heldout"]))
+        r = ev.evaluate(*balanced_samples(FLAGS.neighbours_samples, confusion_matrix))
+        logging.info('copy_rate: {} (held-out {})'.format(r["copy_rate"], r["copy_rate_heldout"]))
+        logging.info('nn_distance_z: {}, intra-class {} ({} of {} classes)'.format(
+            r["nn_distance_z"], r["intra_class_nn_distance_z"], r["classes_used"], N_CLASSES))
+        logging.info('loo_1nn_accuracy: {} (real {}, generated {})'.format(
+            r["loo_1nn_accuracy"], r["loo_1nn_accuracy_real"], r["loo_1nn_accuracy_generated"]))
+        plot.plot('copy_rate', r["copy_rate"])
+        plot.plot('nn_distance_z', r["nn_distance_z"])
+        plot.plot('loo_1nn_accuracy', r["loo_1nn_accuracy"])
+        # the fixed grid's samples, each beside its nearest training image
+        grid = ((m.sample(fixed_labels, fixed_noise) + 1.) * (255. / 2)).astype('int32').reshape((100, 32, 32, 3))
+        _, nearest = ev.nearest_training_rows(grid)
+        found = ev.real["images"][np.maximum(nearest, 0)].reshape((100, 32, 32, 3))          # (kept as NHWC rows by the evaluator)
+        pairs = np.stack([np.clip(grid, 0, 255).astype(np.uint8), found], axis=1).reshape((200, 32, 32, 3))
+        save_images(pairs, os.path.join(DIR, 'neighbours_{}.png'.format(iteration)))
+        return r
+
     def inception_score(n):
         # gan_resnet.py:836-845: 100 samples with uniformly random labels per Generator call, n / 100 calls
         from .inception_score import get_inception_score, samples_as_the_reference_feeds_them
@@ -494,6 +544,10 @@ def main(argv=None):
             logging.info('starting calculating intra-class msssim.')
             msssim_values()
             logging.info('finished calculating intra-class msssim.')
+        if rank == 0 and NEIGHBOURS_FREQ > 0 and iteration % NEIGHBOURS_FREQ == NEIGHBOURS_FREQ - 1:
+            logging.info('starting calculating nearest training images.')
+            neighbour_metrics(iteration)
+            logging.info('finished calculating nearest training images.')
         ECE = max(FLAGS.early_checkpoint_every, 1)
         if rank == 0 and ((iteration < 500 and iteration % ECE == ECE - 1) or (iteration % 1000 == 999)):      # :1007-1014
             drain_losses()
@@ -527,12 +581,19 @@ def main(argv=None):
         logging.info('starting calculating %sintra-class msssim.' % ('min. permuted ' if cm is not None else ''))
         msssim_values(cm)
         logging.info('finished calculating intra-class msssim.')
+    if rank == 0 and NEIGHBOURS_FREQ > 0:
+        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
+        logging.info('starting calculating %snearest training images.' % ('min. permuted ' if cm is not None else ''))
+        neighbour_metrics('final', cm)
+        logging.info('finished calculating nearest training images.')
     drain_losses()
     if rank == 0 and ITERS:
         plot.dir_flush(DIR)
         saver.save(m.state_dict(), CHECKPOINT_DIR, 'model.ckpt', max(ITERS - 1, 0))
     if acc_state["clf"] is not None:
         acc_state["clf"].close()
+    if neighbours_state["ev"] is not None:
+        neighbours_state["ev"].close()
     if msssim_state["ev"] is not None:
         msssim_state["ev"].close()
     if kid_state["ev"] is not None:
