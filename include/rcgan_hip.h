@@ -326,8 +326,15 @@ int rcgan_bn_fwd_segments(rcgan_ctx* ctx, int nseg, int n_per_seg, int rows_per_
  * (= or += by accumulate); dx = or += by accumulate_dx.  y is the forward output (activation mask).
  * n_labels <= 16: per-label accumulators in registers / LDS (the fused, tree and generic paths).  17 .. 1024: per-sample partials
  * in ws, then a deterministic fp64 reduction per (label, channel) in sample order; a label absent from the batch gets 0 (left
- * untouched under accumulate).  ws: rcgan_bn_workspace_bytes_labels(n*rows_per_sample, c, n_labels); the per-sample route uses
- * (n*2*c + 4*c) floats of it (within rcgan_bn_workspace_bytes for n <= 8192). */
+ * untouched under accumulate).  ws: rcgan_bn_workspace_bytes_labels(n*rows_per_sample, c, n_labels).  With labels EVERY route keeps at
+ * least one partial row [2*c] per sample.  In floats: (n + 1)*2*c on the scalar and the power-of-two-c routes, (n + 2)*2*c on the
+ * per-sample route (n_labels > 16), (n + 2)*2*c + n_labels*c where the c % 8 == 0 route holds its tables.  The query returns at least
+ * 8210*2*c + 64 floats (exactly that while n*rows_per_sample <= 4094*512; + 2*(n_labels - 16)*c past 16 labels), which covers every
+ * n <= 8192.  Past it, with exactly the query's bytes, at the earliest: the c % 8 == 0 route no longer holds its tables, and the call
+ * takes the scalar kernels, from the first n > 8208 - n_labels/2 + 32/c (16 labels, c >= 40: 8201); the call returns
+ * RCGAN_EWORKSPACE_TOO_SMALL before it launches anything from n = 8210 + floor(32/c) for n_labels <= 16 (c >= 33: 8210, c = 17 .. 32:
+ * 8211) and from n = 8209 + (n_labels - 16) + floor(32/c) for n_labels > 16, and its message names the bytes it needs
+ * (tests/tools/bn_plan_sweep.cpp finds these n for channel counts on either side of each step). */
 int rcgan_bn_bwd(rcgan_ctx* ctx, int n, int rows_per_sample, int c, int n_labels, int dtype,
                  const void* x, const void* y, const void* dy, const int32_t* labels,
                  const float* gamma, const float* mean, const float* rstd, int act,

@@ -1087,9 +1087,8 @@ static int bn_check_args(rcgan_ctx* ctx, const BnShape& s, const int32_t* labels
              s.nseg, s.n, s.rows_per_sample, s.c);
   RC_REQUIRE(ctx, s.n_labels >= 1 && s.n_labels <= BN_MAX_LABELS_WIDE, "n_labels %d (1 .. %d)", s.n_labels, BN_MAX_LABELS_WIDE);
   RC_REQUIRE(ctx, labels != nullptr || s.n_labels == 1, "labels required for n_labels > 1");
-  // a segment's rows are an int in the kernels' arguments, element offsets 64-bit
-  RC_REQUIRE(ctx, s.rows() <= INT32_MAX && s.nseg <= INT64_MAX / (s.rows() * s.c), "%d x %ld rows x %d channels exceed the index types", s.nseg,
-             s.rows(), s.c);
+  // (bn_plan.h: a segment's rows are an int in the kernels' arguments, the fused apply's chunk index has 32 bits)
+  RC_REQUIRE(ctx, bn_index_ok(s), "%d x %ld rows x %d channels exceed the index types", s.nseg, s.rows(), s.c);
   for (const void* t : tensors) RC_REQUIRE(ctx, t != nullptr, "null tensor");
   return RCGAN_OK;
 }
@@ -1366,7 +1365,7 @@ int rcgan_bn_infer(rcgan_ctx* ctx, int rows, int c, int dtype, const void* x, co
   RC_REQUIRE(ctx, rows >= 1 && c >= 1, "bad shape: %d rows x %d channels", rows, c);
   RC_REQUIRE(ctx, x && gamma && beta && mm && mv && y, "null tensor");
   long total = (long)rows * c;
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_kernel<T>, dim3(bn_apply_grid(total, 0)), dim3(256), 0, ctx->stream, total, c,
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_kernel<T>, dim3(bn_apply_grid(total)), dim3(256), 0, ctx->stream, total, c,
                                                    (const T*)x, gamma, beta, mm, mv, eps, act, (T*)y));
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
@@ -1379,7 +1378,7 @@ int rcgan_bn_infer_bwd(rcgan_ctx* ctx, int rows, int c, int dtype, const void* y
   RC_REQUIRE(ctx, rows >= 1 && c >= 1, "bad shape: %d rows x %d channels", rows, c);
   RC_REQUIRE(ctx, dy && gamma && mv && dx && (y || act == RCGAN_ACT_NONE), "null tensor");
   long total = (long)rows * c;
-  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_bwd_kernel<T>, dim3(bn_apply_grid(total, 0)), dim3(256), 0, ctx->stream, total, c,
+  RC_DISPATCH_DTYPE(ctx, dtype, hipLaunchKernelGGL(bn_infer_bwd_kernel<T>, dim3(bn_apply_grid(total)), dim3(256), 0, ctx->stream, total, c,
                                                    (const T*)y, (const T*)dy, gamma, mv, eps, act, (T*)dx, accumulate));
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;

@@ -6,8 +6,9 @@
 // ---------  --------------------------------------------  ----------------------------------------  ----------------------------------------  ------------------
 // BN_TREE    bn_tree_reduce_kernel, then the fused apply   c = 64 .. 2048, a power of two, and        partial [nseg][ng][2c] | cpart [nseg]      1 + 1 / 1 + 1
 //            (two-level arrival tree: groups -> clusters   rows * c >= RCGAN_BN_TREE_MIN (off unless  [ncl][2c] | PQ [2c]
-//            -> finisher; a workgroup streams whole rows)  set); labelled backward: label staging
-//                                                          <= 96 KiB and n <= 8000
+//            -> finisher; a workgroup streams whole rows)  set), counter lines for every cluster;
+//                                                          labelled backward: label staging <= 96 KiB,
+//                                                          groups + samples <= 8192 partial rows
 // BN_COLUMN  bn_fused_reduce_kernel, bn_apply_fused_kernel c = 64 .. 2048, a power of two             partial [nseg][ng][2c] | (bwd) PQ [2c]     1 + 1 / 1 + 1
 //            / bn_bwd_apply_fused_kernel (64-channel
 //            column blocks, last arrival combines)
@@ -49,7 +50,7 @@
 // ... and the tree kernel's own
 #define BN_TREE_CLUSTER 16                     // groups per cluster (labelled backward: the groups of one sample instead)
 #define BN_TREE_LABEL_STAGE_BYTES (96 * 1024)  // the finisher stages [n_labels][2c] floats per slice in LDS
-#define BN_TREE_MAX_LABELLED_N 8000            // one cluster per sample: below the BN_TREE_LINES - 1 clusters of a launch
+#define BN_WS_PARTIAL_ROWS 8192                // partial rows [2c] that rcgan_bn_workspace_bytes counts at the least (2 x 4096)
 #define BN_TREE_MAX_LDS (128 * 1024)
 #define BN_APPLY_MAX_WGS 8192                  // grid-stride apply kernels
 
@@ -145,8 +146,11 @@ static inline BnChoice bn_choose(const BnShape& s) {
   if (s.op == BN_OP_BWD && s.n_labels > MAX_LABELS) return {BN_WIDE, false};
   if (reduces && bn_tree_ok(s.rows(), s.c)) {
     const bool labelled = s.op == BN_OP_BWD && s.labels;
-    if (!labelled || ((size_t)s.n_labels * 2 * s.c * sizeof(float) <= BN_TREE_LABEL_STAGE_BYTES && s.n <= BN_TREE_MAX_LABELLED_N))
-      return {BN_TREE, false};
+    const BnPlan t = bn_plan(s, BN_TREE);
+    // one counter line per cluster and one per launch, for every segment; with labels a cluster is a sample, and the group and
+    // cluster partials together stay within the partial rows the workspace query counts
+    const bool fits = (long)s.nseg * (t.nclusters + 1L) <= BN_TREE_LINES && (!labelled || (long)t.ngroups + t.nclusters <= BN_WS_PARTIAL_ROWS);
+    if (fits && (!labelled || (size_t)s.n_labels * 2 * s.c * sizeof(float) <= BN_TREE_LABEL_STAGE_BYTES)) return {BN_TREE, false};
   }
   if (fused) return {BN_COLUMN, false};
   // 8-wide kernels; their apply needs room for the affine tables (the statistics pass has none)
@@ -165,13 +169,22 @@ static inline long bn_group_rows(long rows, int c, int dtype) {
   return g;
 }
 
-static inline int bn_apply_grid(long items, int chunks_per_row) {
+// fused apply: the stride (b * 256) must be a multiple of the chunks per row.  It always is: bn_fused_ok admits powers of two up to
+// BN_COLUMN_MAX_C = 2048 channels, so the chunks per row are a power of two <= 256 (tests/tools/bn_plan_sweep.cpp checks every plan)
+static_assert(BN_COLUMN_MAX_C / 8 <= 256, "chunks per row of the fused apply divide the 256 threads of a workgroup");
+static inline int bn_apply_grid(long items) {
   long b = (items + 255) / 256;
   if (b > BN_APPLY_MAX_WGS) b = BN_APPLY_MAX_WGS;
-  // fused apply: the stride (b * 256) must be a multiple of the chunks per row
-  if (chunks_per_row > 256) { const long m = chunks_per_row / 256; b = (b + m - 1) / m * m; }
   if (b < 1) b = 1;
   return (int)b;
+}
+
+// What the index types take: a segment's rows are an int in the kernels' arguments, element offsets 64-bit; the fused apply kernels
+// count a segment's 8-element chunks in 32 bits (the statistics call applies nothing)
+static inline bool bn_index_ok(const BnShape& s) {
+  const long rows = s.rows();
+  if (rows > INT32_MAX || s.nseg > INT64_MAX / (rows * s.c)) return false;
+  return s.op == BN_OP_STATS || !bn_fused_ok(s.c) || rows * s.c / 8 <= INT32_MAX;
 }
 
 // Geometry, workspace layout and need of `route` for the call `s`.
@@ -268,6 +281,6 @@ static inline BnPlan bn_plan(const BnShape& s, BnRoute route) {
     p.apply = bn_fused_ok(c) ? BN_COLUMN : BN_SCALAR;                                  // (BN_WIDE takes any channel count)
   }
   p.apply_items = p.apply == BN_SCALAR ? rows * c : rows * c / 8;
-  p.apply_grid = bn_apply_grid(p.apply_items, p.apply == BN_COLUMN ? c / 8 : 0);
+  p.apply_grid = bn_apply_grid(p.apply_items);
   return p;
 }
