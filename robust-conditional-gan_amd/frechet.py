@@ -15,15 +15,14 @@ import ctypes as C
 import hashlib
 import json
 import os
-import sys
 import zipfile
 
 import numpy as np
 
 from . import _lib as L
+from .evaluators import N_CALIBRATION, FeatureEvaluator, as_nhwc, permuted_labels, standalone  # noqa: F401  (permuted_labels: re-exported)
 
 CACHE_NAME = "frechet_real_stats.npz"
-N_CALIBRATION = 1000
 
 # count [K], mean [K,d], cov [K,d,d] (unbiased, n - 1; zeros for a class with fewer than 2 rows), pooled = (n, mean [d], cov [d,d]) of
 # all accepted rows, rejected = rows whose label was outside [0, K); float64
@@ -193,36 +192,13 @@ def real_statistics(path, key, compute):
     return mom, pairs, False
 
 
-def as_nhwc(images):
-    """[n,3072] CHW rows (the data set's layout) or [n,32,32,3] -> [n,32,32,3]."""
-    x = np.asarray(images)
-    if x.ndim == 2 and x.shape[1] == 3072:
-        x = x.reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
-    return x
+class FrechetEvaluator(FeatureEvaluator):
+    """The metric end to end for one run: a LabelClassifier (its own unless ``clf`` hands one over), the real set's statistics taken
+    once (``prepare_real``, which always sets the classifier's calibration: computed here or restored from the cache), then
+    ``evaluate`` per generated set."""
 
-
-def permuted_labels(labels, confusion_matrix):
-    """rcgan-u: conditioning labels mapped through the arg-max permutation of the learned matrix, exactly as
-    eval_cifar.generated_label_accuracy maps them."""
-    labels = np.asarray(labels)
-    cm = np.asarray(confusion_matrix)
-    perm = np.zeros_like(cm, dtype=int)
-    perm[np.arange(cm.shape[0]), np.argmax(cm, axis=-1)] = 1
-    onehot = np.zeros([labels.shape[0], cm.shape[0]], dtype=float)
-    onehot[np.arange(labels.shape[0]), labels] = 1
-    return np.argmax(onehot.dot(perm), axis=-1)
-
-
-class FrechetEvaluator:
-    """The metric end to end for one run: a LabelClassifier of its own (``asset``; its class count need not be the run's -- only
-    the 64-wide feature is used), the real set's statistics taken once (``prepare_real``), then ``evaluate`` per generated set."""
-
-    def __init__(self, n_classes, asset=None, device=0, chunk=1000):
-        from .eval_cifar import ASSET, LabelClassifier
-        self.asset = ASSET if asset is None else asset
-        self.n_classes, self.chunk = int(n_classes), int(chunk)
-        self.clf = LabelClassifier(device, asset=self.asset)
-        self.real = None
+    def __init__(self, n_classes, asset=None, device=0, chunk=1000, clf=None):
+        super().__init__(n_classes, asset, device, chunk, clf)
         self.reused = False
 
     def moments(self, images, labels):
@@ -251,9 +227,6 @@ class FrechetEvaluator:
             raise RuntimeError("FrechetEvaluator.evaluate needs prepare_real() first")
         return evaluate(self.real, self.moments(as_nhwc(images), labels), min_count)
 
-    def close(self):
-        self.clf.close()
-
 
 def json_ready(result):
     out = dict(result)
@@ -265,29 +238,10 @@ def json_ready(result):
 
 
 def main(argv=None):
-    from .host import Flags
-    f = Flags()
-    f.DEFINE_string("real", None, ".npz with images, labels: the reference set (its first 1000 images calibrate the features)")
-    f.DEFINE_string("generated", None, ".npz with images, labels: the set to score")
-    f.DEFINE_string("label_classifier", None, "weight asset of the feature network; default: the built-in CIFAR-10 network")
-    f.DEFINE_integer("n_classes", 0, "class count of the labels; 0: the largest label of either file + 1")
-    f.DEFINE_integer("min_count", 2, "classes with fewer samples on either side are left out")
-    FLAGS = f.parse(sys.argv[1:] if argv is None else argv)
-    if FLAGS.real is None or FLAGS.generated is None:
-        raise ValueError("flags real and generated are required")
-    with np.load(FLAGS.real) as z:
-        rx, ry = z["images"], z["labels"]
-    with np.load(FLAGS.generated) as z:
-        gx, gy = z["images"], z["labels"]
-    K = FLAGS.n_classes if FLAGS.n_classes > 0 else int(max(ry.max(), gy.max())) + 1
-    ev = FrechetEvaluator(K, asset=FLAGS.label_classifier, device=int(os.environ.get("LOCAL_RANK", "0")))
-    try:
-        ev.prepare_real(rx, ry)
-        result = json_ready(ev.evaluate(gx, gy, FLAGS.min_count))
-    finally:
-        ev.close()
-    print(json.dumps(result))
-    return result
+    return standalone(argv, (("real", "the reference set (its first 1000 images calibrate the features)"), ("generated", "the set to score")),
+                      (("min_count", 2, "classes with fewer samples on either side are left out"),),
+                      lambda K, FLAGS, device: FrechetEvaluator(K, asset=FLAGS.label_classifier, device=device), json_ready, features=True,
+                      evaluate=lambda ev, FLAGS, x, y: ev.evaluate(x, y, FLAGS.min_count))
 
 
 if __name__ == '__main__':

@@ -20,14 +20,12 @@ The numbers are built around the engine's own small classifier: they are NOT com
 Stand-alone:  python -m rcgan_amd.kid --real a.npz --generated b.npz [--n_classes K] [--subset_size 1000] [--label_classifier asset]
 (each file: ``images`` [n,32,32,3] or [n,3072] CHW rows of raw pixels 0..255, ``labels`` [n]) prints the same numbers as one JSON line."""
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-from .frechet import N_CALIBRATION, as_nhwc, permuted_labels  # noqa: F401  (permuted_labels: for the callers of this module)
-from .manifold import MAX_SEGMENTS, FeatureSet, _check_rows, _host
+from .evaluators import (N_CALIBRATION, FeatureEvaluator, FeatureSet, as_nhwc, check_rows, download, permuted_labels,  # noqa: F401
+                         standalone)                    # (FeatureSet, as_nhwc, permuted_labels: re-exported for the callers of this module)
+from .manifold import MAX_SEGMENTS
 
 COEF0 = 1.0                              # with gamma = 1 / d: the kernel of the Kernel Inception Distance
 
@@ -89,8 +87,8 @@ def poly3_rowsum(ctx, q, q_off, r, r_off, exclude_same_row=False):
     (<q_i, r_j> / d + 1)^3 over the rows j of r in its segment; exclude_same_row leaves out j == i (q and r the same tensor and
     offsets).  Rows in no segment are not written.  One launch on ``ctx``'s stream, no synchronisation."""
     import torch
-    _check_rows(q, q_off, "poly3_rowsum queries")
-    _check_rows(r, r_off, "poly3_rowsum references")
+    check_rows(q, q_off, "poly3_rowsum queries")
+    check_rows(r, r_off, "poly3_rowsum references")
     if q.shape[1] != r.shape[1] or q_off.numel() != r_off.numel():
         raise ValueError("poly3_rowsum: queries %s / %d offsets, references %s / %d offsets" % (tuple(q.shape), q_off.numel(), tuple(r.shape), r_off.numel()))
     with torch.cuda.stream(ctx.stream):
@@ -119,7 +117,7 @@ def self_sums(fs, block_off):
 
 
 def compare(real, real_sums, generated, subset_size):
-    """real, generated: manifold.FeatureSet on the same context; real_sums: the HOST vectors of ``self_sums(real, block_offsets(n, n,
+    """real, generated: FeatureSet on the same context; real_sums: the HOST vectors of ``self_sums(real, block_offsets(n, n,
     subset_size))``.  -> the result dict of ``KernelDistanceEvaluator.evaluate``.  Six launches and one download."""
     ctx = real.ctx
     if real.d != generated.d or len(real.count) != len(generated.count):
@@ -132,7 +130,7 @@ def compare(real, real_sums, generated, subset_size):
         d_off = _device_offsets(ctx, boff)
         dev[5] = poly3_rowsum(ctx, generated.pooled, d_off, real.pooled, d_off)
     have = [t for t in dev if t is not None]
-    host = iter(_host(ctx, *have))
+    host = iter(download(ctx, *have))
     gg_p, gg_c, gg_b, gr_p, gr_c, gr_b = [next(host) if t is not None else None for t in dev]
     blocks = (gg_b, real_sums[2], gr_b, boff) if len(boff) > 1 else None
     out = summarise(gg_c, real_sums[1], gr_c, generated.off_grouped, real.off_grouped, (gg_p, real_sums[0], gr_p), blocks)
@@ -140,34 +138,26 @@ def compare(real, real_sums, generated, subset_size):
     return out
 
 
-class KernelDistanceEvaluator:
+class KernelDistanceEvaluator(FeatureEvaluator):
     """The kernel distance end to end for one run, in the shape of manifold.ManifoldEvaluator: a LabelClassifier (its own unless
-    ``clf`` hands one over -- another evaluator's, when several metrics are on: only then it is not closed here), the real set's
-    features and self row sums taken once (``prepare_real``), then ``evaluate`` per generated set."""
+    ``clf`` hands one over), the real set's features and self row sums taken once (``prepare_real``), then ``evaluate`` per
+    generated set."""
 
     def __init__(self, n_classes, subset_size=1000, asset=None, device=0, chunk=1000, clf=None):
         if not 1 <= int(n_classes) <= MAX_SEGMENTS or int(subset_size) < 2:
             raise ValueError("KernelDistanceEvaluator: n_classes %d (1..%d), subset_size %d (at least 2)" % (n_classes, MAX_SEGMENTS, subset_size))
-        self.n_classes, self.subset_size, self.chunk = int(n_classes), int(subset_size), int(chunk)
-        self.owns_clf = clf is None
-        if clf is None:
-            from .eval_cifar import ASSET, LabelClassifier
-            clf = LabelClassifier(device, asset=ASSET if asset is None else asset)
-        self.clf = clf
-        self.real = self.real_sums = None
-
-    def feature_set(self, images, labels):
-        return FeatureSet(self.clf.ctx, self.clf.features(as_nhwc(images), chunk=self.chunk), labels, self.n_classes)
+        super().__init__(n_classes, asset, device, chunk, clf)
+        self.subset_size = int(subset_size)
+        self.real_sums = None
 
     def prepare_real(self, images, clean_labels, n_calibration=N_CALIBRATION):
         """images (the data set's CHW rows or NHWC) with their CLEAN labels.  Calibration on the first n_calibration images, as the
         Frechet evaluator's; a classifier handed over already calibrated keeps its calibration (all metrics read the same features)."""
         x = as_nhwc(images)
-        if self.owns_clf or self.clf.calibration() is None:
-            self.clf.calibrate(x[:n_calibration])
+        self.calibrate(x, n_calibration)
         self.real = self.feature_set(x, clean_labels)
         dev = self_sums(self.real, block_offsets(self.real.n, self.real.n, self.subset_size))
-        host = _host(self.real.ctx, *[t for t in dev if t is not None])
+        host = download(self.real.ctx, *[t for t in dev if t is not None])
         self.real_sums = host + [None] * (3 - len(host))
         return self.real
 
@@ -180,10 +170,6 @@ class KernelDistanceEvaluator:
         if self.real is None:
             raise RuntimeError("KernelDistanceEvaluator.evaluate needs prepare_real() first")
         return compare(self.real, self.real_sums, self.feature_set(images, labels), self.subset_size)
-
-    def close(self):
-        if self.owns_clf:
-            self.clf.close()
 
 
 def json_ready(result):
@@ -198,29 +184,10 @@ def json_ready(result):
 
 
 def main(argv=None):
-    from .host import Flags
-    f = Flags()
-    f.DEFINE_string("real", None, ".npz with images, labels: the reference set (its first 1000 images calibrate the features)")
-    f.DEFINE_string("generated", None, ".npz with images, labels: the set to score")
-    f.DEFINE_string("label_classifier", None, "weight asset of the feature network; default: the built-in CIFAR-10 network")
-    f.DEFINE_integer("n_classes", 0, "class count of the labels; 0: the largest label of either file + 1")
-    f.DEFINE_integer("subset_size", 1000, "rows per subset of the mean +- std over subsets")
-    FLAGS = f.parse(sys.argv[1:] if argv is None else argv)
-    if FLAGS.real is None or FLAGS.generated is None:
-        raise ValueError("flags real and generated are required")
-    with np.load(FLAGS.real) as z:
-        rx, ry = z["images"], z["labels"]
-    with np.load(FLAGS.generated) as z:
-        gx, gy = z["images"], z["labels"]
-    K = FLAGS.n_classes if FLAGS.n_classes > 0 else int(max(ry.max(), gy.max())) + 1
-    ev = KernelDistanceEvaluator(K, subset_size=FLAGS.subset_size, asset=FLAGS.label_classifier, device=int(os.environ.get("LOCAL_RANK", "0")))
-    try:
-        ev.prepare_real(rx, ry)
-        result = json_ready(ev.evaluate(gx, gy))
-    finally:
-        ev.close()
-    print(json.dumps(result))
-    return result
+    return standalone(argv, (("real", "the reference set (its first 1000 images calibrate the features)"), ("generated", "the set to score")),
+                      (("subset_size", 1000, "rows per subset of the mean +- std over subsets"),),
+                      lambda K, FLAGS, device: KernelDistanceEvaluator(K, subset_size=FLAGS.subset_size, asset=FLAGS.label_classifier, device=device),
+                      json_ready, features=True)
 
 
 if __name__ == '__main__':

@@ -17,13 +17,11 @@ The numbers are built around the engine's own small classifier: they are NOT com
 Stand-alone:  python -m rcgan_amd.manifold --real a.npz --generated b.npz [--k 5]   (each file: ``images`` [n,32,32,3] or [n,3072]
 CHW rows of raw pixels 0..255, ``labels`` [n]) prints the same numbers as one JSON line."""
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
-from .frechet import N_CALIBRATION, as_nhwc, permuted_labels  # noqa: F401  (permuted_labels: for the callers of this module)
+from .evaluators import (N_CALIBRATION, FeatureEvaluator, FeatureSet, as_nhwc, check_rows, download, permuted_labels,  # noqa: F401
+                         standalone)                    # (FeatureSet, as_nhwc, permuted_labels: re-exported for the callers of this module)
 
 METRICS = ("precision", "recall", "density", "coverage")
 MAX_K, MAX_SEGMENTS = 16, 1024          # the kernel's bounds on k and on the number of segments (include/rcgan_hip.h)
@@ -68,19 +66,11 @@ def summarise(count_g, count_r, nearest2_r, radius2_r, off_g, off_r, k, pooled):
 
 
 # ------------------------------------------------------------------------------------------------------------- the two kernels
-def _check_rows(x, off, what):
-    import torch
-    if x.dtype != torch.float32 or x.dim() != 2 or not x.is_contiguous():
-        raise ValueError("%s: expected contiguous fp32 [n,d], got %s %s" % (what, tuple(x.shape), x.dtype))
-    if off.dtype != torch.int32 or off.dim() != 1 or off.numel() < 2 or not off.is_contiguous():
-        raise ValueError("%s offsets: expected int32 [n_seg + 1], got %s %s" % (what, tuple(off.shape), off.dtype))
-
-
 def knn_radius(ctx, x, off, k):
     """x: device tensor [n,d] fp32; off: device int32 [n_seg + 1].  -> device fp32 [n]: each row's squared distance to its k-th
     nearest other row of its segment (-1 in a segment of <= k rows).  One launch on ``ctx``'s stream, no synchronisation."""
     import torch
-    _check_rows(x, off, "knn_radius")
+    check_rows(x, off, "knn_radius")
     with torch.cuda.stream(ctx.stream):
         out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     ctx.check(ctx.lib.rcgan_knn_radius(ctx.h, x.shape[0], x.shape[1], int(k), off.numel() - 1, C.c_void_p(x.data_ptr()),
@@ -92,8 +82,8 @@ def ball_query(ctx, q, q_off, r, r_off, r_radius2, want_count=True, want_nearest
     """For every row of q: how many balls (r_j, r_radius2[j]) of its segment contain it, and the squared distance to the nearest r_j.
     -> (device int32 [nq] or None, device fp32 [nq] or None).  One launch on ``ctx``'s stream, no synchronisation."""
     import torch
-    _check_rows(q, q_off, "ball_query queries")
-    _check_rows(r, r_off, "ball_query references")
+    check_rows(q, q_off, "ball_query queries")
+    check_rows(r, r_off, "ball_query references")
     if q.shape[1] != r.shape[1] or q_off.numel() != r_off.numel():
         raise ValueError("ball_query: queries %s / %d offsets, references %s / %d offsets" % (tuple(q.shape), q_off.numel(), tuple(r.shape), r_off.numel()))
     if want_count and (r_radius2 is None or r_radius2.dtype != torch.float32 or r_radius2.numel() != r.shape[0]):
@@ -107,92 +97,47 @@ def ball_query(ctx, q, q_off, r, r_off, r_radius2, want_count=True, want_nearest
     return count, nearest
 
 
-class FeatureSet:
-    """One image set's features on the device, twice: in original order as one segment (pooled) and grouped by class with the classes'
-    offsets; rows whose label is outside [0, K) are dropped and counted.  ``radii(k)`` runs knn_radius on both layouts."""
-
-    def __init__(self, ctx, features, labels, n_classes):
-        import torch
-        f = np.ascontiguousarray(features, np.float32)
-        lab = np.asarray(labels).reshape(-1).astype(np.int64)
-        if f.ndim != 2 or len(lab) != len(f):
-            raise ValueError("FeatureSet: features %s, %d labels" % (f.shape, len(lab)))
-        ok = (lab >= 0) & (lab < n_classes)
-        self.rejected = int((~ok).sum())
-        f, lab = f[ok], lab[ok]
-        self.n, self.d = f.shape
-        if self.n < 1:
-            raise ValueError("FeatureSet: no row has a label in [0, %d)" % n_classes)
-        order = np.argsort(lab, kind="stable")
-        self.count = np.bincount(lab, minlength=n_classes)
-        self.off_pooled = np.array([0, self.n], np.int64)
-        self.off_grouped = np.concatenate([[0], np.cumsum(self.count)]).astype(np.int64)
-        self.ctx = ctx
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(ctx.device)
-        with torch.cuda.stream(ctx.stream):
-            self.pooled, self.grouped = up(f), up(f[order])
-            self.d_off_pooled, self.d_off_grouped = up(self.off_pooled.astype(np.int32)), up(self.off_grouped.astype(np.int32))
-        self.rad_pooled = self.rad_grouped = None
-
-    def radii(self, k):
-        self.rad_pooled = knn_radius(self.ctx, self.pooled, self.d_off_pooled, k)
-        self.rad_grouped = knn_radius(self.ctx, self.grouped, self.d_off_grouped, k)
-
-
-def _host(ctx, *tensors):
-    """Device vectors -> numpy after ONE synchronisation of the context's stream."""
-    import torch
-    with torch.cuda.stream(ctx.stream):
-        host = [t.cpu() for t in tensors]
-    ctx.stream.synchronize()
-    return [h.numpy() for h in host]
+def radii(fs, k):
+    """knn_radius on both layouts of a FeatureSet, kept on it as ``rad_pooled`` and ``rad_grouped``."""
+    fs.rad_pooled = knn_radius(fs.ctx, fs.pooled, fs.d_off_pooled, k)
+    fs.rad_grouped = knn_radius(fs.ctx, fs.grouped, fs.d_off_grouped, k)
 
 
 def compare(real, generated, k):
-    """real, generated: FeatureSet on the same context, ``real.radii(k)`` already taken.  -> the result dict of ``ManifoldEvaluator.evaluate``."""
+    """real, generated: FeatureSet on the same context, ``radii(real, k)`` already taken.  -> the result dict of ``ManifoldEvaluator.evaluate``."""
     ctx = real.ctx
     if real.d != generated.d or len(real.count) != len(generated.count):
         raise ValueError("compare: real %d features x %d classes, generated %d x %d" % (real.d, len(real.count), generated.d, len(generated.count)))
-    generated.radii(k)
+    radii(generated, k)
     dev = []
     for R, Ro, Rr, G, Go, Gr in ((real.pooled, real.d_off_pooled, real.rad_pooled, generated.pooled, generated.d_off_pooled, generated.rad_pooled),
                                  (real.grouped, real.d_off_grouped, real.rad_grouped, generated.grouped, generated.d_off_grouped, generated.rad_grouped)):
         count_g, _ = ball_query(ctx, G, Go, R, Ro, Rr, want_nearest=False)          # real balls around the generated rows
         count_r, nearest_r = ball_query(ctx, R, Ro, G, Go, Gr)                       # generated balls around the real rows
         dev += [count_g, count_r, nearest_r, Rr]
-    host = _host(ctx, *dev)
+    host = download(ctx, *dev)
     out = summarise(*host[4:], generated.off_grouped, real.off_grouped, k, tuple(host[:4]))
     out.update(rejected_real=real.rejected, rejected_generated=generated.rejected)
     return out
 
 
-class ManifoldEvaluator:
+class ManifoldEvaluator(FeatureEvaluator):
     """The four metrics end to end for one run, in the shape of frechet.FrechetEvaluator: a LabelClassifier (its own unless ``clf``
-    hands one over -- the Frechet evaluator's, when both metrics are on: only then it is not closed here), the real set's features
-    and radii taken once (``prepare_real``), then ``evaluate`` per generated set."""
+    hands one over), the real set's features and radii taken once (``prepare_real``), then ``evaluate`` per generated set."""
 
     def __init__(self, n_classes, k=5, asset=None, device=0, chunk=1000, clf=None):
         if not 1 <= int(k) <= MAX_K or not 1 <= int(n_classes) <= MAX_SEGMENTS:
             raise ValueError("ManifoldEvaluator: k %d (1..%d), n_classes %d (1..%d)" % (k, MAX_K, n_classes, MAX_SEGMENTS))
-        self.n_classes, self.k, self.chunk = int(n_classes), int(k), int(chunk)
-        self.owns_clf = clf is None
-        if clf is None:
-            from .eval_cifar import ASSET, LabelClassifier
-            clf = LabelClassifier(device, asset=ASSET if asset is None else asset)
-        self.clf = clf
-        self.real = None
-
-    def feature_set(self, images, labels):
-        return FeatureSet(self.clf.ctx, self.clf.features(as_nhwc(images), chunk=self.chunk), labels, self.n_classes)
+        super().__init__(n_classes, asset, device, chunk, clf)
+        self.k = int(k)
 
     def prepare_real(self, images, clean_labels, n_calibration=N_CALIBRATION):
         """images (the data set's CHW rows or NHWC) with their CLEAN labels.  Calibration on the first n_calibration images, as the
         Frechet evaluator's; a classifier handed over already calibrated keeps its calibration (both metrics read the same features)."""
         x = as_nhwc(images)
-        if self.owns_clf or self.clf.calibration() is None:
-            self.clf.calibrate(x[:n_calibration])
+        self.calibrate(x, n_calibration)
         self.real = self.feature_set(x, clean_labels)
-        self.real.radii(self.k)
+        radii(self.real, self.k)
         return self.real
 
     def evaluate(self, images, labels):
@@ -202,10 +147,6 @@ class ManifoldEvaluator:
         if self.real is None:
             raise RuntimeError("ManifoldEvaluator.evaluate needs prepare_real() first")
         return compare(self.real, self.feature_set(images, labels), self.k)
-
-    def close(self):
-        if self.owns_clf:
-            self.clf.close()
 
 
 def json_ready(result):
@@ -219,29 +160,10 @@ def json_ready(result):
 
 
 def main(argv=None):
-    from .host import Flags
-    f = Flags()
-    f.DEFINE_string("real", None, ".npz with images, labels: the reference set (its first 1000 images calibrate the features)")
-    f.DEFINE_string("generated", None, ".npz with images, labels: the set to score")
-    f.DEFINE_string("label_classifier", None, "weight asset of the feature network; default: the built-in CIFAR-10 network")
-    f.DEFINE_integer("n_classes", 0, "class count of the labels; 0: the largest label of either file + 1")
-    f.DEFINE_integer("k", 5, "the k of the k-nearest-neighbour radii (1..16)")
-    FLAGS = f.parse(sys.argv[1:] if argv is None else argv)
-    if FLAGS.real is None or FLAGS.generated is None:
-        raise ValueError("flags real and generated are required")
-    with np.load(FLAGS.real) as z:
-        rx, ry = z["images"], z["labels"]
-    with np.load(FLAGS.generated) as z:
-        gx, gy = z["images"], z["labels"]
-    K = FLAGS.n_classes if FLAGS.n_classes > 0 else int(max(ry.max(), gy.max())) + 1
-    ev = ManifoldEvaluator(K, k=FLAGS.k, asset=FLAGS.label_classifier, device=int(os.environ.get("LOCAL_RANK", "0")))
-    try:
-        ev.prepare_real(rx, ry)
-        result = json_ready(ev.evaluate(gx, gy))
-    finally:
-        ev.close()
-    print(json.dumps(result))
-    return result
+    return standalone(argv, (("real", "the reference set (its first 1000 images calibrate the features)"), ("generated", "the set to score")),
+                      (("k", 5, "the k of the k-nearest-neighbour radii (1..16)"),),
+                      lambda K, FLAGS, device: ManifoldEvaluator(K, k=FLAGS.k, asset=FLAGS.label_classifier, device=device), json_ready,
+                      features=True)
 
 
 if __name__ == '__main__':

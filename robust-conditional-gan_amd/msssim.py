@@ -18,11 +18,10 @@ Stand-alone:  python -m rcgan_amd.msssim --real a.npz --generated b.npz [--n_cla
 (each file: ``images`` [n,32,32,3], [n,3072] CHW rows, [n,28,28,1] or [n,784] of raw pixels 0..255, ``labels`` [n]) prints the numbers
 as one JSON line."""
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
+
+from .evaluators import download, standalone  # noqa: F401  (download: re-exported)
 
 WEIGHTS = np.array([0.0448, 0.2856, 0.3001, 0.2363, 0.1333])
 LEVELS = 5
@@ -162,15 +161,6 @@ def upload(ctx, images, pairs):
         return torch.from_numpy(images).to(ctx.device), torch.from_numpy(pairs).to(ctx.device)
 
 
-def download(ctx, out):
-    """A device tensor -> numpy after one synchronisation of the context's stream."""
-    import torch
-    with torch.cuda.stream(ctx.stream):
-        host = out.cpu()
-    ctx.stream.synchronize()
-    return host.numpy()
-
-
 class MsssimEvaluator:
     """Intra-class MS-SSIM end to end for one run: the real set's per-class and pooled values taken once (``prepare_real``), then
     ``evaluate`` per generated set.  Per image set: the images uploaded once as uint8, the pairs as one int32 array, one launch, one
@@ -244,29 +234,9 @@ def json_ready(result):
 
 
 def main(argv=None):
-    from .host import Flags
-    f = Flags()
-    f.DEFINE_string("real", None, ".npz with images, labels: the reference set")
-    f.DEFINE_string("generated", None, ".npz with images, labels: the set to score")
-    f.DEFINE_integer("n_classes", 0, "class count of the labels; 0: the largest label of either file + 1")
-    f.DEFINE_integer("pairs", 1000, "pairs per class (and of the pooled value)")
-    f.DEFINE_integer("seed", SEED, "seed of the pair draw")
-    FLAGS = f.parse(sys.argv[1:] if argv is None else argv)
-    if FLAGS.real is None or FLAGS.generated is None:
-        raise ValueError("flags real and generated are required")
-    with np.load(FLAGS.real) as z:
-        rx, ry = z["images"], z["labels"]
-    with np.load(FLAGS.generated) as z:
-        gx, gy = z["images"], z["labels"]
-    K = FLAGS.n_classes if FLAGS.n_classes > 0 else int(max(ry.max(), gy.max())) + 1
-    ev = MsssimEvaluator(K, pairs=FLAGS.pairs, seed=FLAGS.seed, device=int(os.environ.get("LOCAL_RANK", "0")))
-    try:
-        ev.prepare_real(rx, ry)
-        result = json_ready(ev.evaluate(gx, gy))
-    finally:
-        ev.close()
-    print(json.dumps(result))
-    return result
+    return standalone(argv, (("real", "the reference set"), ("generated", "the set to score")),
+                      (("pairs", 1000, "pairs per class (and of the pooled value)"), ("seed", SEED, "seed of the pair draw")),
+                      lambda K, FLAGS, device: MsssimEvaluator(K, pairs=FLAGS.pairs, seed=FLAGS.seed, device=device), json_ready)
 
 
 if __name__ == '__main__':

@@ -32,12 +32,10 @@ Stand-alone:  python -m rcgan_amd.neighbours --real a.npz --heldout h.npz --gene
 (each file: ``images`` [n,32,32,3], [n,3072] CHW rows, [n,28,28,1] or [n,784] of raw pixels 0..255, ``labels`` [n]) prints the numbers
 as one JSON line."""
 import ctypes as C
-import json
-import os
-import sys
 
 import numpy as np
 
+from .evaluators import download, standalone  # noqa: F401  (download: re-exported)
 from .msssim import as_uint8_nhwc
 
 MIN_D, MAX_D = 16, 12288                 # the kernel's bounds on the row length, a multiple of 16 (include/rcgan_hip.h)
@@ -146,15 +144,6 @@ def nn_u8(ctx, q, q_off, r, r_off, exclude_same_row):
                                   C.c_void_p(q_off.data_ptr()), C.c_void_p(r.data_ptr()), C.c_void_p(r_off.data_ptr()),
                                   1 if exclude_same_row else 0, C.c_void_p(best.data_ptr())))
     return best
-
-
-def download(ctx, out):
-    """A device tensor -> numpy after one synchronisation of the context's stream."""
-    import torch
-    with torch.cuda.stream(ctx.stream):
-        host = out.cpu()
-    ctx.stream.synchronize()
-    return host.numpy()
 
 
 def nearest_sets(ctx, qs, rs, per_class=False, exclude_same=False):
@@ -345,28 +334,8 @@ def json_ready(result):
 
 
 def main(argv=None):
-    from .host import Flags
-    f = Flags()
-    f.DEFINE_string("real", None, ".npz with images, labels: the training set")
-    f.DEFINE_string("heldout", None, ".npz with images, labels: real images the generator never saw")
-    f.DEFINE_string("generated", None, ".npz with images, labels: the set to score")
-    f.DEFINE_integer("n_classes", 0, "class count of the labels; 0: the largest label of the files + 1")
-    FLAGS = f.parse(sys.argv[1:] if argv is None else argv)
-    if FLAGS.real is None or FLAGS.heldout is None or FLAGS.generated is None:
-        raise ValueError("flags real, heldout and generated are required")
-    sets = []
-    for path in (FLAGS.real, FLAGS.heldout, FLAGS.generated):
-        with np.load(path) as z:
-            sets.append((z["images"], z["labels"]))
-    K = FLAGS.n_classes if FLAGS.n_classes > 0 else int(max(y.max() for _, y in sets)) + 1
-    ev = NeighbourEvaluator(K, device=int(os.environ.get("LOCAL_RANK", "0")))
-    try:
-        ev.prepare_real(*sets[0], *sets[1])
-        result = json_ready(ev.evaluate(*sets[2]))
-    finally:
-        ev.close()
-    print(json.dumps(result))
-    return result
+    return standalone(argv, (("real", "the training set"), ("heldout", "real images the generator never saw"), ("generated", "the set to score")),
+                      (), lambda K, FLAGS, device: NeighbourEvaluator(K, device=device), json_ready)
 
 
 if __name__ == '__main__':

@@ -14,6 +14,7 @@ from datetime import datetime
 import numpy as np
 
 from . import data as D
+from . import metrics as M
 from .host import Flags, Plot, Saver, latest_checkpoint, load_checkpoint, record_setting, save_images
 
 DATA_DIR = '../data/cifar10/cifar-10-batches-py/'
@@ -67,29 +68,7 @@ def define_flags():
                     "rcgan_amd.train_classifier writes one for any class count); default: the built-in CIFAR-10 network")
     f.DEFINE_string("diffaugment", '', "differentiable augmentation of every image the critic sees: a comma-separated subset of "
                     "color,translation,cutout (empty: off)")
-    f.DEFINE_integer("frechet_freq", 0, "period (iterations) of the Frechet distance on the label classifier's features, pooled and "
-                     "per class against the clean training set; also taken at the end of training (0: off)")
-    f.DEFINE_integer("frechet_samples", 10000, "generated samples per Frechet evaluation (hundreds), balanced over the classes")
-    f.DEFINE_integer("frechet_real_samples", 0, "real images behind the real-set statistics (0: the whole training set)")
-    f.DEFINE_integer("prdc_freq", 0, "period (iterations) of k-NN precision / recall / density / coverage on the label classifier's "
-                     "features, pooled and per class against the clean training set; also taken at the end of training (0: off)")
-    f.DEFINE_integer("prdc_samples", 10000, "generated samples per precision / recall evaluation (hundreds), balanced over the classes")
-    f.DEFINE_integer("prdc_real_samples", 0, "real images behind the real manifold (0: the whole training set)")
-    f.DEFINE_integer("prdc_k", 5, "the k of the k-nearest-neighbour radii (1..16)")
-    f.DEFINE_integer("kid_freq", 0, "period (iterations) of the kernel distance (unbiased cubic-kernel MMD^2) on the label classifier's "
-                     "features, pooled and per class against the clean training set; also taken at the end of training (0: off)")
-    f.DEFINE_integer("kid_samples", 10000, "generated samples per kernel-distance evaluation (hundreds), balanced over the classes")
-    f.DEFINE_integer("kid_real_samples", 0, "real images behind the kernel distance (0: the whole training set)")
-    f.DEFINE_integer("kid_subset_size", 1000, "rows per subset of the kernel distance's mean +- std over subsets (at least 2)")
-    f.DEFINE_integer("msssim_freq", 0, "period (iterations) of the intra-class MS-SSIM of the generated IMAGES (random pairs per class, "
-                     "beside the same number on the clean training set); also taken at the end of training (0: off)")
-    f.DEFINE_integer("msssim_samples", 10000, "generated samples per MS-SSIM evaluation (hundreds), balanced over the classes")
-    f.DEFINE_integer("msssim_real_samples", 0, "real images behind the real MS-SSIM values (0: the whole training set)")
-    f.DEFINE_integer("msssim_pairs", 1000, "image pairs per class, and of the pooled value (at least 1)")
-    f.DEFINE_integer("neighbours_freq", 0, "period (iterations) of the pixel-space nearest-training-image metrics (copy rate, nearest-neighbour "
-                     "distance z, leave-one-out 1-NN accuracy: does the generator memorise?); also taken at the end of training (0: off)")
-    f.DEFINE_integer("neighbours_samples", 10000, "generated samples per nearest-neighbour evaluation (hundreds), balanced over the classes")
-    f.DEFINE_integer("neighbours_real_samples", 0, "training images the neighbours are searched in (0: the whole training set)")
+    M.define_flags(f)             # the sample-quality metrics' flags
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
     return f
@@ -144,16 +123,7 @@ def main(argv=None):
     FLAGS = define_flags().parse(argv)
     if FLAGS.log_file is None:
         raise ValueError('flag log_file is required')                         # gan_resnet.py:81-82
-    if FLAGS.frechet_freq < 0 or FLAGS.frechet_real_samples < 0 or (FLAGS.frechet_freq > 0 and FLAGS.frechet_samples < 100):
-        raise ValueError('--frechet_freq and --frechet_real_samples must not be negative, --frechet_samples at least 100')
-    if FLAGS.prdc_freq < 0 or FLAGS.prdc_real_samples < 0 or (FLAGS.prdc_freq > 0 and (FLAGS.prdc_samples < 100 or not 1 <= FLAGS.prdc_k <= 16)):
-        raise ValueError('--prdc_freq and --prdc_real_samples must not be negative, --prdc_samples at least 100, --prdc_k in 1..16')
-    if FLAGS.kid_freq < 0 or FLAGS.kid_real_samples < 0 or (FLAGS.kid_freq > 0 and (FLAGS.kid_samples < 100 or FLAGS.kid_subset_size < 2)):
-        raise ValueError('--kid_freq and --kid_real_samples must not be negative, --kid_samples at least 100, --kid_subset_size at least 2')
-    if FLAGS.msssim_freq < 0 or FLAGS.msssim_real_samples < 0 or (FLAGS.msssim_freq > 0 and (FLAGS.msssim_samples < 100 or FLAGS.msssim_pairs < 1)):
-        raise ValueError('--msssim_freq and --msssim_real_samples must not be negative, --msssim_samples at least 100, --msssim_pairs at least 1')
-    if FLAGS.neighbours_freq < 0 or FLAGS.neighbours_real_samples < 0 or (FLAGS.neighbours_freq > 0 and FLAGS.neighbours_samples < 100):
-        raise ValueError('--neighbours_freq and --neighbours_real_samples must not be negative, --neighbours_samples at least 100')
+    M.check_flags(FLAGS)
     N_CLASSES, DATA = dataset_setup(FLAGS)
     if FLAGS.label_classifier is not None:
         # before anything touches the GPU: the asset's dense layer has to be as wide as this run has classes
@@ -220,8 +190,8 @@ def main(argv=None):
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
-    clean_train = None                 # (images, clean labels) of the training set: the real side of --frechet_freq / --prdc_freq / --kid_freq / --msssim_freq
-    clean_heldout = None               # (images, clean labels) of real images outside the training set: the held-out side of --neighbours_freq
+    clean_train = None                 # (images, clean labels) of the training set: the real side of the sample-quality metrics
+    clean_heldout = None               # (images, clean labels) of real images outside the training set: their held-out side
     if FLAGS.synthetic:
         tx, ty = D.synthetic_cifar(50000, 1234, FLAGS.synthetic_kind, N_CLASSES)
         clean_train = (tx, np.array(ty))
@@ -284,160 +254,6 @@ def main(argv=None):
         logging.info('generated label accuracy: {}'.format(acc))
         return acc
 
-    # Frechet distance on the label classifier's frozen features (frechet.py), pooled and per class against the CLEAN training set
-    FRECHET_FREQ = FLAGS.frechet_freq
-    frechet_state = {"ev": None}
-
-    def frechet_evaluator():
-        from . import frechet as FR
-        ev = frechet_state["ev"]
-        if ev is None:
-            ev = frechet_state["ev"] = FR.FrechetEvaluator(N_CLASSES, asset=FLAGS.label_classifier, device=local)
-            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
-            n_real = FLAGS.frechet_real_samples if FLAGS.frechet_real_samples > 0 else len(rx)
-            ev.prepare_real(rx[:n_real], ry[:n_real], cache_path=os.path.join(DIR, FR.CACHE_NAME))
-            logging.info('frechet real statistics: {} images, {}'.format(
-                min(n_real, len(rx)), 'reused from ' + FR.CACHE_NAME if ev.reused else 'computed'))
-        return ev
-
-    def balanced_samples(n, confusion_matrix=None):
-        """n generated images (NHWC, as save_samples) with their conditioning labels balanced over the classes; rcgan-u: the labels
-        mapped through the learned matrix."""
-        from . import frechet as FR
-        balanced = gen_acc_label_lists(N_CLASSES, balanced=True)
-        calls = [balanced[j % len(balanced)] for j in range(n // 100)]
-        samples = [m.sample(labels, is_rs.normal(size=(100, Z_DIM)).astype('float32')) for labels in calls]
-        samples = ((np.concatenate(samples, axis=0) + 1.) * (255.99 / 2)).astype('int32').reshape((-1, 32, 32, 3))
-        labels = np.concatenate(calls, axis=0)
-        if confusion_matrix is not None:
-            labels = FR.permuted_labels(labels, confusion_matrix)
-        return samples, labels
-
-    def frechet_distances(confusion_matrix=None):
-        ev = frechet_evaluator()
-        r = ev.evaluate(*balanced_samples(FLAGS.frechet_samples, confusion_matrix))
-        logging.info('frechet_distance: {}'.format(r["frechet_distance"]))
-        logging.info('intra_class_frechet_distance: {} ({} of {} classes)'.format(
-            r["intra_class_frechet_distance"], r["classes_used"], N_CLASSES))
-        return r
-
-    # k-NN precision / recall / density / coverage on the same features (manifold.py), pooled and per class against the CLEAN training set
-    PRDC_FREQ = FLAGS.prdc_freq
-    manifold_state = {"ev": None}
-
-    def manifold_evaluator():
-        from . import manifold as MF
-        ev = manifold_state["ev"]
-        if ev is None:
-            # both metrics on: one classifier, the one the other evaluator has calibrated
-            shared = frechet_evaluator().clf if FRECHET_FREQ > 0 else None
-            ev = manifold_state["ev"] = MF.ManifoldEvaluator(N_CLASSES, k=FLAGS.prdc_k, asset=FLAGS.label_classifier, device=local, clf=shared)
-            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
-            n_real = FLAGS.prdc_real_samples if FLAGS.prdc_real_samples > 0 else len(rx)
-            ev.prepare_real(rx[:n_real], ry[:n_real])
-            logging.info('manifold real set: {} images, k = {}, label classifier {}'.format(
-                min(n_real, len(rx)), FLAGS.prdc_k, 'shared' if shared is not None else 'of its own'))
-        return ev
-
-    def manifold_metrics(confusion_matrix=None):
-        from . import manifold as MF
-        ev = manifold_evaluator()
-        r = ev.evaluate(*balanced_samples(FLAGS.prdc_samples, confusion_matrix))
-        for name in MF.METRICS:
-            logging.info('manifold_{}: {}'.format(name, r[name]))
-        for name in MF.METRICS:
-            logging.info('intra_class_manifold_{}: {} ({} of {} classes)'.format(name, r["intra_class_" + name], r["classes_used"], N_CLASSES))
-        for name in MF.METRICS:
-            plot.plot('manifold_' + name, r[name])
-            plot.plot('intra_class_manifold_' + name, r["intra_class_" + name])
-        return r
-
-    # kernel distance (unbiased cubic-kernel MMD^2) on the same features (kid.py), pooled and per class against the CLEAN training set
-    KID_FREQ = FLAGS.kid_freq
-    kid_state = {"ev": None}
-
-    def kernel_distances(confusion_matrix=None):
-        from . import kid as KD
-        ev = kid_state["ev"]
-        if ev is None:
-            # several metrics on: one classifier, the one another evaluator has calibrated (and owns)
-            shared = frechet_evaluator().clf if FRECHET_FREQ > 0 else manifold_evaluator().clf if PRDC_FREQ > 0 else None
-            ev = kid_state["ev"] = KD.KernelDistanceEvaluator(N_CLASSES, subset_size=FLAGS.kid_subset_size, asset=FLAGS.label_classifier,
-                                                              device=local, clf=shared)
-            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
-            n_real = FLAGS.kid_real_samples if FLAGS.kid_real_samples > 0 else len(rx)
-            ev.prepare_real(rx[:n_real], ry[:n_real])
-            logging.info('kernel distance real set: {} images, label classifier {}'.format(
-                min(n_real, len(rx)), 'shared' if shared is not None else 'of its own'))
-        r = ev.evaluate(*balanced_samples(FLAGS.kid_samples, confusion_matrix))
-        logging.info('kernel_distance: {}'.format(r["kernel_distance"]))
-        logging.info('intra_class_kernel_distance: {} +- {} ({} of {} classes)'.format(
-            r["intra_class_kernel_distance"], r["intra_class_kernel_distance_se"], r["classes_used"], N_CLASSES))
-        logging.info('kernel_distance_subsets: {} +- {} ({} of size {})'.format(
-            r["subset_mean"], r["subset_std"], r["subsets"], FLAGS.kid_subset_size))
-        plot.plot('kernel_distance', r["kernel_distance"])
-        plot.plot('intra_class_kernel_distance', r["intra_class_kernel_distance"])
-        plot.plot('kernel_distance_subsets', r["subset_mean"])
-        return r
-
-    # intra-class MS-SSIM of the images themselves (msssim.py): random pairs per class, beside the same number on the CLEAN training set
-    MSSSIM_FREQ = FLAGS.msssim_freq
-    msssim_state = {"ev": None}
-
-    def msssim_values(confusion_matrix=None):
-        from . import msssim as MS
-        ev = msssim_state["ev"]
-        if ev is None:
-            ev = msssim_state["ev"] = MS.MsssimEvaluator(N_CLASSES, pairs=FLAGS.msssim_pairs, device=local)
-            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
-            n_real = FLAGS.msssim_real_samples if FLAGS.msssim_real_samples > 0 else len(rx)
-            real = ev.prepare_real(rx[:n_real], ry[:n_real])
-            logging.info('msssim real set: {} images, {} pairs per class, intra-class {}'.format(
-                min(n_real, len(rx)), FLAGS.msssim_pairs, real["intra_class_msssim"]))
-        r = ev.evaluate(*balanced_samples(FLAGS.msssim_samples, confusion_matrix))
-        used = N_CLASSES - len(r["left_out"]) - len(r["undefined"])
-        logging.info('msssim: {}'.format(r["msssim"]))
-        logging.info('intra_class_msssim: {} +- {} ({} of {} classes), real {}'.format(
-            r["intra_class_msssim"], r["intra_class_msssim_se"], used, N_CLASSES, r["intra_class_msssim_real"]))
-        logging.info('msssim_classes_above_real: {} of {}'.format(r["classes_above_real"], r["classes_compared"]))
-        plot.plot('msssim', r["msssim"])
-        plot.plot('intra_class_msssim', r["intra_class_msssim"])
-        plot.plot('msssim_classes_above_real', r["classes_above_real"])
-        return r
-
-    # nearest training images in pixel space (neighbours.py): does the generator memorise?  Against the CLEAN training set, beside the
-    # same numbers of a held-out real set
-    NEIGHBOURS_FREQ = FLAGS.neighbours_freq
-    neighbours_state = {"ev": None}
-
-    def neighbour_metrics(iteration, confusion_matrix=None):
-        from . import neighbours as NB
-        ev = neighbours_state["ev"]
-        if ev is None:
-            ev = neighbours_state["ev"] = NB.NeighbourEvaluator(N_CLASSES, device=local)
-            rx, ry = clean_train if clean_train is not None else clean_training_set(FLAGS, DATA)
-            hx, hy = clean_heldout if clean_heldout is not None else clean_heldout_set(FLAGS, DATA)
-            n_real = FLAGS.neighbours_real_samples if FLAGS.neighbours_real_samples > 0 else len(rx)
-            real = ev.prepare_real(rx[:n_real], ry[:n_real], hx, hy)
-            logging.info('neighbours real set: {} training images, {} held-out images, held-out copy rate {}'.format(
-                min(n_real, len(rx)), len(hx), real["copy_rate_heldout"]))
-        r = ev.evaluate(*balanced_samples(FLAGS.neighbours_samples, confusion_matrix))
-        logging.info('copy_rate: {} (held-out {})'.format(r["copy_rate"], r["copy_rate_heldout"]))
-        logging.info('nn_distance_z: {}, intra-class {} ({} of {} classes)'.format(
-            r["nn_distance_z"], r["intra_class_nn_distance_z"], r["classes_used"], N_CLASSES))
-        logging.info('loo_1nn_accuracy: {} (real {}, generated {})'.format(
-            r["loo_1nn_accuracy"], r["loo_1nn_accuracy_real"], r["loo_1nn_accuracy_generated"]))
-        plot.plot('copy_rate', r["copy_rate"])
-        plot.plot('nn_distance_z', r["nn_distance_z"])
-        plot.plot('loo_1nn_accuracy', r["loo_1nn_accuracy"])
-        # the fixed grid's samples, each beside its nearest training image
-        grid = ((m.sample(fixed_labels, fixed_noise) + 1.) * (255. / 2)).astype('int32').reshape((100, 32, 32, 3))
-        _, nearest = ev.nearest_training_rows(grid)
-        found = ev.real["images"][np.maximum(nearest, 0)].reshape((100, 32, 32, 3))          # (kept as NHWC rows by the evaluator)
-        pairs = np.stack([np.clip(grid, 0, 255).astype(np.uint8), found], axis=1).reshape((200, 32, 32, 3))
-        save_images(pairs, os.path.join(DIR, 'neighbours_{}.png'.format(iteration)))
-        return r
-
     def inception_score(n):
         # gan_resnet.py:836-845: 100 samples with uniformly random labels per Generator call, n / 100 calls
         from .inception_score import get_inception_score, samples_as_the_reference_feeds_them
@@ -448,6 +264,10 @@ def main(argv=None):
         return get_inception_score(samples_as_the_reference_feeds_them(np.concatenate(all_samples, axis=0)), inception_fn)
 
     is_rs = np.random.RandomState(0x15c0 + rank)
+    # the sample-quality metrics (metrics.py), against the CLEAN training set and a held-out real set
+    evaluations = M.Evaluations(FLAGS, N_CLASSES, local, DIR, m.sample, is_rs, plot, fixed_noise, fixed_labels,
+                                lambda: clean_train if clean_train is not None else clean_training_set(FLAGS, DATA),
+                                lambda: clean_heldout if clean_heldout is not None else clean_heldout_set(FLAGS, DATA))
     inception_score_max = 0.0                                                  # gan_resnet.py:917
     from .dp import mean_over_ranks
     pending = []                       # (iteration, ticket) of losses read back asynchronously
@@ -526,28 +346,8 @@ def main(argv=None):
             plot.plot('gen_label_acc', accuracy)
             plot.plot('gen_label_acc_max', acc_state["max"])
             logging.info('finished calculating generated label accuracy.')
-        if rank == 0 and FRECHET_FREQ > 0 and iteration % FRECHET_FREQ == FRECHET_FREQ - 1:
-            logging.info('starting calculating frechet distance.')
-            r = frechet_distances()
-            plot.plot('frechet_distance', r["frechet_distance"])
-            plot.plot('intra_class_frechet_distance', r["intra_class_frechet_distance"])
-            logging.info('finished calculating frechet distance.')
-        if rank == 0 and PRDC_FREQ > 0 and iteration % PRDC_FREQ == PRDC_FREQ - 1:
-            logging.info('starting calculating manifold precision and recall.')
-            manifold_metrics()
-            logging.info('finished calculating manifold precision and recall.')
-        if rank == 0 and KID_FREQ > 0 and iteration % KID_FREQ == KID_FREQ - 1:
-            logging.info('starting calculating kernel distance.')
-            kernel_distances()
-            logging.info('finished calculating kernel distance.')
-        if rank == 0 and MSSSIM_FREQ > 0 and iteration % MSSSIM_FREQ == MSSSIM_FREQ - 1:
-            logging.info('starting calculating intra-class msssim.')
-            msssim_values()
-            logging.info('finished calculating intra-class msssim.')
-        if rank == 0 and NEIGHBOURS_FREQ > 0 and iteration % NEIGHBOURS_FREQ == NEIGHBOURS_FREQ - 1:
-            logging.info('starting calculating nearest training images.')
-            neighbour_metrics(iteration)
-            logging.info('finished calculating nearest training images.')
+        if rank == 0:
+            evaluations.run(iteration)
         ECE = max(FLAGS.early_checkpoint_every, 1)
         if rank == 0 and ((iteration < 500 and iteration % ECE == ECE - 1) or (iteration % 1000 == 999)):      # :1007-1014
             drain_losses()
@@ -559,49 +359,15 @@ def main(argv=None):
         logging.info('starting calculating %sgenerated label accuracy.' % ('min. permuted ' if cm is not None else ''))
         plot.plot('gen_label_acc', label_accuracy(cm))
         logging.info('finished calculating generated label accuracy.')
-    if rank == 0 and FRECHET_FREQ > 0:
-        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
-        logging.info('starting calculating %sfrechet distance.' % ('min. permuted ' if cm is not None else ''))
-        r = frechet_distances(cm)
-        plot.plot('frechet_distance', r["frechet_distance"])
-        plot.plot('intra_class_frechet_distance', r["intra_class_frechet_distance"])
-        logging.info('finished calculating frechet distance.')
-    if rank == 0 and PRDC_FREQ > 0:
-        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
-        logging.info('starting calculating %smanifold precision and recall.' % ('min. permuted ' if cm is not None else ''))
-        manifold_metrics(cm)
-        logging.info('finished calculating manifold precision and recall.')
-    if rank == 0 and KID_FREQ > 0:
-        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
-        logging.info('starting calculating %skernel distance.' % ('min. permuted ' if cm is not None else ''))
-        kernel_distances(cm)
-        logging.info('finished calculating kernel distance.')
-    if rank == 0 and MSSSIM_FREQ > 0:
-        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
-        logging.info('starting calculating %sintra-class msssim.' % ('min. permuted ' if cm is not None else ''))
-        msssim_values(cm)
-        logging.info('finished calculating intra-class msssim.')
-    if rank == 0 and NEIGHBOURS_FREQ > 0:
-        cm = m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None
-        logging.info('starting calculating %snearest training images.' % ('min. permuted ' if cm is not None else ''))
-        neighbour_metrics('final', cm)
-        logging.info('finished calculating nearest training images.')
+    if rank == 0 and evaluations.enabled:
+        evaluations.finish(m.confusion_matrix_value() if FLAGS.perm_gen_label_acc else None)
     drain_losses()
     if rank == 0 and ITERS:
         plot.dir_flush(DIR)
         saver.save(m.state_dict(), CHECKPOINT_DIR, 'model.ckpt', max(ITERS - 1, 0))
     if acc_state["clf"] is not None:
         acc_state["clf"].close()
-    if neighbours_state["ev"] is not None:
-        neighbours_state["ev"].close()
-    if msssim_state["ev"] is not None:
-        msssim_state["ev"].close()
-    if kid_state["ev"] is not None:
-        kid_state["ev"].close()
-    if manifold_state["ev"] is not None:
-        manifold_state["ev"].close()
-    if frechet_state["ev"] is not None:
-        frechet_state["ev"].close()
+    evaluations.close()
     m.ctx.close()
     return DIR
 

@@ -3,13 +3,12 @@
 distances on template images, and the training command line."""
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import frechet_ref as FRF
+from tests.train_launch import launch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -179,16 +178,8 @@ def test_the_stand_alone_entry_compares_two_sample_dumps(tmp_path, capsys):
 
 # ------------------------------------------------------------------------------------------------------------- command line
 def _launch(tmp_path, extra, expt="f1"):
-    log = os.path.join(str(tmp_path), "log_%s.txt" % expt)
-    argv = [sys.executable, os.path.join(ROOT, "cifar10", "gan_resnet.py"), "--algorithm", "rcgan", "--alpha", "0.6", "--log_file", log,
-            "--parent_dir", str(tmp_path), "--expt_dir", expt, "--ngpus", "1", "--multi_gpu_multi_batch", "--niters", "2", "--batch_size", "8",
-            "--synthetic", "--synthetic_kind", "templates", "--sample_freq", "0", "--inception_freq", "0",
-            "--generated_label_accuracy_freq", "0", "--early_checkpoint_every", "4"] + extra
-    r = subprocess.run(argv, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    text = open(log).read()
-    os.remove(log)
-    return text
+    """Two iterations through the reference-compatible launcher."""
+    return launch(tmp_path, extra, expt, niters=2, script=os.path.join(ROOT, "cifar10", "gan_resnet.py"))[0]
 
 
 def _logged(text, name):

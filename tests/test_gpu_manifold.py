@@ -10,13 +10,12 @@ that undecided pairs are at most 0.1 % of all pairs, so the allowance cannot hid
 import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import manifold_ref as MR
+from tests.train_launch import launch as _launch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -180,23 +179,6 @@ def test_the_stand_alone_entry_prints_the_evaluators_numbers(tmp_path, capsys):
 # ------------------------------------------------------------------------------------------------------------- command line
 KEYS = ["manifold_" + m for m in MR.METRICS] + ["intra_class_manifold_" + m for m in MR.METRICS]
 PRDC = ["--prdc_freq", "2", "--prdc_samples", "512", "--prdc_real_samples", "1024"]
-# the training entry with every construction of a LabelClassifier counted
-COUNTING = ("import sys; sys.path.insert(0, %r); import rcgan_amd; from rcgan_amd import eval_cifar, train_cifar; built = []; "
-            "init = eval_cifar.LabelClassifier.__init__; "
-            "eval_cifar.LabelClassifier.__init__ = lambda self, *a, **k: (built.append(1), init(self, *a, **k))[1]; "
-            "train_cifar.main(sys.argv[1:]); print('label classifiers built: %%d' %% len(built))" % ROOT)
-
-
-def _launch(tmp_path, extra, expt):
-    log = os.path.join(str(tmp_path), "log_%s.txt" % expt)
-    argv = [sys.executable, "-c", COUNTING, "--algorithm", "rcgan", "--alpha", "0.6", "--log_file", log,
-            "--parent_dir", str(tmp_path), "--expt_dir", expt, "--ngpus", "1", "--multi_gpu_multi_batch", "--niters", "4", "--batch_size", "8",
-            "--synthetic", "--synthetic_kind", "templates", "--sample_freq", "0", "--inception_freq", "0",
-            "--generated_label_accuracy_freq", "0", "--early_checkpoint_every", "4"] + extra
-    r = subprocess.run(argv, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    built = int(re.search(r"label classifiers built: (\d+)", r.stdout.decode()).group(1))
-    return open(log).read(), built
 
 
 def _logged(text, name):

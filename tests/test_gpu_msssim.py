@@ -7,13 +7,12 @@ is a mean over pairs, and the value prod m_l^{w_l} lies between the products tak
 import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import msssim_ref as MR
+from tests.train_launch import launch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -123,15 +122,7 @@ def test_the_stand_alone_tool_prints_the_evaluators_numbers_as_one_json_line(wor
 
 # ------------------------------------------------------------------------------------------------------------- command line
 def test_training_logs_the_lines_at_every_period_and_at_the_end(tmp_path):
-    log = os.path.join(str(tmp_path), "log.txt")
-    argv = [sys.executable, "-c", "import sys; sys.path.insert(0, %r); import rcgan_amd; from rcgan_amd import train_cifar; train_cifar.main(sys.argv[1:])" % ROOT,
-            "--algorithm", "rcgan", "--alpha", "0.6", "--log_file", log, "--parent_dir", str(tmp_path), "--expt_dir", "m1", "--ngpus", "1",
-            "--multi_gpu_multi_batch", "--niters", "4", "--batch_size", "8", "--synthetic", "--synthetic_kind", "templates", "--sample_freq", "0",
-            "--inception_freq", "0", "--generated_label_accuracy_freq", "0", "--early_checkpoint_every", "4",
-            "--msssim_freq", "2", "--msssim_samples", "200", "--msssim_real_samples", "400", "--msssim_pairs", "20"]
-    r = subprocess.run(argv, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    text = open(log).read()
+    text, _ = launch(tmp_path, ["--msssim_freq", "2", "--msssim_samples", "200", "--msssim_real_samples", "400", "--msssim_pairs", "20"], "m1")
     num = r"(-?[\d.]+(?:e[-+]?\d+)?|nan)"
     pooled = re.findall(r"INFO\s+msssim: %s$" % num, text, flags=re.M)
     intra = re.findall(r"INFO\s+intra_class_msssim: %s \+- %s \((\d+) of 10 classes\), real %s$" % (num, num, num), text, flags=re.M)

@@ -11,13 +11,12 @@ The kernel is exact, so the evaluator must EQUAL the restatement: distances, ind
 import json
 import os
 import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 from tests import neighbours_ref as NR
+from tests.train_launch import launch
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -154,14 +153,7 @@ def test_the_stand_alone_tool_prints_the_evaluators_numbers_as_one_json_line(wor
 
 # ------------------------------------------------------------------------------------------------------------- command line
 def _train(tmp_path, name, extra):
-    log = os.path.join(str(tmp_path), name + ".txt")
-    argv = [sys.executable, "-c", "import sys; sys.path.insert(0, %r); import rcgan_amd; from rcgan_amd import train_cifar; train_cifar.main(sys.argv[1:])" % ROOT,
-            "--algorithm", "rcgan", "--alpha", "0.6", "--log_file", log, "--parent_dir", str(tmp_path), "--expt_dir", name, "--ngpus", "1",
-            "--multi_gpu_multi_batch", "--niters", "4", "--batch_size", "8", "--synthetic", "--synthetic_kind", "templates", "--sample_freq", "0",
-            "--inception_freq", "0", "--generated_label_accuracy_freq", "0", "--early_checkpoint_every", "4"] + extra
-    r = subprocess.run(argv, cwd=str(tmp_path), stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
-    assert r.returncode == 0, r.stderr.decode()[-3000:]
-    return open(log).read()
+    return launch(tmp_path, extra, name)[0]
 
 
 def test_training_logs_the_three_lines_at_every_period_and_at_the_end_and_writes_the_picture(tmp_path):
