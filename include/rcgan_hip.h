@@ -780,6 +780,48 @@ int rcgan_msssim_pairs(rcgan_ctx* ctx, int n, int h, int w, int c, int n_pairs, 
 int rcgan_nn_u8(rcgan_ctx* ctx, int nq, int nr, int d, int n_seg, const uint8_t* q, const int32_t* q_off, const uint8_t* r,
                 const int32_t* r_off, int exclude_same_row, uint64_t* best);
 
+/* ---- sliced Wasserstein distance on Laplacian-pyramid patch descriptors (csrc/swd.hip; the pixel-space distance of swd.py)
+ * x: n images [n][h][w][c], NHWC, raw pixels 0..255 (uint8, DEVICE), sorted by segment; off: int32 DEVICE array [n_seg + 1], every
+ * offset clamped to [0, n], a decreasing pair an empty segment, an image outside every segment (or in several: the lowest one counts)
+ * is read but never written for; a bad array gives wrong numbers and never an access outside the tensors.
+ * The pyramid: G0 = x, G1 = down(G0), G2 = down(G1); L0 = G0 - up(G1), L1 = G1 - up(G2), L2 = G2.  down: the taps [1,4,6,4,1]/16
+ * along each axis under the mirror boundary that does not repeat the edge (-1 -> 1, -2 -> 2, n -> n - 2, n + 1 -> n - 3), even
+ * indices kept; up: zero-insert to twice the size, then [1,4,6,4,1]/8 along each axis, the same boundary.  Level `level` of an
+ * image has (h >> level) x (w >> level) pixels; its descriptors are the 7 x 7 x c neighbourhoods centred on y = 3, 3 + stride, ...
+ * <= (h >> level) - 4, likewise x (n_pos per image, at most 49), elements in the order (dy, dx, channel).
+ *
+ * rcgan_swd_moments: mom[s][ch] = {sum, sum of squares} (fp64) of channel ch over ALL descriptor entries of segment s -- a pixel
+ *   counts once per descriptor that covers it; zeros for an empty segment.  part: fp64 DEVICE scratch of the caller, [n][c][2],
+ *   overwritten (the per-image sums: the call is two launches, images then segments).  Every sum is fp64 in an order fixed by the
+ *   launch geometry, no floating-point atomics.
+ * rcgan_swd_project: proj[d][s][j * n_pos + p] (fp32, [n_dir][n_seg][width]) = the dot product of direction dirs[d] (fp32,
+ *   [n_dir][49 c]) with descriptor p of the j-th image of segment s, normalised per channel with the segment's mean and 1 / deviation
+ *   (ddof 0), both derived on the device from `mom` as S / N and 1 / sqrt(Q / N - (S / N)^2) in fp64 and rounded to fp32; 1 / deviation
+ *   := 0 where that variance is not positive.  Every entry at or behind the segment's descriptor count is +inf; entries that would
+ *   fall behind `width` are dropped.  1 + ceil(n_dir / 128) launches.
+ *   Arithmetic: the pyramid in fp32 (L0, L2, G1, G2 exact; |L1 - exact| <= delta_1 = 7 u 255, u = 2^-24), centring and scaling in
+ *   fp32, the dot product a chain of 49 c fused multiply-adds.  With delta_0 = delta_2 = 0, r_max the largest 1 / deviation of the
+ *   segment's channels, a_l = 2 delta_l + 765 u + 2^-40 and eps64 = 2^-45 max_ch (Q / N) / variance,
+ *     |proj - exact| <= (1 + 1e-5) (r_max a_l sqrt(49 c) + (delta_l r_max + (49 c + 2) u / (1 - 49 c u) + eps64) sum_i |xhat_i w_i|)
+ *   per entry, xhat the exactly normalised descriptor (derivation: the header of csrc/swd.hip; delta_l r_max <= 1e-3 assumed).
+ * rcgan_sort_rows_f32: every row of x[rows][width] sorted ascending in place, in the total order of the keys
+ *   bits ^ (sign ? 0xffffffff : 0x80000000): -0 before +0, +inf behind every finite value (the padding above relies on it).
+ *   Bitonic: one launch for every compare-exchange stride below a chunk of min(width, 8192) floats held in LDS, one launch per
+ *   stride at or above it; the kernel boundary is the only synchronisation between passes.  width 1: no launch.
+ * rcgan_absdiff_rowsum: out[r] = sum_{i < count[r mod n_seg]} |a[r][i] - b[r][i]| in fp64 (a, b: [rows][width] fp32; count: int32
+ *   DEVICE [n_seg], clamped to [0, width]), one workgroup per row, the order fixed by the launch geometry.
+ * All four: on the context's stream, nothing written but the output (and `part`), no workspace, no host synchronisation, the same
+ * bits on every run, legal inside a captured graph.
+ * h, w each 28 or 32, c 1 or 3, level 0..2, stride >= 1 with n_pos <= 49, n >= 1, 1 <= n_seg <= 1024, 1 <= n_dir <= 1024, width a
+ * power of two (sort: rows * width <= 2^36), rows >= 1, non-NULL pointers (x 16-byte, fp64 arrays 8-byte, the others 4-byte aligned):
+ * anything else is RCGAN_EINVALID_ARG before any launch (a NULL context included, so the checks need no device). */
+int rcgan_swd_moments(rcgan_ctx* ctx, int n, int h, int w, int c, int level, int stride, int n_seg, const uint8_t* x, const int32_t* off,
+                      double* part, double* mom);
+int rcgan_swd_project(rcgan_ctx* ctx, int n, int h, int w, int c, int level, int stride, int n_seg, const uint8_t* x, const int32_t* off,
+                      const double* mom, int n_dir, const float* dirs, int width, float* proj);
+int rcgan_sort_rows_f32(rcgan_ctx* ctx, int rows, int width, float* x);
+int rcgan_absdiff_rowsum(rcgan_ctx* ctx, int rows, int width, int n_seg, const int32_t* count, const float* a, const float* b, double* out);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

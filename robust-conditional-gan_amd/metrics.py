@@ -1,5 +1,6 @@
 """The schedule of the sample-quality metrics of a training run: Frechet distance (frechet.py), k-NN precision / recall / density /
-coverage (manifold.py), kernel distance (kid.py), intra-class MS-SSIM (msssim.py) and pixel-space nearest neighbours (neighbours.py).
+coverage (manifold.py), kernel distance (kid.py), intra-class MS-SSIM (msssim.py), pixel-space nearest neighbours (neighbours.py) and
+the sliced Wasserstein distance on Laplacian-pyramid patches (swd.py): six in all.
 
 ``METRICS`` holds, per metric and in the order they run, what differs between them: its flags, whether it reads the label classifier's
 features, how its evaluator is built and prepared on the real set, and how a result becomes log lines and plot values.  Everything
@@ -108,6 +109,23 @@ def _neighbours_picture(E, ev, iteration):
     save_images(pairs, os.path.join(E.dir, 'neighbours_{}.png'.format(iteration)))
 
 
+def _prepare_swd(E, rx, ry):
+    from . import swd as SW
+    ev = SW.SwdEvaluator(E.n_classes, directions=E.FLAGS.swd_directions, device=E.device)
+    ev.prepare_real(rx, ry)
+    return ev, 'swd real set: {} images, {} directions per level'.format(len(rx), E.FLAGS.swd_directions)
+
+
+def _report_swd(r, K, FLAGS):
+    return (['swd: {}, floor {}'.format(r["swd"], r["floor_swd"]),
+             'intra_class_swd: {} +- {} ({} of {} classes), floor {}'.format(
+                 r["intra_class_swd"], r["intra_class_swd_se"], r["classes_used"], K, r["floor_intra_class_swd"])] +
+            ['swd_level_{}: {}, intra-class {}, floors {}, {}'.format(
+                l, r["swd_levels"][l], r["intra_class_swd_levels"][l], r["floor_swd_levels"][l], r["floor_intra_class_swd_levels"][l])
+             for l in range(3)],
+            [('swd', r["swd"]), ('intra_class_swd', r["intra_class_swd"])])
+
+
 METRICS = (
     Metric("frechet", "frechet distance",
            ("period (iterations) of the Frechet distance on the label classifier's features, pooled and "
@@ -142,6 +160,13 @@ METRICS = (
             "generated samples per nearest-neighbour evaluation (hundreds), balanced over the classes",
             "training images the neighbours are searched in (0: the whole training set)"),
            (), False, _prepare_neighbours, _report_neighbours, _neighbours_picture),
+    Metric("swd", "sliced wasserstein distance",
+           ("period (iterations) of the sliced Wasserstein distance on Laplacian-pyramid patches of the generated IMAGES, pooled "
+            "and per class against the clean training set, beside its floor; also taken at the end of training (0: off)",
+            "generated samples per sliced-Wasserstein evaluation (hundreds), balanced over the classes",
+            "real images the distance is taken against (0: the whole training set)"),
+           (("swd_directions", 128, "random directions per pyramid level (1..1024)", 1, 1024, "in 1..1024"),),
+           False, _prepare_swd, _report_swd, None),
 )
 
 
