@@ -822,6 +822,25 @@ int rcgan_swd_project(rcgan_ctx* ctx, int n, int h, int w, int c, int level, int
 int rcgan_sort_rows_f32(rcgan_ctx* ctx, int rows, int width, float* x);
 int rcgan_absdiff_rowsum(rcgan_ctx* ctx, int rows, int width, int n_seg, const int32_t* count, const float* a, const float* b, double* out);
 
+/* ---- azimuthally averaged power spectrum of square images (csrc/spectrum.hip; the radial power-spectrum distance of spectrum.py)
+ * x: n images [n][N][N][c], NHWC, raw pixels 0..255 (uint8, DEVICE).  With a = x - 128 (exact),
+ *   F_ch(u,v) = sum_{y,x} a[y][x][ch] exp(-2 pi i (u y + v x) / N),   P = |F|^2 / N^2,
+ * signed frequencies f(u) = u if u <= N / 2 (integer division) else u - N, and the ring of (u,v) the integer b with
+ *   (2b - 1)^2 <= 4 (f(u)^2 + f(v)^2) < (2b + 1)^2        (integer arithmetic; ring 0 is the point (0,0) alone),
+ *   out[i][ch][b] = the mean of P over the members of ring b,   b < B(N) = 1 + the ring of (N/2, N/2)   (24 at 32, 21 at 28, 7 at 9).
+ * Parseval: sum_b members_b out[i][ch][b] = sum a^2.  A smaller N is its own transform, not a zero-padded one.
+ * Arithmetic: the transform in two passes of fp32 fused multiply-adds on the vector units, the twiddles computed in float64 on the
+ * host (2 N values, passed as kernel arguments) and rounded to fp32; |F|^2, the ring sums (an order fixed by the launch geometry, no
+ * floating-point atomics) and the mean in fp64, rounded once to fp32.  With u = 2^-24,
+ *   |F^ - F| <= delta = g sum_{y,x} |a[y][x][ch]|,   g = sqrt(2) (2N + 8) u / (1 - (2N + 8) u),
+ *   E = (2 mean_ring|F| delta + delta^2) / N^2,      |out - exact| <= E + 2 u (exact + E) + 2^-149
+ * for every image, channel and ring (derivation: the header of csrc/spectrum.hip).  An image of 128s gives exact zeros.
+ * One launch on the context's stream, every image's rings written on every call, nothing else written, no workspace, no host
+ * synchronisation, the same bits on every run, legal inside a captured graph.
+ * 8 <= N <= 32, c 1 or 3, n >= 1, non-NULL pointers (out 4-byte aligned; x of any alignment, 16-byte aligned images are read in
+ * 16-byte loads): anything else is RCGAN_EINVALID_ARG before any launch (a NULL context included, so the checks need no device). */
+int rcgan_radial_spectrum(rcgan_ctx* ctx, int n, int N, int c, const uint8_t* x, float* out /* [n][c][B(N)] */);
+
 /* ---- optimiser ---------------------------------------------------------------------------------------- */
 /* tf.train.AdamOptimizer on a flat fp32 range (model.py:250-262, gan_resnet.py:802-817):
  *   lr_t = lr*sqrt(1-b2^t)/(1-b1^t); m,v EMA; w -= lr_t*m/(sqrt(v)+eps); optional clip to [-clip,clip]

@@ -241,6 +241,7 @@ SIGNATURES = {
     "rcgan_swd_project": (I, [P, I, I, I, I, I, I, I, P, P, P, I, P, I, P]),
     "rcgan_sort_rows_f32": (I, [P, I, I, P]),
     "rcgan_absdiff_rowsum": (I, [P, I, I, I, P, P, P, P]),
+    "rcgan_radial_spectrum": (I, [P, I, I, I, P, P]),
     "rcgan_sgd_momentum": (I, [P, SZ, SZ, P, P, P, P, F, F, I, F]),
     "rcgan_augment_cifar": (I, [P, I, I, P, P, P, P, I, I, P, P]),
     "rcgan_relu_maxpool2_fwd": (I, [P, I, I, I, I, I, P, P]),

@@ -1,4 +1,4 @@
-"""What the six sample-quality evaluators (frechet.py, manifold.py, kid.py, msssim.py, neighbours.py, swd.py) have in common: the image and
+"""What the seven sample-quality evaluators (frechet.py, manifold.py, kid.py, msssim.py, neighbours.py, swd.py, spectrum.py) have in common: the image and
 label layouts they take, one download, the class-grouped feature layout and the classifier handling of the three that read the label
 classifier's features, and the stand-alone entry point behind each module's ``main``.  numpy only at import; torch where a function
 touches the device."""

@@ -1,8 +1,9 @@
 """The schedule of the sample-quality metrics of a training run: Frechet distance (frechet.py), k-NN precision / recall / density /
-coverage (manifold.py), kernel distance (kid.py), intra-class MS-SSIM (msssim.py), pixel-space nearest neighbours (neighbours.py) and
-the sliced Wasserstein distance on Laplacian-pyramid patches (swd.py): six in all.
+coverage (manifold.py), kernel distance (kid.py), intra-class MS-SSIM (msssim.py), pixel-space nearest neighbours (neighbours.py), the
+sliced Wasserstein distance on Laplacian-pyramid patches (swd.py) and the radial power-spectrum distance (spectrum.py): seven in all.
 
-``METRICS`` holds, per metric and in the order they run, what differs between them: its flags, whether it reads the label classifier's
+``SCHEDULE`` (``METRICS``, the six rows that came first, and behind them ``SPECTRUM``) holds, per metric and in the order they run,
+what differs between them: its flags, whether it reads the label classifier's
 features, how its evaluator is built and prepared on the real set, and how a result becomes log lines and plot values.  Everything
 else is said once, in ``Evaluations``: the periods, the balanced generated samples drawn from the run's private stream, the real sets
 (read once), the one LabelClassifier the feature metrics share, and the order of closing.  numpy only at import; an evaluator module
@@ -126,6 +127,31 @@ def _report_swd(r, K, FLAGS):
             [('swd', r["swd"]), ('intra_class_swd', r["intra_class_swd"])])
 
 
+def _prepare_spectrum(E, rx, ry):
+    from . import spectrum as SP
+    ev = SP.SpectrumEvaluator(E.n_classes, device=E.device)
+    ev.prepare_real(rx, ry)
+    return ev, 'spectrum real set: {} images'.format(len(rx))
+
+
+def _report_spectrum(r, K, FLAGS):
+    return (['spectral_distance: {} dB, floor {}'.format(r["spectral_distance"], r["floor_spectral_distance"]),
+             'intra_class_spectral_distance: {} +- {} dB ({} of {} classes), floor {}'.format(
+                 r["intra_class_spectral_distance"], r["intra_class_spectral_distance_se"], r["classes_used"], K,
+                 r["floor_intra_class_spectral_distance"])] +
+            ['{}: {} dB, intra-class {}'.format(name, r[name], r["intra_class_" + name])
+             for name in ("high_frequency_db", "nyquist_db", "checkerboard_db")],
+            [('spectral_distance', r["spectral_distance"]), ('floor_spectral_distance', r["floor_spectral_distance"]),
+             ('intra_class_spectral_distance', r["intra_class_spectral_distance"]),
+             ('floor_intra_class_spectral_distance', r["floor_intra_class_spectral_distance"]),
+             ('high_frequency_db', r["high_frequency_db"]), ('nyquist_db', r["nyquist_db"]), ('checkerboard_db', r["checkerboard_db"])])
+
+
+def _spectrum_curves(E, ev, iteration):
+    """spectrum_<iteration>.npz: the real and the generated reduced spectra, pooled [c,B] and per class [K,c,B], to plot later."""
+    np.savez(os.path.join(E.dir, 'spectrum_{}.npz'.format(iteration)), **ev.spectra())
+
+
 METRICS = (
     Metric("frechet", "frechet distance",
            ("period (iterations) of the Frechet distance on the label classifier's features, pooled and "
@@ -169,9 +195,19 @@ METRICS = (
            False, _prepare_swd, _report_swd, None),
 )
 
+# the seventh row; the schedule walks SCHEDULE, METRICS keeps the six rows it has always named
+SPECTRUM = Metric("spectrum", "radial power spectrum",
+                  ("period (iterations) of the radial power-spectrum distance of the generated IMAGES (log-spectral distance, high-frequency, "
+                   "Nyquist and checkerboard energy in dB), pooled and per class against the clean training set, beside its floor; also "
+                   "taken at the end of training (0: off)",
+                   "generated samples per power-spectrum evaluation (hundreds), balanced over the classes",
+                   "real images the spectra are compared with (0: the whole training set)"),
+                  (), False, _prepare_spectrum, _report_spectrum, _spectrum_curves)
+SCHEDULE = METRICS + (SPECTRUM,)
+
 
 def define_flags(f):
-    for mt in METRICS:
+    for mt in SCHEDULE:
         f.DEFINE_integer(mt.prefix + "_freq", 0, mt.help[0])
         f.DEFINE_integer(mt.prefix + "_samples", 10000, mt.help[1])
         f.DEFINE_integer(mt.prefix + "_real_samples", 0, mt.help[2])
@@ -180,7 +216,7 @@ def define_flags(f):
 
 
 def check_flags(FLAGS):
-    for mt in METRICS:
+    for mt in SCHEDULE:
         freq, real = getattr(FLAGS, mt.prefix + "_freq"), getattr(FLAGS, mt.prefix + "_real_samples")
         inside = all(lo <= getattr(FLAGS, name) and (hi is None or getattr(FLAGS, name) <= hi) for name, _, _, lo, hi, _ in mt.extra)
         if freq < 0 or real < 0 or (freq > 0 and (getattr(FLAGS, mt.prefix + "_samples") < 100 or not inside)):
@@ -199,7 +235,7 @@ class Evaluations:
         self.sample, self.rs, self.plot = sample, rs, plot
         self.fixed_noise, self.fixed_labels = fixed_noise, fixed_labels
         self.loaders, self.sets = dict(train=load_train, heldout=load_heldout), {}
-        self.enabled = [mt for mt in METRICS if getattr(FLAGS, mt.prefix + "_freq") > 0]
+        self.enabled = [mt for mt in SCHEDULE if getattr(FLAGS, mt.prefix + "_freq") > 0]
         # the feature metrics read ONE classifier, built here on first need and calibrated by the first enabled of them in table order
         self.calibrating = next((mt for mt in self.enabled if mt.features), None)
         self.clf = None
