@@ -525,6 +525,25 @@ int rcgan_fragments_prepare(rcgan_ctx* ctx, const void* const* trunk_prepared, v
                             const void* const* prepared, void* const* frags);
 int rcgan_conv2d_rf(rcgan_ctx* ctx, const rcgan_conv_desc* d, int backward, const void* x, const void* frag, const float* bias,
                     const void* mask_x, const void* residual, void* y);
+
+/* ---- the 16x16 down block's forward as one launch (csrc/conv_dblock2.hip) ----------------------------------------------------------
+ * D.Block.2 of the CIFAR critic (gan_resnet.py:275-328 with resample='down'), 16 x 16 x 128 -> 8 x 8 x 128, two workgroups per image:
+ *   h = Conv1(relu(x)) + b1;  xp = meanpool2(x);  t = Shortcut(xp) + bs;  y = t + meanpool2(Conv2(relu(h)) + b2)
+ * with the 16-bit rounding points of the four launches it replaces (h, xp, t, y): h and xp are bit-identical to rcgan_conv2d_rf and
+ * rcgan_meanpool2_fwd, and Conv2's reduction runs in the order of the gather-form tile kernel with two K-split groups (the kernel the
+ * training step's shape takes), so y has the four launches' bits there and differs by fp32 summation order at most elsewhere.  h, xp and y are what the block's (unfused) backward pass reads.
+ * rcgan_dblock2_ok: 1 if d is Conv1's descriptor of exactly that block (3x3, stride 1, RCGAN_CONV_IN_RELU alone, the build's 16-bit
+ * dtype, any n >= 1) and both fragment copies exist.  conv1_frag: Conv1's copy of rcgan_conv_rf_prepare / rcgan_fragments_prepare;
+ * dblock2_frag (rcgan_dblock2_fragment_bytes): written by rcgan_fragments_prepare_dblock2 -- rcgan_fragments_prepare with two more
+ * items in the same launch -- from conv2_prepared = Conv2's prepared filter under RCGAN_CONV_OUT_MEANPOOL2 and shortcut_prepared = the
+ * 1x1 shortcut's. */
+int rcgan_dblock2_ok(const rcgan_conv_desc* d, const void* conv1_frag, const void* dblock2_frag);
+size_t rcgan_dblock2_fragment_bytes(void);
+int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
+                                    const void* const* prepared, void* const* frags, const void* conv2_prepared,
+                                    const void* shortcut_prepared, void* dblock2_frag);
+int rcgan_dblock2_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* conv1_frag, const void* dblock2_frag,
+                      const float* bias1, const float* bias2, const float* bias_shortcut, void* h, void* xp, void* y);
 /* Fused projection head: pooled features -> psi (D.Output, SN linear d -> 1), label embeddings E = table @ W_e / sigma_e + b_e
  * (embedding.py:29-51 + D.Embedding_y, gan_resnet.py:414-421), logits psi + <feat, E[l]> (:588, :654-660), loss terms and ALL
  * gradients in one launch.  Rows [0, rows_a) form part a, rows [rows_a, n) part b (real | fake of the critic step, :604-606);

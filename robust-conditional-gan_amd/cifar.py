@@ -325,9 +325,21 @@ def Discriminator(inputs, labels, update_collection=None, _head=True):
             t = Conv2D(xp if xp is not None else O.meanpool2(ctx, x), IMG_DIM, DIM_D, 1, 1, 'D.Block.1.Shortcut', he_init=False, **kw)
             h = Conv2D(x, IMG_DIM, DIM_D, 3, 1, 'D.Block.1.Conv1', **kw)
             x = Conv2D(h, DIM_D, DIM_D, 3, 1, 'D.Block.1.Conv2', _in_relu=True, _accumulate_into=t, _out_meanpool=True, **kw)
-            t = Conv2D(O.meanpool2(ctx, x), DIM_D, DIM_D, 1, 1, 'D.Block.2.Shortcut', he_init=False, **kw)
-            h = Conv2D(x, DIM_D, DIM_D, 3, 1, 'D.Block.2.Conv1', _in_relu=True, **kw)
-            x = Conv2D(h, DIM_D, DIM_D, 3, 1, 'D.Block.2.Conv2', _in_relu=True, _accumulate_into=t, _out_meanpool=True, **kw)
+            # D.Block.2 (down): its forward as ONE launch where the step's fragment-major copies exist (ops.d_block2), else four
+            g, wb = Graph.current, []
+            for cv in ('Shortcut', 'Conv1', 'Conv2'):
+                with variable_scope('D.Block.2.%s' % cv):
+                    fname = scoped('Filters')
+                    with variable_scope('filters'):
+                        wb.append(spectral_normed_weight(fname, update_collection=update_collection))
+                    wb.append(g.param(scoped('Biases')))
+            dfrag = getattr(g, "dblock2_frag", None)
+            if O.d_block2_ok(ctx, x, wb[2], dfrag):
+                x = O.d_block2(ctx, x, *wb, frag=dfrag)
+            else:
+                t = O.conv2d(ctx, O.meanpool2(ctx, x), wb[0], wb[1], 1)
+                h = O.conv2d(ctx, x, wb[2], wb[3], 3, in_relu=True)
+                x = O.conv2d_meanpool(ctx, h, wb[4], wb[5], in_relu=True, accumulate_into=t)
         else:
             # D.Block.1: shortcut = conv1x1(meanpool(x)) == meanpool(conv1x1(x)); pooled together with Conv2
             t = Conv2D(x, IMG_DIM, DIM_D, 1, 1, 'D.Block.1.Shortcut', he_init=False, **kw)
@@ -760,8 +772,8 @@ class CifarRCGAN:
         # every fragment-major filter copy of the critic: the 8x8 stage's (ops.d_trunk) and the register-filter layers' (ops.conv2d ->
         # rcgan_conv2d_rf: D.Block.2.Conv1, 16 x 16 x 128) -- one launch behind the preparation (rf_fragments_kernel); or, measured slower
         # and off by default (ops.FRAG_IN_PREPARE), fragment rows of the preparation launch itself.
-        g.trunk_frag = None
-        trunk, rf = None, []
+        g.trunk_frag = g.dblock2_frag = None
+        trunk, rf, db2 = None, [], None
         if self.PD in which and self.ctx.act_dtype != L.F32 and (FUSED_TRUNK or O.RF_CONV):
             sn = lambda n: g.sn["Discriminator/%s/Filters" % n][0]
             trunk = [sn("D.Block.%d.%s" % (b, c)) for b in (3, 4, 5, 6) for c in ("Conv1", "Conv2")] if FUSED_TRUNK else None
@@ -769,6 +781,9 @@ class CifarRCGAN:
                 d = L.ConvDesc(1, 16, 16, DIM_D, DIM_D, 3, 3, 1, self.ctx.act_dtype, L.CONV_IN_RELU)
                 if self.ctx.lib.rcgan_conv_rf_ok(C.byref(d)):
                     rf.append((sn("D.Block.2.Conv1"), d))
+                    # ... and the two more copies the 16x16 down block's fused forward reads (ops.d_block2), items of the same launch
+                    if O.FUSED_DBLOCK2 and fused_pool_d(self.ctx, GEN_BS_MULTIPLE * self.B):
+                        db2 = (sn("D.Block.2.Conv2"), sn("D.Block.2.Shortcut"))
         if (trunk or rf) and O.FRAG_IN_PREPARE:
             tf, reqs = O.fragment_requests(self.ctx, trunk, rf)
             rode, written = g.prepare_convs(names, self.ctx.act_dtype, embed=embed, inputs=inputs, frags=reqs)
@@ -777,9 +792,12 @@ class CifarRCGAN:
             else:
                 # (some of these filters were prepared earlier in the step: their row-major copies exist, the separate launch re-lays them)
                 g.trunk_frag = O.fragments_batch(self.ctx, trunk, rf)
+            # (the down block's copies are items of the separate fragment launch only: with the fragment rows its forward stays four launches)
         else:
             rode = g.prepare_convs(names, self.ctx.act_dtype, embed=embed, inputs=inputs)
-            if trunk or rf:
+            if db2 is not None:
+                g.trunk_frag, g.dblock2_frag = O.fragments_batch(self.ctx, trunk, rf, dblock2=db2)
+            elif trunk or rf:
                 g.trunk_frag = O.fragments_batch(self.ctx, trunk, rf)
         if rode and embed is not None:
             g.head_E = embed[3]

@@ -22,16 +22,9 @@
 
 #include "conv_mfma.h"
 #include "mfma_util.h"
+#include "rf_asm.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(4))) int i32x4_t;
-
-#if RCGAN_HALF_FP16
-#define RF_MFMA "v_mfma_f32_16x16x32_f16"
-#else
-#define RF_MFMA "v_mfma_f32_16x16x32_bf16"
-#endif
 
 struct RfArgs {
   const bf16_t* in;        // [n][H][W][Cin]: x (forward) / dy (data gradient)
@@ -48,41 +41,12 @@ struct RfArgs {
   unsigned long long* stamps;   // diagnostics (rcgan_debug_stamps): 16 s_memtime stamps per workgroup, normally null
 };
 
-template <int OFF> __device__ __forceinline__ void rf_load_a(i32x4_t& dst, const void* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=a"(dst) : "v"(p), "n"(OFF) : "memory");
-}
-template <int OFF> __device__ __forceinline__ void rf_load_v(i32x4_t& dst, const void* p) {
-  asm volatile("global_load_dwordx4 %0, %1, off offset:%2" : "=v"(dst) : "v"(p), "n"(OFF) : "memory");
-}
-__device__ __forceinline__ void rf_mfma_a(f32x4_t& acc, const i32x4_t& w, const bf16x8_t& x) {
-  asm volatile(RF_MFMA " %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(x) : "memory");
-}
-__device__ __forceinline__ void rf_mfma_v(f32x4_t& acc, const i32x4_t& w, const bf16x8_t& x) {
-  asm volatile(RF_MFMA " %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(x) : "memory");
-}
-// first K-step of a group: C = 0 (an inline constant) -- a VALU zero-fill in front of an MFMA the compiler cannot see misses the wait
-// states "VALU write -> MFMA SrcC read" needs: the group's first accumulator came out wrong
-__device__ __forceinline__ void rf_mfma_a0(f32x4_t& acc, const i32x4_t& w, const bf16x8_t& x) {
-  asm volatile(RF_MFMA " %0, %1, %2, 0" : "=v"(acc) : "a"(w), "v"(x) : "memory");
-}
-__device__ __forceinline__ void rf_lds_read(bf16x8_t& dst, unsigned lds_byte_addr) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_byte_addr) : "memory");
-}
-template <int N> __device__ __forceinline__ void rf_wait() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void rf_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-template <int I, int N, typename F> __device__ __forceinline__ void rf_for(F&& f) {
-  if constexpr (I < N) { f(std::integral_constant<int, I>{}); rf_for<I + 1, N>(f); }
-}
-
 constexpr int RF_ROWS = 8;              // image rows per workgroup
 constexpr int RF_UPFRONT = 4;           // K-steps whose filter loads go out before the K loop; K-step s then issues those of K-step s + 4
 constexpr int RF_ASTEPS = 16;           // K-steps whose fragments live in AccVGPRs (4 x 4 registers each: 256); the other 2 in VGPRs
 constexpr int RF_RED = 4 * 16 * 64 * 16;   // bytes of the partial-tile exchange: 4 wavefronts x 16 tiles x 64 lanes x float4
 
-// rows [R][K] (rcgan_conv_prepare layout) -> fragment-major [block of 16*ctn rows][slice][step][tile ctn][lane 64][8]: lane (r = l & 15,
-// kc = l >> 4) of (block b, slice sl, step s, tile ct) owns row b*16*ctn + ct*16 + r, elements (sl*ss + s)*32 + kc*8 ..+8.
-struct FragItem { const bf16_t* src; bf16_t* dst; int K, ctn, ss, nsl, chunks; };
+// (FragItem and its layout: rf_asm.h)
 struct FragBatch { FragItem it[40]; };
 __global__ __launch_bounds__(256) void rf_fragments_kernel(FragBatch b) {
   const FragItem it = b.it[blockIdx.y];
@@ -335,10 +299,27 @@ int rcgan_conv_rf_prepare(rcgan_ctx* ctx, int n, const rcgan_conv_desc* descs, c
 // eight prepared filters in forward order, or NULL) and n register-filter layers' (what rcgan_conv_rf_prepare writes).
 int rcgan_fragments_prepare(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
                             const void* const* prepared, void* const* frags) {
+  return rcgan_fragments_prepare_dblock2(ctx, trunk_prepared, trunk_frag, n, descs, prepared, frags, nullptr, nullptr, nullptr);
+}
+
+// ... and, in the same launch, the two copies the 16x16 down block's fused forward reads (conv_dblock2.hip; rcgan_dblock2_fragment_bytes):
+// conv2_prepared = D.Block.2.Conv2's prepared filter under RCGAN_CONV_OUT_MEANPOOL2 (its summed gather-layout rows are re-laid),
+// shortcut_prepared = the 1x1 shortcut's.  All three NULL: rcgan_fragments_prepare.
+int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
+                                    const void* const* prepared, void* const* frags, const void* conv2_prepared,
+                                    const void* shortcut_prepared, void* dblock2_frag) {
   if (!ctx) return RCGAN_EINVALID_ARG;
   RC_REQUIRE(ctx, n >= 0 && n <= 12 && (n == 0 || (descs && prepared && frags)) && (!trunk_prepared || trunk_frag), "bad arguments");
+  RC_REQUIRE(ctx, (conv2_prepared != nullptr) == (dblock2_frag != nullptr) && (shortcut_prepared != nullptr) == (dblock2_frag != nullptr),
+             "the down block's copies need both prepared filters and a destination");
   FragBatch b;
   int m = 0, maxchunks = 0;
+  if (dblock2_frag) {
+    const rcgan_conv_desc d2 = {1, 16, 16, 128, 128, 3, 3, 1, RCGAN_H16, RCGAN_CONV_OUT_MEANPOOL2};
+    dblock2_frag_items((const bf16_t*)conv2_prepared + mfma_prepared_sum_fwd(&d2), (const bf16_t*)shortcut_prepared, (bf16_t*)dblock2_frag, b.it);
+    m = 2;
+    maxchunks = b.it[0].chunks;
+  }
   if (trunk_prepared) {
     const long elems = 9L * 128 * 128;
     for (int i = 0; i < 8; ++i) {
@@ -347,7 +328,7 @@ int rcgan_fragments_prepare(rcgan_ctx* ctx, const void* const* trunk_prepared, v
       b.it[m++] = FragItem{(const bf16_t*)trunk_prepared[i], (bf16_t*)trunk_frag + i * elems, 1152, 2, 36, 1, (int)(elems / 8)};
       b.it[m++] = FragItem{(const bf16_t*)trunk_prepared[7 - i] + elems, (bf16_t*)trunk_frag + (8 + i) * elems, 1152, 2, 36, 1, (int)(elems / 8)};
     }
-    maxchunks = (int)(elems / 8);
+    if ((int)(elems / 8) > maxchunks) maxchunks = (int)(elems / 8);
   }
   for (int i = 0; i < n; ++i) {
     const rcgan_conv_desc* d = descs + i;

@@ -203,10 +203,12 @@ def fragment_requests(ctx, trunk, rf):
     return tf, reqs
 
 
-def fragments_batch(ctx, trunk, rf):
+def fragments_batch(ctx, trunk, rf, dblock2=None):
     """ONE launch writes every fragment-major filter copy of a step (rcgan_fragments_prepare): trunk = the 8x8 stage's eight Weights in
     forward order (or None) -> returns its fragment buffer (ops.d_trunk(frag=...)); rf = [(Weight, desc)] of the layers the
-    register-filter kernel takes -> each Weight gets .rf_frag.  All filters must be prepared already (prepare_batch)."""
+    register-filter kernel takes -> each Weight gets .rf_frag.  All filters must be prepared already (prepare_batch).
+    dblock2 = (Weight Conv2, Weight Shortcut) of the 16x16 down block: the same launch also writes the two copies its fused forward
+    reads (ops.d_block2) -> returns (trunk buffer, down-block buffer)."""
     tp = tf = None
     if trunk:
         tdesc = L.ConvDesc(1, 8, 8, 128, 128, 3, 3, 1, ctx.act_dtype, L.CONV_IN_RELU)
@@ -221,6 +223,15 @@ def fragments_batch(ctx, trunk, rf):
         nb = ctx.lib.rcgan_conv_rf_fragment_bytes(C.byref(d))
         w.rf_frag = DT(ctx.arena.alloc(nb), (nb,), "u8", ctx.arena.buf)
         frags.append(w.rf_frag.ptr)
+    if dblock2 is not None:
+        w2, ws = dblock2
+        p2 = w2.prepared(L.ConvDesc(1, 8, 8, 128, 128, 3, 3, 1, ctx.act_dtype, L.CONV_OUT_MEANPOOL2))
+        ps = ws.prepared(L.ConvDesc(1, 8, 8, 128, 128, 1, 1, 1, ctx.act_dtype, 0))
+        nb = ctx.lib.rcgan_dblock2_fragment_bytes()
+        df = DT(ctx.arena.alloc(nb), (nb,), "u8", ctx.arena.buf)
+        ctx.check(ctx.lib.rcgan_fragments_prepare_dblock2(ctx.h, tp, _p(tf), n, descs, preps, (C.c_void_p * max(n, 1))(*frags),
+                                                          _p(p2), _p(ps), _p(df)))
+        return tf, df
     ctx.check(ctx.lib.rcgan_fragments_prepare(ctx.h, tp, _p(tf), n, descs, preps, (C.c_void_p * max(n, 1))(*frags)))
     return tf
 
@@ -319,7 +330,7 @@ FUSE_BN_STATS = os.environ.get("RCGAN_FUSE_BN_STATS", "0") == "1"
 
 
 def conv2d(ctx, x, weight, bias, k, stride=1, in_up=False, in_relu=False, accumulate_into=None, force_direct=False,
-           residual=None, residual_up=False, want_stats=False):
+           residual=None, residual_up=False, want_stats=False, _done=None):
     """SAME conv on NHWC x with HWIO weight [k,k,cin,cout] (tf.nn.conv2d + bias_add: mnist/ops.py:62-65,
     cifar10/common/ops/conv2d.py:181-216).  in_up / in_relu fold the preceding nearest-2x upsample
     (gan_resnet.py:263-264) and ReLU into the operand load; accumulate_into adds the result into an
@@ -328,7 +339,9 @@ def conv2d(ctx, x, weight, bias, k, stride=1, in_up=False, in_relu=False, accumu
     residual lives on the half-resolution grid and is added nearest-upsampled (the up blocks' 1x1 shortcut evaluated before
     the upsample it commutes with); its gradient is the 2x2 sum of dy.
     want_stats: the caller will batch-normalise the result -- where the producing kernel can, the per-tile column sums of the stored
-    output come out of its epilogue (rcgan_conv2d_fwd_stats) and are attached as ``y.tile_stats`` for batch_norm_act."""
+    output come out of its epilogue (rcgan_conv2d_fwd_stats) and are attached as ``y.tile_stats`` for batch_norm_act.
+    _done: the tensor a fused launch has already written this layer's output to (ops.d_block2): nothing is launched, the tape entry is
+    recorded as usual."""
     if isinstance(x, BnPending):
         pend = x
         n, hs, ws_, cin = pend.shape
@@ -366,7 +379,8 @@ def conv2d(ctx, x, weight, bias, k, stride=1, in_up=False, in_relu=False, accumu
         assert y.shape == (n, oh, ow, cout)
         fdesc = L.ConvDesc(n, h, w, cin, cout, k, k, stride, x.dtype, flags | L.CONV_ACCUMULATE)
     else:
-        y = ctx.empty((n, oh, ow, cout), x.dtype)
+        y = _done if _done is not None else ctx.empty((n, oh, ow, cout), x.dtype)
+        assert y.shape == (n, oh, ow, cout)
         fdesc = desc
     # the register-filter kernel (conv_rf.hip) for the small-grid 3x3 layers it takes, when this step's fragment-major copy exists
     use_rf = (RF_CONV and weight.rf_frag is not None and residual is None and not in_up and not force_direct
@@ -376,7 +390,9 @@ def conv2d(ctx, x, weight, bias, k, stride=1, in_up=False, in_relu=False, accumu
         sd = L.ConvDesc(n, h, w, cin, cout, k, k, stride, x.dtype, flags | (L.CONV_RESID_UPSAMPLE2X if (residual is not None and residual_up) else 0))
         if ctx.lib.rcgan_conv_stats_ok(C.byref(sd)):
             sdesc = sd
-    if sdesc is not None:
+    if _done is not None:
+        assert accumulate_into is None and residual is None
+    elif sdesc is not None:
         assert residual is None or residual.shape == ((n, oh // 2, ow // 2, cout) if residual_up else (n, oh, ow, cout))
         sums = ctx.empty((ctx.lib.rcgan_conv_stats_bytes(C.byref(sdesc)) // 4,), L.F32)
         ctx.check(ctx.lib.rcgan_conv2d_fwd_stats(ctx.h, C.byref(sdesc), _p(x), _p(prep), _p(bias), _p(residual), _p(y), _p(sums)))
@@ -470,12 +486,13 @@ def conv_meanpool_ok(ctx, x, weight, k=3):
     return bool(ctx.lib.rcgan_conv_fused_pool_ok(C.byref(desc)))
 
 
-def conv2d_meanpool(ctx, x, weight, bias, in_relu=False, accumulate_into=None):
+def conv2d_meanpool(ctx, x, weight, bias, in_relu=False, accumulate_into=None, _done=False):
     """ConvMeanPool (gan_resnet.py:241-247): meanpool2(conv3x3(x) + bias) as ONE 4x4 stride-2 convolution with summed filters
     (RCGAN_CONV_OUT_MEANPOOL2: 4/9 of the multiply-adds, no full-resolution conv output, no pooling pass).  accumulate_into: a
     pooled-resolution tensor the result is added to (the block's shortcut).  Backward: data and filter gradient in their
     sub-pixel forms straight from the pooled dy (the filter gradient in the grouped launch; where the three-tap kernel does
-    not take the shape, through the ordinary path on dy spread back to the conv resolution)."""
+    not take the shape, through the ordinary path on dy spread back to the conv resolution).
+    _done: a fused launch has already added this layer's result into accumulate_into (ops.d_block2): only the tape entry is recorded."""
     n, h, w, cin = x.shape
     cout = weight.param.shape[-1]
     assert weight.param.shape == (3, 3, cin, cout)
@@ -489,7 +506,8 @@ def conv2d_meanpool(ctx, x, weight, bias, in_relu=False, accumulate_into=None):
     else:
         y = ctx.empty((n, h // 2, w // 2, cout), x.dtype)
         fdesc = desc
-    ctx.check(ctx.lib.rcgan_conv2d_fwd(ctx.h, C.byref(fdesc), _p(x), _p(prep), _p(bias), _p(y)))
+    if not _done:
+        ctx.check(ctx.lib.rcgan_conv2d_fwd(ctx.h, C.byref(fdesc), _p(x), _p(prep), _p(bias), _p(y)))
     prev_req = y.req if accumulate_into is not None else False
     if _track(ctx, y, x, weight.param, bias) or prev_req:
         y.req = True
@@ -522,6 +540,39 @@ def conv2d_meanpool(ctx, x, weight, bias, in_relu=False, accumulate_into=None):
                                                         _p(dx), C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
         ctx.record(bw)
     return y
+
+
+# The 16x16 down block's forward as one launch (conv_dblock2.hip).  Read once; 0: the four launches (the A/B, the tests' reference side).
+FUSED_DBLOCK2 = os.environ.get("RCGAN_FUSED_DBLOCK2", "1") != "0"
+
+
+def d_block2_ok(ctx, x, w1, frag):
+    """rcgan_dblock2_ok for D.Block.2 on x: [n, 16, 16, 128] 16-bit activations, Conv1's register-filter copy (w1.rf_frag) and the
+    block's own two copies (frag: fragments_batch(dblock2=...)) written for this step's weights."""
+    if not FUSED_DBLOCK2 or not RF_CONV or frag is None or w1.rf_frag is None or len(x.shape) != 4:
+        return False
+    n, h, w, c = x.shape
+    d = L.ConvDesc(n, h, w, c, w1.param.shape[-1], w1.param.shape[0], w1.param.shape[1], 1, x.dtype, L.CONV_IN_RELU)
+    return bool(ctx.lib.rcgan_dblock2_ok(C.byref(d), _p(w1.rf_frag), _p(frag)))
+
+
+def d_block2(ctx, x, ws, bs, w1, b1, w2, b2, frag, _saved=None):
+    """D.Block.2 of the CIFAR discriminator (gan_resnet.py:275-328, resample='down'), forward, as ONE launch (rcgan_dblock2_fwd):
+    y = Shortcut(meanpool2(x)) + ConvMeanPool(relu(Conv1(relu(x)))) with the 16-bit rounding points of the four launches it replaces.
+    The tape gets exactly the four entries those launches record (meanpool2, conv2d, conv2d, conv2d_meanpool, each told its output
+    exists already), so the backward pass is theirs, unchanged."""
+    n = x.shape[0]
+    d = L.ConvDesc(n, 16, 16, 128, 128, 3, 3, 1, x.dtype, L.CONV_IN_RELU)
+    h = ctx.empty((n, 16, 16, 128), x.dtype)
+    xp = ctx.empty((n, 8, 8, 128), x.dtype)
+    y = ctx.empty((n, 8, 8, 128), x.dtype)
+    ctx.check(ctx.lib.rcgan_dblock2_fwd(ctx.h, C.byref(d), _p(x), _p(w1.rf_frag), _p(frag), _p(b1), _p(b2), _p(bs), _p(h), _p(xp), _p(y)))
+    xp = meanpool2(ctx, x, _done=xp)
+    t = conv2d(ctx, xp, ws, bs, 1, _done=y)
+    h = conv2d(ctx, x, w1, b1, 3, in_relu=True, _done=h)
+    if _saved is not None:
+        _saved += [h, xp]           # what the backward entries hold on to, for whoever wants to look (the tests)
+    return conv2d_meanpool(ctx, h, w2, b2, in_relu=True, accumulate_into=t, _done=True)
 
 
 def d_trunk_ok(ctx, x):
@@ -897,10 +948,15 @@ def add(ctx, a, b):
     return y
 
 
-def meanpool2(ctx, x):
+def meanpool2(ctx, x, _done=None):
+    """_done: the tensor a fused launch has already written the pooled x to (ops.d_block2): only the tape entry is recorded."""
     n, h, w, c = x.shape
-    y = ctx.empty((n, h // 2, w // 2, c), x.dtype)
-    ctx.check(ctx.lib.rcgan_meanpool2_fwd(ctx.h, n, h, w, c, x.dtype, _p(x), _p(y)))
+    if _done is not None:
+        y = _done
+        assert y.shape == (n, h // 2, w // 2, c)
+    else:
+        y = ctx.empty((n, h // 2, w // 2, c), x.dtype)
+        ctx.check(ctx.lib.rcgan_meanpool2_fwd(ctx.h, n, h, w, c, x.dtype, _p(x), _p(y)))
     if _track(ctx, y, x):
         def bw():
             if y.grad is None:
