@@ -4,6 +4,7 @@
 #include "small_gemm.h"
 #include "step_inputs.h"
 #include "conv_image.h"
+#include "gather_plan.h"      // colsum_tail_bytes: the column-sum partials at the end of a transposed convolution's workspace
 
 // ---- provided by the other translation units ------------------------------------------------------
 
@@ -865,7 +866,7 @@ int rcgan_deconv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const vo
     (void)oh; (void)ow;
     long rows = (long)d->n * d->h * d->w;
     // partial column sums go to the tail of the workspace (the filter-gradient slabs sit at its head and are consumed)
-    size_t need = ((size_t)(cdiv(rows, 2048) + 1024) * d->cin * sizeof(float) + 255) / 256 * 256;
+    size_t need = colsum_tail_bytes(rows, d->cin);
     float* part = (ws != nullptr && ws_bytes >= direct_wgrad_ws_bytes(d) + need) ? (float*)((char*)ws + (ws_bytes - need) / 256 * 256) : nullptr;
     RC_DISPATCH_DTYPE(ctx, d->dtype, rc = colsum_launch<T>(ctx, (const T*)dy, rows, d->cin, dbias, accumulate, part));
     if (rc) return rc;
@@ -876,7 +877,7 @@ int rcgan_deconv2d_bwd_weight(rcgan_ctx* ctx, const rcgan_conv_desc* d, const vo
 size_t rcgan_deconv2d_bwd_weight_concat_bytes(const rcgan_conv_desc* d, int n_cols) {
   if (!d || n_cols <= 0 || n_cols >= d->cout) return 0;
   const long rows = (long)d->n * d->h * d->w;
-  return direct_wgrad_cols_ws_bytes(d, n_cols) + ((size_t)(cdiv(rows, 2048) + 1024) * d->cin * sizeof(float) + 255) / 256 * 256 + 256;
+  return direct_wgrad_cols_ws_bytes(d, n_cols) + colsum_tail_bytes(rows, d->cin) + 256;
 }
 
 int rcgan_deconv2d_bwd_weight_concat(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* dy, int n_cols, const float* yb,
@@ -891,7 +892,7 @@ int rcgan_deconv2d_bwd_weight_concat(rcgan_ctx* ctx, const rcgan_conv_desc* d, c
   if (rc) return rc;
   if (dbias) {
     const long rows = (long)d->n * d->h * d->w;
-    const size_t tail = ((size_t)(cdiv(rows, 2048) + 1024) * d->cin * sizeof(float) + 255) / 256 * 256;
+    const size_t tail = colsum_tail_bytes(rows, d->cin);
     float* part = (float*)((char*)ws + (ws_bytes - tail) / 256 * 256);
     RC_DISPATCH_DTYPE(ctx, d->dtype, rc = colsum_launch<T>(ctx, (const T*)dy, rows, d->cin, dbias, accumulate, part));
     if (rc) return rc;

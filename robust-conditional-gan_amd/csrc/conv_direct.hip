@@ -9,32 +9,8 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gather_plan.h"      // FastDiv, the stride-2 class table and every launch decision of this file
 #include <type_traits>
-
-// Division by a launch-invariant 32-bit divisor as multiply-high + shifts (Granlund-Montgomery, branch-free form):
-// the operand decode of every K-step divides by the channel count and the filter width, ~30 VALU ops each when the
-// compiler has to expand a general division.
-struct FastDiv {
-  unsigned d, m, s;
-  __host__ __device__ __forceinline__ unsigned div(unsigned n) const {
-#if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned t = __umulhi(n, m);
-#else
-    const unsigned t = (unsigned)(((unsigned long long)n * m) >> 32);
-#endif
-    const unsigned q = (t + ((n - t) >> 1)) >> s;
-    return d == 1 ? n : q;
-  }
-};
-static FastDiv make_fastdiv(unsigned d) {
-  FastDiv f; f.d = d; f.m = 0; f.s = 0;
-  if (d <= 1) return f;
-  unsigned l = 0;
-  while ((1ull << l) < d) ++l;                       // ceil(log2 d)
-  f.m = (unsigned)(((1ull << 32) * ((1ull << l) - d)) / d + 1);
-  f.s = l - 1;
-  return f;
-}
 
 struct ConvGeom {
   int N, H, W, Cin;      // logical conv input (post-upsample)
@@ -83,12 +59,7 @@ template <typename T> struct Vec2 {
   __device__ __forceinline__ static Vec2 load(const T* p) { Vec2 r; r.v = *(const typename VecOf<T>::v2*)p; return r; }
 };
 
-template <typename T> static int vec_of(const T* p, long c) {
-  const uintptr_t a = (uintptr_t)p;
-  if (c % 4 == 0 && a % (4 * sizeof(T)) == 0) return 4;
-  if (c % 2 == 0 && a % (2 * sizeof(T)) == 0) return 2;
-  return 1;
-}
+template <typename T> static int vec_of(const T* p, long c) { return gather_vec_of((uintptr_t)p, c, sizeof(T)); }
 
 // 4 contiguous elements
 template <typename T> __device__ __forceinline__ void ld4(const T* p, int vec, T* out) {
@@ -320,8 +291,7 @@ template <typename T> struct DgradOp {
 //      kh = kh0 + 2*jh, kw = kw0 + 2*jw (kh0 = (ph + PT) % 2) reach an output pixel, so the reduction runs over
 //      ceil(KH/2) x ceil(KW/2) x Cout instead of KH x KW x Cout with three quarters of the gathers returning zero.
 //      i = (n, ih/2, iw/2) inside the class, j = ci, r = (jh, jw, co).
-struct S2Cls { int ph, pw, Hp, Wp, kh0, kw0, nkh, nkw, dh, dwc; long M, R; FastDiv dnkw; };
-struct S2Table { S2Cls cls[4]; };
+//      (S2Cls / S2Table, and which classes a layer has: gather_plan.h)
 template <typename T> struct DgradS2Op {
   typedef T AT; typedef float BT;
   static constexpr bool A_KMAJOR = true, B_KMAJOR = true;
@@ -592,7 +562,7 @@ template <class Op> __device__ __forceinline__ auto b_init(const Op& op, long j0
   else return j0 + (tid & 15) * 4;
 }
 
-#define GG_XBUF 2304   /* floats per operand buffer: max(64 x 36 K-major, 32 x 68 N-major) */
+// (GG_XBUF, the floats per operand buffer: gather_plan.h)
 
 // Split-bf16 MFMA ("high" fp32 matmul precision, rcgan_set_f32_matmul_precision): every fp32 operand element x is stored as
 // hi = bf16(x), lo = bf16(x - hi) (round to nearest even; x - hi is exact in fp32) and a K-step of 32 runs as two 16-wide halves
@@ -803,18 +773,19 @@ __global__ __launch_bounds__(256 * KS) void gemm_gather_kernel(Op op_in, typenam
       buf ^= 1;
     }
   }
-  if constexpr (KS > 1) {                          // sum the groups' accumulators: [group-1][wave][reg][lane]
+  if constexpr (KS > 1) {                          // sum the groups' accumulators: [group-1][wave][reg][lane], GG_RED_FLOATS per group
+    static_assert(GG_RED_FLOATS == 4 * 16 * 64 && (KS - 1) * GG_RED_FLOATS <= KS * 4 * GG_XBUF, "the reduction area lies inside the operand buffers");
     float* red = gg_smem;
     if (kg > 0) {
 #pragma unroll
-      for (int p = 0; p < 16; ++p) red[(((kg - 1) * 4 + wv) * 16 + p) * 64 + lane] = acc[p];
+      for (int p = 0; p < 16; ++p) red[(kg - 1) * GG_RED_FLOATS + (wv * 16 + p) * 64 + lane] = acc[p];
     }
     __syncthreads();
     if (kg > 0) return;
 #pragma unroll
     for (int g2 = 0; g2 < KS - 1; ++g2)
 #pragma unroll
-      for (int p = 0; p < 16; ++p) acc[p] += red[((g2 * 4 + wv) * 16 + p) * 64 + lane];
+      for (int p = 0; p < 16; ++p) acc[p] += red[g2 * GG_RED_FLOATS + (wv * 16 + p) * 64 + lane];
   }
   const long j = j0 + wc * 32 + l31;
   if (j < op.N) {
@@ -1026,6 +997,21 @@ static int gg_env_int(const char* name, int dflt) {
   const char* e = getenv(name);
   return (e && *e) ? atoi(e) : dflt;
 }
+// the switches of gather_plan.h, read once at the first call that plans
+static const GatherSwitches& gather_switches() {
+  static const GatherSwitches s = [] {
+    GatherSwitches v;
+    v.ks_min_steps = gg_env_int("RCGAN_GG_KS_MINSTEPS", v.ks_min_steps);
+    v.ks_force = gg_env_int("RCGAN_GG_KS", v.ks_force);
+    v.ks2_min_wgs = gg_env_int("RCGAN_GG_KS2_MINWGS", (int)v.ks2_min_wgs);
+    v.split_r = gg_env_int("RCGAN_GG_SPLIT_R", v.split_r);
+    v.wgrad_fit = gg_env_int("RCGAN_GG_WGRAD_FIT", v.wgrad_fit);
+    v.narrow_two_step = gg_env_int("RCGAN_NARROW_TWO_STEP", v.narrow_two_step);
+    v.s2_lpt = gg_env_int("RCGAN_S2_LPT", v.s2_lpt);
+    return v;
+  }();
+  return s;
+}
 
 template <class Op, int KS, bool SPLIT>
 static int launch_gemm_kernel(rcgan_ctx* ctx, Op& op, dim3 grid, const typename Op::Aux& aux) {
@@ -1058,49 +1044,27 @@ static int launch_gemm_ks(rcgan_ctx* ctx, Op& op, dim3 grid, const typename Op::
 template <class Op>
 static int launch_gemm(rcgan_ctx* ctx, Op& op, int nz, const typename Op::Aux& aux = typename Op::Aux()) {
   op.zp = ctx->zero_page;
+  if (!gather_grid_ok(op.M, nz)) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "M too large");
   dim3 grid(cdiv(op.N, 64), cdiv(op.M, 64), nz);
-  if (grid.y > 65535u || grid.z > 65535u) RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "M too large");
-  static const int ks_min_steps = gg_env_int("RCGAN_GG_KS_MINSTEPS", 8);
-  const long steps = (op.r_chunk + 31) / 32;
-  static const int ks_force = gg_env_int("RCGAN_GG_KS", 0);
-  if (ks_force == 2) return launch_gemm_ks<Op, 2>(ctx, op, grid, aux);
-  if (ks_force == 1) return launch_gemm_ks<Op, 1>(ctx, op, grid, aux);
-  if (steps >= ks_min_steps) {
-    // four K-slices per workgroup = 1024 threads = ONE workgroup per CU: a grid of more workgroups than CUs runs in whole rounds (392
-    // workgroups: two, the second half empty).  Two slices = two workgroups per CU, the same K-steps per wavefront pair -- measured on the
-    // MNIST iteration (B = 256), per launch: 1568 workgroups 214 -> 177 us, 1666 111 -> 84, 392 170 -> 161; but 196 workgroups 46 -> 53,
-    // 128 44 -> 51 (fewer workgroups than CUs: the four slices are the parallelism).
-    static const long ks2_min_wgs = gg_env_int("RCGAN_GG_KS2_MINWGS", 256);
-    if ((long)grid.x * grid.y * grid.z >= ks2_min_wgs) return launch_gemm_ks<Op, 2>(ctx, op, grid, aux);
-    return launch_gemm_ks<Op, 4>(ctx, op, grid, aux);
+  switch (gather_ks(op.r_chunk, gather_wgs(op.M, op.N, nz), gather_switches())) {      // (why 1, 2 or 4: gather_plan.h)
+    case 4: return launch_gemm_ks<Op, 4>(ctx, op, grid, aux);
+    case 2: return launch_gemm_ks<Op, 2>(ctx, op, grid, aux);
+    default: return launch_gemm_ks<Op, 1>(ctx, op, grid, aux);
   }
-  return launch_gemm_ks<Op, 1>(ctx, op, grid, aux);
 }
 
 // Forward / data-gradient GEMMs with few output tiles and a long reduction (the MNIST critic's 4x4 and 2x2 layers: 64 / 16 tiles over
 // K = 1600; the generator's 6272 -> 1024 dense data gradient: 64 tiles over K = 6272) leave most of the chip idle behind a serial chain
 // of K-steps.  Here the reduction is cut into nz chunks (grid.z) that write fp32 partial tiles to a scratch slab; a second launch adds
 // them up in a fixed order (+ bias, + the accumulate target).  fp32 outputs only; the scratch is the context's grow-only buffer.
-static int split_r_enabled() {
-  static const int v = gg_env_int("RCGAN_GG_SPLIT_R", 1);
-  return v;
-}
-static int split_r_chunks(long M, long N, long R, int kind = 1) {      // kind 1: convolution forward, 2: dense data gradient
-  const long tiles = (long)cdiv(M, 64) * cdiv(N, 64), steps = (R + 31) / 32;
-  const int en = split_r_enabled();        // (debug: 2 = convolutions only, 3 = dense layers only)
-  if (!en || (en == 2 && kind != 1) || (en == 3 && kind != 2) || tiles >= 128 || steps < 32) return 1;
-  long nz = 256 / tiles;
-  if (nz > steps / 8) nz = steps / 8;       // >= 8 K-steps per chunk
-  if (nz > 8) nz = 8;
-  return nz < 2 ? 1 : (int)nz;
-}
 template <class Op>
 static int launch_gemm_split_r(rcgan_ctx* ctx, Op& op, int nz, float* out, long ld_count, const float* bias, int ncols, int accumulate) {
   const size_t need = (size_t)nz * ld_count * sizeof(float);
   RC_HIP(ctx, ctx_grow_scratch(ctx, &ctx->splitr_ws, &ctx->splitr_ws_bytes, need));
   op.slab = (float*)ctx->splitr_ws;
-  op.r_chunk = (((op.R + nz - 1) / nz) + 31) / 32 * 32;
-  nz = (int)cdiv(op.R, op.r_chunk);
+  const GatherChunks ch = split_r_plan(op.R, nz);
+  op.r_chunk = ch.r_chunk;
+  nz = ch.nz;
   int rc = launch_gemm(ctx, op, nz);
   if (rc != RCGAN_OK) return rc;
   hipLaunchKernelGGL(slab_reduce_bias_kernel, dim3((unsigned)cdiv(ld_count, 256)), dim3(256), 0, ctx->stream, (const float*)op.slab, out, ld_count, nz,
@@ -1109,69 +1073,27 @@ static int launch_gemm_split_r(rcgan_ctx* ctx, Op& op, int nz, float* out, long 
   return RCGAN_OK;
 }
 
-// pick the number of r-splits for a filter-gradient GEMM so the grid fills the chip
-static int wgrad_splits(long K, long Cout, long M) {
-  long tiles = (long)cdiv(K, 64) * cdiv(Cout, 64);
-  long want = (1024 + tiles - 1) / tiles;
-  long maxs = (M + 255) / 256;
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  if (want > 256) want = 256;
-  // (round 6) whole rounds: such a grid runs two 512-thread workgroups per CU (launch_gemm: two K-slices, 74 KB of LDS each), 512 at
-  // a time on 256 CUs.  tiles x splits just above a multiple of 512 -- the MNIST generator's 5x5 transposed convolution: 150 tiles
-  // x 7 splits = 1050 -- pays a whole extra round for a few workgroups; one split less (900: two rounds of 17 % longer workgroups)
-  // is the shorter launch.  RCGAN_GG_WGRAD_FIT=0: the plain ceil(1024 / tiles).
-  static const int fit = gg_env_int("RCGAN_GG_WGRAD_FIT", 1);
-  if (fit && want > 1 && tiles * want >= 512) {
-    const long over = (tiles * want) % 512;
-    if (over != 0 && over * 4 < 512) {               // the last round less than a quarter full
-      long w2 = want;
-      while (w2 > 1 && (tiles * w2) % 512 != 0 && ((tiles * w2) % 512) * 4 < 512 && tiles * w2 > 512) --w2;
-      // accept when the rounds saved outweigh the longer workgroups: rounds(w2) / w2 < rounds(want) / want
-      const long r1 = (tiles * want + 511) / 512, r2 = (tiles * w2 + 511) / 512;
-      if (r2 * want < r1 * w2) want = w2;
-    }
-  }
-  return (int)want;
-}
-
 size_t direct_wgrad_ws_bytes(const rcgan_conv_desc* d) {
   ConvGeom g = make_geom(d);
-  long K = (long)g.KH * g.KW * g.Cin, M = (long)g.N * g.OH * g.OW;
-  int nz = wgrad_splits(K, g.Cout, M);
-  size_t bias_part = (size_t)(cdiv(M, 2048) + 1024) * g.Cout * sizeof(float);
-  return (size_t)nz * K * g.Cout * sizeof(float) + bias_part + 256;
+  return gather_wgrad_ws_bytes((long)g.KH * g.KW * g.Cin, g.Cout, (long)g.N * g.OH * g.OW, gather_switches());
 }
 
 template <typename T>
 int colsum_launch(rcgan_ctx* ctx, const T* x, long rows, int c, float* out, int accumulate, float* partial_ws) {
-  if (partial_ws != nullptr && rows >= 2048 && c % 8 == 0 && c <= 256 && 256 % (c / 8) == 0) {
-    long rpb = 256;
-    while ((rows + rpb - 1) / rpb > 1024) rpb *= 2;
-    int nb = cdiv(rows, rpb);          // <= 1024 <= the cdiv(rows, 2048)*... slots? see colsum_ws_rows()
-    hipLaunchKernelGGL(colsum_vec_partial_kernel<T>, dim3(nb), dim3(256), 0, ctx->stream, x, rows, c, rpb, partial_ws);
-    RC_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3(cdiv(c, 64)), dim3(256), 0, ctx->stream, (const float*)partial_ws, (long)nb, c, out, accumulate);
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  if (partial_ws != nullptr && rows >= 4096 && c <= 8) {
-    long rpb = 1024;
-    while ((rows + rpb - 1) / rpb > 1024) rpb *= 2;
-    int nb = cdiv(rows, rpb);
-    hipLaunchKernelGGL(colsum_narrow_partial_kernel<T>, dim3(nb), dim3(256), 0, ctx->stream, x, rows, c, rpb, partial_ws);
-    RC_LAUNCH_CHECK(ctx);
-    hipLaunchKernelGGL(colsum_kernel<float>, dim3(cdiv(c, 64)), dim3(256), 0, ctx->stream, (const float*)partial_ws, (long)nb, c, out, accumulate);
-    RC_LAUNCH_CHECK(ctx);
-    return RCGAN_OK;
-  }
-  if (rows <= 4096 || partial_ws == nullptr) {
+  // partial_ws holds colsum_partial_floats(rows, c) floats (every caller reserves that); the plan's nb * c stay within them
+  const ColsumPlan p = colsum_plan(rows, c, partial_ws != nullptr);
+  if (p.route == COLSUM_SINGLE) {
     hipLaunchKernelGGL(colsum_kernel<T>, dim3(cdiv(c, 64)), dim3(256), 0, ctx->stream, x, rows, c, out, accumulate);
     RC_LAUNCH_CHECK(ctx);
     return RCGAN_OK;
   }
-  int nb = cdiv(rows, 2048);
-  hipLaunchKernelGGL(colsum_partial_kernel<T>, dim3(cdiv(c, 64), nb), dim3(256), 0, ctx->stream, x, rows, c, (long)2048, partial_ws);
+  const int nb = (int)p.nb;
+  if (p.route == COLSUM_VEC)
+    hipLaunchKernelGGL(colsum_vec_partial_kernel<T>, dim3(nb), dim3(256), 0, ctx->stream, x, rows, c, p.rows_per_blk, partial_ws);
+  else if (p.route == COLSUM_NARROW)
+    hipLaunchKernelGGL(colsum_narrow_partial_kernel<T>, dim3(nb), dim3(256), 0, ctx->stream, x, rows, c, p.rows_per_blk, partial_ws);
+  else
+    hipLaunchKernelGGL(colsum_partial_kernel<T>, dim3(cdiv(c, 64), nb), dim3(256), 0, ctx->stream, x, rows, c, p.rows_per_blk, partial_ws);
   RC_LAUNCH_CHECK(ctx);
   hipLaunchKernelGGL(colsum_kernel<float>, dim3(cdiv(c, 64)), dim3(256), 0, ctx->stream, (const float*)partial_ws, (long)nb, c, out, accumulate);
   RC_LAUNCH_CHECK(ctx);
@@ -1252,7 +1174,7 @@ __global__ __launch_bounds__(256) void linear_tiny_kernel(int m, int k, int n, c
   }
 }
 
-static inline bool linear_tiny(long outputs, long red) { return outputs <= 65536 && red <= 4096; }
+// (linear_tiny, which layers this kernel takes: gather_plan.h)
 
 // y[row][n <= 16]: the GEMM tiling would put the whole reduction in one workgroup (one 64-column tile); here one
 // workgroup per row splits K over its 256 threads (the RCGAN permutation classifier: [B,3072] x [3072,10]).
@@ -1288,7 +1210,7 @@ __global__ __launch_bounds__(256) void linear_skinny_fwd_kernel(int k, int n, co
 
 template <typename T>
 int linear_fwd(rcgan_ctx* ctx, long m, long k, long n, const T* x, const float* w, const float* wscale, const float* bias, T* y) {
-  if (n <= 16 && k >= 512 && m <= 65535) {
+  if (linear_skinny(m, k, n)) {
     hipLaunchKernelGGL(linear_skinny_fwd_kernel<T>, dim3((int)m), dim3(256), 0, ctx->stream, (int)k, (int)n, x, w, wscale, bias, y);
     RC_LAUNCH_CHECK(ctx);
     return RCGAN_OK;
@@ -1321,7 +1243,7 @@ int linear_dgrad(rcgan_ctx* ctx, long m, long k, long n, const T* dy, const floa
   op.M = m; op.N = k; op.R = n; op.r_chunk = n;
   op.avec = vec_of(dy, n); op.bvec = vec_of(w, n);
   if constexpr (std::is_same<T, float>::value) {
-    const int nz = split_r_chunks(m, k, n, 2);
+    const int nz = split_r_chunks(m, k, n, 2, gather_switches());
     if (nz > 1) return launch_gemm_split_r(ctx, op, nz, (float*)dx, m * k, nullptr, (int)k, accumulate);
   }
   return launch_gemm(ctx, op, 1);
@@ -1329,10 +1251,7 @@ int linear_dgrad(rcgan_ctx* ctx, long m, long k, long n, const T* dy, const floa
 template int linear_dgrad<float>(rcgan_ctx*, long, long, long, const float*, const float*, const float*, float*, int);
 template int linear_dgrad<bf16_t>(rcgan_ctx*, long, long, long, const bf16_t*, const float*, const float*, bf16_t*, int);
 
-size_t linear_wgrad_ws_bytes(long m, long k, long n) {
-  int nz = m <= 1024 ? 1 : wgrad_splits(k, n, m);
-  return (size_t)(nz > 1 ? nz : 0) * k * n * sizeof(float) + (size_t)(cdiv(m, 2048) + 1024) * n * sizeof(float) + 256;
-}
+size_t linear_wgrad_ws_bytes(long m, long k, long n) { return linear_wgrad_plan_bytes(m, k, n, gather_switches()); }
 
 template <typename T>
 int linear_wgrad(rcgan_ctx* ctx, long m, long k, long n, const T* x, const T* dy, float* dw, float* dbias, int accumulate,
@@ -1349,8 +1268,8 @@ int linear_wgrad(rcgan_ctx* ctx, long m, long k, long n, const T* x, const T* dy
   op.x = x; op.dy = dy; op.wscale = nullptr; op.accumulate = accumulate;
   op.M = k; op.N = n; op.R = m;
   op.avec = vec_of(x, k); op.bvec = vec_of(dy, n);
-  int nz = m <= 1024 ? 1 : wgrad_splits(k, n, m);
-  size_t slab_bytes = (size_t)(nz > 1 ? nz : 0) * k * n * sizeof(float);
+  int nz = linear_wgrad_splits(m, k, n, gather_switches());
+  size_t slab_bytes = linear_wgrad_slab_bytes(m, k, n, gather_switches());
   if (ws_bytes < linear_wgrad_ws_bytes(m, k, n)) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", linear_wgrad_ws_bytes(m, k, n), ws_bytes);
   if (nz == 1) {
     op.direct = 1; op.out = dw; op.r_chunk = m;
@@ -1358,8 +1277,9 @@ int linear_wgrad(rcgan_ctx* ctx, long m, long k, long n, const T* x, const T* dy
     if (rc) return rc;
   } else {
     op.direct = 0; op.out = (float*)ws;
-    op.r_chunk = ((m + nz - 1) / nz + 15) / 16 * 16;
-    nz = cdiv(m, op.r_chunk);
+    const GatherChunks ch = wgrad_plan(m, nz);
+    op.r_chunk = ch.r_chunk;
+    nz = ch.nz;
     int rc = launch_gemm(ctx, op, nz);
     if (rc) return rc;
     long cnt = k * n;
@@ -1386,7 +1306,7 @@ int direct_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* x, const float
   op.ldy = (int)op.N; op.slab = nullptr;
   op.avec = vec_of(x, op.g.Cin); op.bvec = vec_of(w, op.g.Cout);
   if constexpr (std::is_same<T, float>::value) {
-    const int nz = split_r_chunks(op.M, op.N, op.R);
+    const int nz = split_r_chunks(op.M, op.N, op.R, 1, gather_switches());
     if (nz > 1) return launch_gemm_split_r(ctx, op, nz, (float*)y, op.M * op.ldy, bias, op.ldy, op.accumulate);
   }
   return launch_gemm(ctx, op, 1);
@@ -1423,11 +1343,6 @@ __global__ __launch_bounds__(256) void col2im_s2_kernel(long total, ConvGeom g, 
   dx[e] = accumulate ? dx[e] + v : v;
 }
 
-static int narrow_two_step_enabled() {
-  static const int v = gg_env_int("RCGAN_NARROW_TWO_STEP", 1);
-  return v;
-}
-
 // dgrad at the LOGICAL input resolution (no upsample folding here; the caller pools afterwards).
 template <typename T>
 int direct_dgrad(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* dy, const float* w, const float* wscale, const float* bias,
@@ -1439,40 +1354,21 @@ int direct_dgrad(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* dy, const fl
       op.g = g; op.g.up = 0; op.dy = dy; op.w = w; op.wscale = wscale; op.bias = bias; op.dx = dx; op.xmask = xmask; op.accumulate = accumulate;
       op.N = g.Cin;
       op.avec = vec_of(dy, g.Cout); op.bvec = vec_of(w, g.Cout);
-      S2Table tab;
-      int ncls = 0;
-      long maxM = 0, maxR = 0;
-      for (int ph = 0; ph < 2; ++ph)
-        for (int pw = 0; pw < 2; ++pw) {
-          S2Cls c;
-          c.ph = ph; c.pw = pw; c.Hp = (g.H - ph + 1) / 2; c.Wp = (g.W - pw + 1) / 2;
-          if (c.Hp <= 0 || c.Wp <= 0) continue;
-          c.kh0 = (ph + g.PT) % 2; c.kw0 = (pw + g.PL) % 2;
-          c.nkh = g.KH > c.kh0 ? (g.KH - c.kh0 + 1) / 2 : 0;
-          c.nkw = g.KW > c.kw0 ? (g.KW - c.kw0 + 1) / 2 : 0;
-          c.dh = (ph + g.PT - c.kh0) / 2; c.dwc = (pw + g.PL - c.kw0) / 2;
-          if (c.nkw == 0) { c.nkw = 1; c.nkh = 0; }          // keeps the divisions defined; R = 0: outputs are bias / 0
-          c.dnkw = make_fastdiv(c.nkw);
-          c.M = (long)g.N * c.Hp * c.Wp; c.R = (long)c.nkh * c.nkw * g.Cout;
-          if (c.M > maxM) maxM = c.M;
-          if (c.R > maxR) maxR = c.R;
-          tab.cls[ncls++] = c;
-        }
+      const S2Plan plan = s2_classes(g.N, g.H, g.W, g.Cout, g.KH, g.KW, g.PT, g.PL, gather_switches());      // the parity classes, longest first
+      const S2Table& tab = plan.tab;
+      const int ncls = plan.ncls;
+      const long maxM = plan.maxM, maxR = plan.maxR;
       if (ncls == 0) return RCGAN_OK;
-      // (round 6) longest class first: grid.z is the slowest dispatch index, and with a 5x5 filter the classes reduce over 4, 6, 6 and 9
-      // taps -- in (ph, pw) order the 9-tap workgroups started last and the launch ended on them alone.  RCGAN_S2_LPT=0: (ph, pw) order.
-      static const int lpt = gg_env_int("RCGAN_S2_LPT", 1);
-      if (lpt) std::stable_sort(tab.cls, tab.cls + ncls, [](const S2Cls& a, const S2Cls& b) { return a.R * a.M > b.R * b.M; });
-      for (int q = ncls; q < 4; ++q) tab.cls[q] = tab.cls[0];
       // launch-shape fields (the kernel re-selects per class)
       op.M = maxM; op.R = maxR; op.r_chunk = maxR;
       { const auto& c = tab.cls[0]; op.ph = c.ph; op.pw = c.pw; op.Hp = c.Hp; op.Wp = c.Wp; op.kh0 = c.kh0; op.kw0 = c.kw0;
         op.nkh = c.nkh; op.nkw = c.nkw; op.dh = c.dh; op.dwc = c.dwc; op.dnkw = c.dnkw; }
+      // one or two output channels, fp32, no ReLU mask: products per source pixel on the matrix cores + col2im (above)
+      const long m = (long)g.N * g.OH * g.OW, kcols = (long)g.KH * g.KW * g.Cin;
+      const size_t need = (size_t)m * kcols * sizeof(float);
+      const S2Route route = s2_route(std::is_same<T, float>::value, op.N, xmask != nullptr, g.Cout, need, maxR, gather_switches());
       if constexpr (std::is_same<T, float>::value) {
-        // one or two output channels, fp32, no ReLU mask: products per source pixel on the matrix cores + col2im (above)
-        const long m = (long)g.N * g.OH * g.OW, kcols = (long)g.KH * g.KW * g.Cin;
-        const size_t need = (size_t)m * kcols * sizeof(float);
-        if (narrow_two_step_enabled() && op.N <= 2 && xmask == nullptr && g.Cout >= 32 && need <= ((size_t)1 << 30)) {
+        if (route == S2_TWO_STEP) {
           RC_HIP(ctx, ctx_grow_scratch(ctx, &ctx->narrow_ws, &ctx->narrow_ws_bytes, need));
           int rc = linear_dgrad<float>(ctx, m, kcols, g.Cout, (const float*)dy, w, wscale, (float*)ctx->narrow_ws, 0);
           if (rc != RCGAN_OK) return rc;
@@ -1483,7 +1379,7 @@ int direct_dgrad(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* dy, const fl
           return RCGAN_OK;
         }
       }
-      if (op.N <= 4 && maxR > 0 && (size_t)maxR * op.N * sizeof(float) <= 48 * 1024) return launch_dgrad_s2_narrow(ctx, op, tab, ncls, maxM, maxR);
+      if (route == S2_NARROW) return launch_dgrad_s2_narrow(ctx, op, tab, ncls, maxM, maxR);
       return launch_gemm(ctx, op, ncls, tab);
     }
   }
@@ -1502,21 +1398,22 @@ int direct_wgrad(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* x, const T* 
   WgradOp<T> op;
   op.g = make_geom(d); op.x = x; op.dy = dy; op.wscale = nullptr;
   long K = (long)op.g.KH * op.g.KW * op.g.Cin, M = (long)op.g.N * op.g.OH * op.g.OW;
-  int nz = wgrad_splits(K, op.g.Cout, M);
+  int nz = wgrad_splits(K, op.g.Cout, M, gather_switches());
   size_t need = direct_wgrad_ws_bytes(d);
   if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
   op.slab = (float*)ws;
   op.M = K; op.N = op.g.Cout; op.R = M;
   op.avec = vec_of(x, op.g.Cin); op.bvec = vec_of(dy, op.g.Cout);
-  op.r_chunk = ((M + nz - 1) / nz + 15) / 16 * 16;
-  nz = cdiv(M, op.r_chunk);
+  const GatherChunks ch = wgrad_plan(M, nz);
+  op.r_chunk = ch.r_chunk;
+  nz = ch.nz;
   int rc = launch_gemm(ctx, op, nz);
   if (rc) return rc;
   long cnt = K * op.g.Cout;
   hipLaunchKernelGGL(slab_reduce_kernel, dim3(cdiv(cnt, 64)), dim3(256), 0, ctx->stream, (const float*)op.slab, dw, cnt, nz, accumulate);
   RC_LAUNCH_CHECK(ctx);
   if (dbias) {
-    float* part = (float*)((char*)ws + (size_t)wgrad_splits(K, op.g.Cout, M) * K * op.g.Cout * sizeof(float));
+    float* part = (float*)((char*)ws + gather_wgrad_slab_bytes(K, op.g.Cout, M, gather_switches()));
     rc = colsum_launch<T>(ctx, dy, M, op.g.Cout, dbias, accumulate, part);
     if (rc) return rc;
   }
@@ -1533,7 +1430,7 @@ int direct_wgrad(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* x, const T* 
 // -- D is a sum over a sub-grid of the image, separable in rows and columns: ONE pass over x (wgrad_label_sums_kernel), then a
 // [c2 x N] x [N x K] product in sample chunks (wgrad_label_cols_kernel), and one reduction that writes the c1 columns from the GEMM's
 // slabs and the c2 columns from the chunk partials with the filter's own row stride.
-#define WGRAD_LABEL_RG 4        /* row groups: a sample's image rows ih = rg, rg + 4, ... go to workgroup (n, rg) */
+// (WGRAD_LABEL_RG row groups: a sample's image rows ih = rg, rg + 4, ... go to workgroup (n, rg); gather_plan.h)
 // which image columns (rows) a tap column kw (row kh) reaches: bit iw of col[kw] is set iff (iw + PL - kw) is a multiple of S inside the
 // output grid -- computed on the host, so the kernel's inner loop is a mask test instead of two integer divisions per (pixel, tap)
 struct LabelMasks { unsigned col[5], row[5]; };
@@ -1582,7 +1479,6 @@ __global__ __launch_bounds__(128) void wgrad_label_sums_kernel(ConvGeom g, Label
 
 // partial[chunk][i][l] = sum over the chunk's samples (at most 8) of yb[n][l] * D[n][i]   (i = (kh, kw, c), K of them; c2 <= 16)
 // (D arrives as WGRAD_LABEL_RG row-group partials [rg][n][K], summed here in a fixed order; every load of the chunk in flight at once)
-#define WGRAD_LABEL_PER_CHUNK 8
 __global__ __launch_bounds__(128) void wgrad_label_cols_kernel(const float* D, const float* yb, int N, long K, int c2, float* partial) {
   __shared__ float yb_s[WGRAD_LABEL_PER_CHUNK * 16];
   const int n0 = blockIdx.y * WGRAD_LABEL_PER_CHUNK;
@@ -1644,9 +1540,7 @@ __global__ void slab_reduce_cols_kernel(const float* slab, int nz, const float* 
 size_t direct_wgrad_cols_ws_bytes(const rcgan_conv_desc* d, int c1) {
   ConvGeom g = make_geom(d);
   const long K = (long)g.KH * g.KW * g.Cin, M = (long)g.N * g.OH * g.OW;
-  const int c2 = g.Cout - c1;
-  const int nz = wgrad_splits(K, c1, M);
-  return ((size_t)nz * K * c1 + (size_t)WGRAD_LABEL_RG * g.N * K + (size_t)cdiv(g.N, WGRAD_LABEL_PER_CHUNK) * K * c2) * sizeof(float) + 1024;
+  return gather_wgrad_cols_ws_bytes(K, c1, g.Cout - c1, M, g.N, gather_switches());
 }
 
 // dy rows: [c1 real columns ; c2 = Cout - c1 label columns = yb[n][:]]  (yb: fp32 [N][c2], c2 <= 16; KH, KW <= 5)
@@ -1659,12 +1553,13 @@ int direct_wgrad_cols(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* x, cons
   if (c1 <= 0 || (c1 & 3) || c2 <= 0 || c2 > 16 || op.g.KH > 5 || op.g.KW > 5 || op.g.W > 32 || op.g.H > 32 || op.g.up || yb == nullptr)
     RC_FAIL(ctx, RCGAN_EUNSUPPORTED_SHAPE, "label-column filter gradient: %d + %d columns, %d x %d filter", c1, c2, op.g.KH, op.g.KW);
   const long K = (long)op.g.KH * op.g.KW * op.g.Cin, M = (long)op.g.N * op.g.OH * op.g.OW;
-  int nz = wgrad_splits(K, c1, M);
+  int nz = wgrad_splits(K, c1, M, gather_switches());
   const size_t need = direct_wgrad_cols_ws_bytes(d, c1);
   if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
+  const WgradColsLayout lay = gather_wgrad_cols_layout(K, c1, c2, M, op.g.N, gather_switches());
   float* const slab = (float*)ws;
-  float* const Dn = slab + (size_t)nz * K * c1;
-  float* const partial = Dn + (size_t)WGRAD_LABEL_RG * op.g.N * K;
+  float* const Dn = slab + lay.D;
+  float* const partial = slab + lay.partial;
   // the label columns' two small launches first (they only read x and yb), then the GEMM over the real columns
   LabelMasks mk;
   for (int t = 0; t < 5; ++t) {
@@ -1684,8 +1579,9 @@ int direct_wgrad_cols(rcgan_ctx* ctx, const rcgan_conv_desc* d, const T* x, cons
   op.slab = slab;
   op.M = K; op.N = c1; op.R = M;               // (the row stride of dy stays g.Cout: b4 reads columns j < N of a Cout-wide row)
   op.avec = vec_of(x, op.g.Cin); op.bvec = vec_of(dy, op.g.Cout);
-  op.r_chunk = ((M + nz - 1) / nz + 15) / 16 * 16;
-  nz = cdiv(M, op.r_chunk);
+  const GatherChunks ch = wgrad_plan(M, nz);
+  op.r_chunk = ch.r_chunk;
+  nz = ch.nz;
   int rc = launch_gemm(ctx, op, nz);
   if (rc) return rc;
   const long cnt = K * ((c1 >> 2) + c2);
