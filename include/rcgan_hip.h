@@ -536,7 +536,15 @@ int rcgan_conv2d_rf(rcgan_ctx* ctx, const rcgan_conv_desc* d, int backward, cons
  * dtype, any n >= 1) and both fragment copies exist.  conv1_frag: Conv1's copy of rcgan_conv_rf_prepare / rcgan_fragments_prepare;
  * dblock2_frag (rcgan_dblock2_fragment_bytes): written by rcgan_fragments_prepare_dblock2 -- rcgan_fragments_prepare with two more
  * items in the same launch -- from conv2_prepared = Conv2's prepared filter under RCGAN_CONV_OUT_MEANPOOL2 and shortcut_prepared = the
- * 1x1 shortcut's. */
+ * 1x1 shortcut's.
+ * rcgan_dblock2_bwd (csrc/conv_dblock2_bwd.hip): the block's data gradient as one launch with the same geometry, from dy [n][8][8][128] and
+ * the forward's h and x (ReLU masks):
+ *   dh = 16bit([h > 0] . (Conv2 + pool)^T(dy));  dxp = 16bit(Shortcut^T(dy));  dx = 16bit(16bit([x > 0] . Conv1^T(dh)) + 0.25 spread2x2(dxp))
+ * -- the rounding points of the four launches it replaces (the ConvMeanPool data gradient in its sub-pixel form, rcgan_conv2d_rf backward,
+ * the 1x1 data gradient, rcgan_meanpool2_bwd accumulating), and their fp32 summation orders at the training step's shapes, so dh and dx have
+ * their bits there.  dh (read by Conv1's filter gradient) and dx are written, dx is not accumulated into; dxp never reaches memory.  It
+ * reads two more copies in dblock2_frag (Conv2's summed data-gradient filters, the shortcut's rotated rows), items of the same fragment
+ * launch behind the forward's two, whose bytes are unchanged.  Refuses what rcgan_dblock2_ok refuses. */
 int rcgan_dblock2_ok(const rcgan_conv_desc* d, const void* conv1_frag, const void* dblock2_frag);
 size_t rcgan_dblock2_fragment_bytes(void);
 int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
@@ -544,6 +552,8 @@ int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_pre
                                     const void* shortcut_prepared, void* dblock2_frag);
 int rcgan_dblock2_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* conv1_frag, const void* dblock2_frag,
                       const float* bias1, const float* bias2, const float* bias_shortcut, void* h, void* xp, void* y);
+int rcgan_dblock2_bwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* dy, const void* h, const void* x, const void* conv1_frag,
+                      const void* dblock2_frag, void* dh, void* dx);
 /* Fused projection head: pooled features -> psi (D.Output, SN linear d -> 1), label embeddings E = table @ W_e / sigma_e + b_e
  * (embedding.py:29-51 + D.Embedding_y, gan_resnet.py:414-421), logits psi + <feat, E[l]> (:588, :654-660), loss terms and ALL
  * gradients in one launch.  Rows [0, rows_a) form part a, rows [rows_a, n) part b (real | fake of the critic step, :604-606);

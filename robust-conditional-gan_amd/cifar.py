@@ -781,7 +781,7 @@ class CifarRCGAN:
                 d = L.ConvDesc(1, 16, 16, DIM_D, DIM_D, 3, 3, 1, self.ctx.act_dtype, L.CONV_IN_RELU)
                 if self.ctx.lib.rcgan_conv_rf_ok(C.byref(d)):
                     rf.append((sn("D.Block.2.Conv1"), d))
-                    # ... and the two more copies the 16x16 down block's fused forward reads (ops.d_block2), items of the same launch
+                    # ... and the copies the 16x16 down block's fused forward and data gradient read (ops.d_block2), items of the same launch
                     if O.FUSED_DBLOCK2 and fused_pool_d(self.ctx, GEN_BS_MULTIPLE * self.B):
                         db2 = (sn("D.Block.2.Conv2"), sn("D.Block.2.Shortcut"))
         if (trunk or rf) and O.FRAG_IN_PREPARE:

@@ -347,7 +347,7 @@ int rcgan_dblock2_ok(const rcgan_conv_desc* d, const void* conv1_frag, const voi
   return dblock2_takes(d) && conv1_frag && dblock2_frag ? 1 : 0;
 }
 
-size_t rcgan_dblock2_fragment_bytes(void) { return (size_t)(DB2_FRAG_CONV2 + DB2_FRAG_SHORT) * sizeof(bf16_t); }
+size_t rcgan_dblock2_fragment_bytes(void) { return (size_t)DB2_FRAG_ELEMS * sizeof(bf16_t); }      // the forward's copies, then the data gradient's
 
 // h [n][16][16][128], xp [n][8][8][128] and y [n][8][8][128] are written: everything the block's (unfused) backward pass reads.
 int rcgan_dblock2_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* conv1_frag, const void* dblock2_frag,

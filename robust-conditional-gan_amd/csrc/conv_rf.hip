@@ -302,7 +302,8 @@ int rcgan_fragments_prepare(rcgan_ctx* ctx, const void* const* trunk_prepared, v
   return rcgan_fragments_prepare_dblock2(ctx, trunk_prepared, trunk_frag, n, descs, prepared, frags, nullptr, nullptr, nullptr);
 }
 
-// ... and, in the same launch, the two copies the 16x16 down block's fused forward reads (conv_dblock2.hip; rcgan_dblock2_fragment_bytes):
+// ... and, in the same launch, the copies the 16x16 down block's fused forward and data gradient read (conv_dblock2.hip, conv_dblock2_bwd.hip;
+// rcgan_dblock2_fragment_bytes; two items each):
 // conv2_prepared = D.Block.2.Conv2's prepared filter under RCGAN_CONV_OUT_MEANPOOL2 (its summed gather-layout rows are re-laid),
 // shortcut_prepared = the 1x1 shortcut's.  All three NULL: rcgan_fragments_prepare.
 int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
@@ -312,12 +313,18 @@ int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_pre
   RC_REQUIRE(ctx, n >= 0 && n <= 12 && (n == 0 || (descs && prepared && frags)) && (!trunk_prepared || trunk_frag), "bad arguments");
   RC_REQUIRE(ctx, (conv2_prepared != nullptr) == (dblock2_frag != nullptr) && (shortcut_prepared != nullptr) == (dblock2_frag != nullptr),
              "the down block's copies need both prepared filters and a destination");
+  RC_REQUIRE(ctx, (dblock2_frag ? DB2_FRAG_ITEMS : 0) + (trunk_prepared ? 16 : 0) + 2 * n <= (int)(sizeof(FragBatch::it) / sizeof(FragItem)),
+             "more fragment items than one launch holds");
   FragBatch b;
   int m = 0, maxchunks = 0;
   if (dblock2_frag) {
+    // the forward's two copies, then the data gradient's (conv_dblock2_bwd.hip): Conv2's summed phase filters, the shortcut's rotated rows
     const rcgan_conv_desc d2 = {1, 16, 16, 128, 128, 3, 3, 1, RCGAN_H16, RCGAN_CONV_OUT_MEANPOOL2};
-    dblock2_frag_items((const bf16_t*)conv2_prepared + mfma_prepared_sum_fwd(&d2), (const bf16_t*)shortcut_prepared, (bf16_t*)dblock2_frag, b.it);
-    m = 2;
+    const rcgan_conv_desc ds = {1, 8, 8, 128, 128, 1, 1, 1, RCGAN_H16, 0};
+    dblock2_frag_items((const bf16_t*)conv2_prepared + mfma_prepared_sum_fwd(&d2), (const bf16_t*)shortcut_prepared,
+                       (const bf16_t*)conv2_prepared + mfma_prepared_sum_bwd(&d2), (const bf16_t*)shortcut_prepared + mfma_prepared_rot(&ds),
+                       (bf16_t*)dblock2_frag, b.it);
+    m = DB2_FRAG_ITEMS;
     maxchunks = b.it[0].chunks;
   }
   if (trunk_prepared) {

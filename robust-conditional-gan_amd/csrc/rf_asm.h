@@ -52,9 +52,19 @@ struct FragItem { const bf16_t* src; bf16_t* dst; int K, ctn, ss, nsl, chunks; }
 
 // The down block's fused forward (conv_dblock2.hip) reads two more copies, [Conv2 summed filters: 4 blocks of 32 rows][64 K-steps][2 tiles]
 // followed by [Shortcut: 4 blocks][4 K-steps][2 tiles]: its fragment items, written by the fragment launch of conv_rf.hip.
+// Its fused data gradient (conv_dblock2_bwd.hip) reads two more behind them: [Conv2's summed data-gradient filters, phase layout
+// [4 phases][128][4 * 128] taken as 512 rows: 16 blocks of 32 rows (phase, channel block)][16 K-steps][2 tiles] and [Shortcut, rotated rows:
+// 4 blocks][4 K-steps][2 tiles].
 constexpr long DB2_FRAG_CONV2 = 16L * 128 * 128;      // elements of the gather layout [128][16 * 128]
 constexpr long DB2_FRAG_SHORT = 128L * 128;
-inline void dblock2_frag_items(const bf16_t* conv2_sum_fwd, const bf16_t* shortcut_fwd, bf16_t* frag, FragItem* it) {
+constexpr long DB2_FRAG_CONV2_BWD = DB2_FRAG_CONV2 + DB2_FRAG_SHORT;          // element offsets of the data gradient's copies
+constexpr long DB2_FRAG_SHORT_BWD = DB2_FRAG_CONV2_BWD + DB2_FRAG_CONV2;
+constexpr long DB2_FRAG_ELEMS = DB2_FRAG_SHORT_BWD + DB2_FRAG_SHORT;
+constexpr int DB2_FRAG_ITEMS = 4;
+inline void dblock2_frag_items(const bf16_t* conv2_sum_fwd, const bf16_t* shortcut_fwd, const bf16_t* conv2_sum_bwd, const bf16_t* shortcut_rot,
+                               bf16_t* frag, FragItem* it) {
   it[0] = FragItem{conv2_sum_fwd, frag, 2048, 2, 64, 1, (int)(DB2_FRAG_CONV2 / 8)};
   it[1] = FragItem{shortcut_fwd, frag + DB2_FRAG_CONV2, 128, 2, 4, 1, (int)(DB2_FRAG_SHORT / 8)};
+  it[2] = FragItem{conv2_sum_bwd, frag + DB2_FRAG_CONV2_BWD, 512, 2, 16, 1, (int)(DB2_FRAG_CONV2 / 8)};
+  it[3] = FragItem{shortcut_rot, frag + DB2_FRAG_SHORT_BWD, 128, 2, 4, 1, (int)(DB2_FRAG_SHORT / 8)};
 }

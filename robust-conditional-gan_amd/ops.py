@@ -207,8 +207,8 @@ def fragments_batch(ctx, trunk, rf, dblock2=None):
     """ONE launch writes every fragment-major filter copy of a step (rcgan_fragments_prepare): trunk = the 8x8 stage's eight Weights in
     forward order (or None) -> returns its fragment buffer (ops.d_trunk(frag=...)); rf = [(Weight, desc)] of the layers the
     register-filter kernel takes -> each Weight gets .rf_frag.  All filters must be prepared already (prepare_batch).
-    dblock2 = (Weight Conv2, Weight Shortcut) of the 16x16 down block: the same launch also writes the two copies its fused forward
-    reads (ops.d_block2) -> returns (trunk buffer, down-block buffer)."""
+    dblock2 = (Weight Conv2, Weight Shortcut) of the 16x16 down block: the same launch also writes the copies its fused forward and
+    its fused data gradient read, two each (ops.d_block2) -> returns (trunk buffer, down-block buffer)."""
     tp = tf = None
     if trunk:
         tdesc = L.ConvDesc(1, 8, 8, 128, 128, 3, 3, 1, ctx.act_dtype, L.CONV_IN_RELU)
@@ -556,23 +556,68 @@ def d_block2_ok(ctx, x, w1, frag):
     return bool(ctx.lib.rcgan_dblock2_ok(C.byref(d), _p(w1.rf_frag), _p(frag)))
 
 
+def d_block2_bwd(ctx, d, dy, h, x, w1, frag):
+    """The block's data gradient as ONE launch (rcgan_dblock2_bwd, conv_dblock2_bwd.hip) -> (dh, dx): dh = [h > 0] (Conv2 + pool)^T(dy),
+    dx = [x > 0] Conv1^T(dh) + the pool's adjoint of Shortcut^T(dy), rounded where the four backward launches round."""
+    dh = ctx.empty(h.shape, h.dtype)
+    dx = ctx.empty(x.shape, x.dtype)
+    ctx.check(ctx.lib.rcgan_dblock2_bwd(ctx.h, C.byref(d), _p(dy), _p(h), _p(x), _p(w1.rf_frag), _p(frag), _p(dh), _p(dx)))
+    return dh, dx
+
+
 def d_block2(ctx, x, ws, bs, w1, b1, w2, b2, frag, _saved=None):
     """D.Block.2 of the CIFAR discriminator (gan_resnet.py:275-328, resample='down'), forward, as ONE launch (rcgan_dblock2_fwd):
     y = Shortcut(meanpool2(x)) + ConvMeanPool(relu(Conv1(relu(x)))) with the 16-bit rounding points of the four launches it replaces.
-    The tape gets exactly the four entries those launches record (meanpool2, conv2d, conv2d, conv2d_meanpool, each told its output
-    exists already), so the backward pass is theirs, unchanged."""
+    The four ops those launches belong to (meanpool2, conv2d, conv2d, conv2d_meanpool) are each told their output exists already and
+    record their backward entries as usual.  Under FUSED_DBLOCK2_BWD the tape gets ONE entry in their place: the four data gradients as
+    one launch (d_block2_bwd), then the three deferred filter gradients queued with the descriptors, operands and bias targets and in
+    the order the four entries queue them.  Where that does not apply when the entry runs -- x has a gradient already, or needs none,
+    filter gradients are not grouped -- the entry runs the four, last to first: the same result as without the switch."""
     n = x.shape[0]
     d = L.ConvDesc(n, 16, 16, 128, 128, 3, 3, 1, x.dtype, L.CONV_IN_RELU)
     h = ctx.empty((n, 16, 16, 128), x.dtype)
     xp = ctx.empty((n, 8, 8, 128), x.dtype)
     y = ctx.empty((n, 8, 8, 128), x.dtype)
     ctx.check(ctx.lib.rcgan_dblock2_fwd(ctx.h, C.byref(d), _p(x), _p(w1.rf_frag), _p(frag), _p(b1), _p(b2), _p(bs), _p(h), _p(xp), _p(y)))
+    mark = len(ctx.tape)
     xp = meanpool2(ctx, x, _done=xp)
     t = conv2d(ctx, xp, ws, bs, 1, _done=y)
     h = conv2d(ctx, x, w1, b1, 3, in_relu=True, _done=h)
     if _saved is not None:
         _saved += [h, xp]           # what the backward entries hold on to, for whoever wants to look (the tests)
-    return conv2d_meanpool(ctx, h, w2, b2, in_relu=True, accumulate_into=t, _done=True)
+    out = conv2d_meanpool(ctx, h, w2, b2, in_relu=True, accumulate_into=t, _done=True)
+    four = ctx.tape[mark:]
+    if FUSED_DBLOCK2_BWD and len(four) == 4:
+        del ctx.tape[mark:]
+        d2 = L.ConvDesc(n, 16, 16, 128, 128, 3, 3, 1, x.dtype, L.CONV_OUT_MEANPOOL2 | L.CONV_IN_RELU)
+        ds = L.ConvDesc(n, 8, 8, 128, 128, 1, 1, 1, x.dtype, 0)
+        layers = ((d2, h, w2, b2), (d, x, w1, b1), (ds, xp, ws, bs))      # (descriptor, operand, Weight, bias) in the four entries' order
+        wreq = [w.req for _, _, w, _ in layers]
+
+        def bw():
+            dy = out.grad
+            if dy is None:
+                return
+            fused = (x.req and x.grad is None and ctx.group_wgrads and h.grad is None and xp.grad is None
+                     and not (ctx.overlap and wreq[1])                          # (Conv1's filter gradient would fork to the side stream)
+                     and all(wr or not b.req for wr, (_, _, _, b) in zip(wreq, layers))
+                     and (not wreq[0] or ctx.lib.rcgan_conv_wgrad_pool_ok(C.byref(d2))))
+            if not fused:
+                for fn in reversed(four):
+                    fn()
+                return
+            dh, dx = d_block2_bwd(ctx, d, dy, h, x, w1, frag)
+            for wr, (desc, operand, w, b), g in zip(wreq, layers, (dy, dh, dy)):
+                if wr:
+                    ctx.defer_wgrad(desc, operand, g, w.grad_target(), b.grad if b.req else None)
+            h.grad = dh
+            x.grad = dx
+        ctx.record(bw)
+    return out
+
+
+# ... and its data gradient as one launch in place of the four backward entries' (conv_dblock2_bwd.hip).  Read once; 0: the four entries.
+FUSED_DBLOCK2_BWD = os.environ.get("RCGAN_FUSED_DBLOCK2_BWD", "1") != "0"
 
 
 def d_trunk_ok(ctx, x):

@@ -3,6 +3,9 @@
 register-filter Conv1, Conv2 + pool as one 4x4 stride-2 convolution), in one process, HIP events on the launch stream.  After a warm-up
 the two routes alternate in trains of about 0.3 s, five repetitions each; the bar is mean(four) - mean(fused) > 3 x the larger of the
 two routes' ranges (slowest minus fastest train).  STAMPS=1: the fused kernel's per-workgroup s_memtime segments.
+Then the same for the data gradient: rcgan_dblock2_bwd vs the four backward launches (Conv2 + pool's data gradient in its sub-pixel form,
+the register-filter Conv1 data gradient, the 1x1 shortcut's, the pool's adjoint accumulated into dx); its bar is mean(four) - mean(fused) >
+the two routes' ranges added together.
 usage: python scripts/bench_dblock2.py [n] [--json FILE]"""
 import ctypes as C
 import json
@@ -54,6 +57,21 @@ def main():
         ctx.check(lib.rcgan_conv2d_rf(h, C.byref(d1), 0, P(x.ptr), P(frag1), P(bias["1"].ptr), None, None, P(hh.ptr)))
         ctx.check(lib.rcgan_conv2d_fwd(h, C.byref(d2), P(hh.ptr), P(prep["2"]), P(bias["2"].ptr), P(y.ptr)))
 
+    # ---- the data gradient: dy, and the forward's h and x as masks ----
+    dy, dh, dx, dxp = ctx.empty((n, 8, 8, 128)), ctx.empty((n, 16, 16, 128)), ctx.empty((n, 16, 16, 128)), ctx.empty((n, 8, 8, 128))
+    ctx.check(lib.rcgan_rng_fill(h, dy.size, dy.dtype, 1, 0.0, 1.0, 29, None, P(dy.ptr)))
+    d2b = L.ConvDesc(n, 16, 16, 128, 128, 3, 3, 1, L.BF16, L.CONV_IN_RELU | L.CONV_OUT_MEANPOOL2)
+    ws = C.c_void_p(ctx.ws_ptr)
+
+    def fused_bwd():
+        ctx.check(lib.rcgan_dblock2_bwd(h, C.byref(d1), P(dy.ptr), P(hh.ptr), P(x.ptr), P(frag1), P(fragb), P(dh.ptr), P(dx.ptr)))
+
+    def four_bwd():
+        ctx.check(lib.rcgan_conv2d_bwd_data(h, C.byref(d2b), P(dy.ptr), P(prep["2"]), P(hh.ptr), P(dh.ptr), ws, ctx.ws_bytes))
+        ctx.check(lib.rcgan_conv2d_rf(h, C.byref(d1), 1, P(dh.ptr), P(frag1), None, P(x.ptr), None, P(dx.ptr)))
+        ctx.check(lib.rcgan_conv2d_bwd_data(h, C.byref(ds), P(dy.ptr), P(prep["s"]), None, P(dxp.ptr), ws, ctx.ws_bytes))
+        ctx.check(lib.rcgan_meanpool2_bwd(h, n, 16, 16, 128, L.BF16, P(dxp.ptr), P(dx.ptr), 1))
+
     result = {"n": n}
     if os.environ.get("STAMPS"):
         import torch
@@ -72,6 +90,22 @@ def main():
         for k, v in seg.items():
             print("  %-22s %6.2f" % (k, v.mean()))
         result["stamps_us"] = {k: round(float(v.mean()), 3) for k, v in seg.items()}
+        fused()                                     # (h for the masks)
+        st.zero_()
+        fused_bwd(); fused_bwd()
+        ctx.check(lib.rcgan_debug_stamps(h, P(st.data_ptr())))
+        fused_bwd()
+        ctx.sync()
+        ctx.check(lib.rcgan_debug_stamps(h, None))
+        t = st.cpu().numpy().reshape(2 * n, 16).astype(np.float64) / 2270.0
+        seg = {"dy and h wait": t[:, 2] - t[:, 0], "shortcut": t[:, 3] - t[:, 2], "stage 1: four classes": t[:, 7] - t[:, 3],
+               "filters of stage 2, barrier": t[:, 8] - t[:, 7],
+               "stage 2 K loop": (t[:, 9] - t[:, 8]) + (t[:, 11] - t[:, 10]),
+               "exchange and epilogue": (t[:, 10] - t[:, 9]) + (t[:, 12] - t[:, 11]), "total": t[:, 12] - t[:, 0]}
+        print("data gradient, per-workgroup segments, us (mean over %d workgroups):" % (2 * n))
+        for k, v in seg.items():
+            print("  %-28s %6.2f" % (k, v.mean()))
+        result["bwd_stamps_us"] = {k: round(float(v.mean()), 3) for k, v in seg.items()}
 
     def train(fn, reps):
         ctx.event_record(0)
@@ -96,6 +130,24 @@ def main():
     noise = float(max(max(v) - min(v) for v in us.values()))
     result.update(gain_us=round(gain, 3), largest_range_us=round(noise, 3), bar_met=bool(gain > 3 * noise))
     print("four - fused = %.2f us; 3 x largest range = %.2f us: bar %s" % (gain, 3 * noise, "met" if gain > 3 * noise else "NOT met"))
+    # ---- the data gradient, same method ----
+    fused()
+    for fn in (fused_bwd, four_bwd):
+        for _ in range(20):
+            fn()
+    reps = {fn: max(50, int(0.3e6 / train(fn, 200))) for fn in (fused_bwd, four_bwd)}
+    us = {fused_bwd: [], four_bwd: []}
+    for _ in range(5):
+        for fn in (fused_bwd, four_bwd):
+            us[fn].append(train(fn, reps[fn]))
+    for name, fn in (("fused bwd", fused_bwd), ("four bwd launches", four_bwd)):
+        v = us[fn]
+        print("n=%d %-18s mean %7.2f us  range %.2f  (%s)" % (n, name, np.mean(v), max(v) - min(v), " ".join("%.2f" % t for t in v)))
+        result[name.replace(" ", "_") + "_us"] = [round(t, 3) for t in v]
+    gain = float(np.mean(us[four_bwd]) - np.mean(us[fused_bwd]))
+    noise = float(sum(max(v) - min(v) for v in us.values()))
+    result.update(bwd_gain_us=round(gain, 3), bwd_ranges_added_us=round(noise, 3), bwd_bar_met=bool(gain > noise))
+    print("four bwd - fused bwd = %.2f us; the two ranges added = %.2f us: bar %s" % (gain, noise, "met" if gain > noise else "NOT met"))
     if out_json:
         with open(out_json, "w") as f:
             json.dump(result, f, indent=1)
