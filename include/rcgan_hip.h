@@ -694,7 +694,7 @@ int rcgan_dropout_bwd(rcgan_ctx* ctx, size_t count, int dtype, float keep_prob, 
  *   CUTOUT       oy = min(floor(u5 (h + 1)), h), ox likewise from u6 and w
  *                rows max(oy - h/4, 0) .. min(oy + h/4 - 1, h - 1) x columns max(ox - w/4, 0) .. min(ox + w/4 - 1, w - 1) are set to 0
  *                (a window of h/2 x w/2 pixels, clipped at the border)
- *   u7 is reserved and ignored.
+ *   u7 is reserved and ignored (the gates of the adaptive probability live in a buffer of their own, gate_u: see below).
  * y_pool (may be NULL): [n, h/2, w/2, 3], the 2x2 mean of the STORED y -- the bits rcgan_meanpool2_fwd gives on y -- out of the
  * same launch (D.Block.1's shortcut reads the pooled critic input, gan_resnet.py:346).
  * Backward: dx (=|+=) A_u^T dy.  The map is affine in x, so the adjoint needs u only: dy is masked by the cutout window, shifted by
@@ -710,6 +710,35 @@ int rcgan_diffaugment_fwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int po
                           void* y_pool);
 int rcgan_diffaugment_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* dy, const float* u, void* dx,
                           int accumulate);
+
+/* ---- adaptive augmentation probability on top of the above (csrc/augment.hip; Karras et al., "Training Generative Adversarial
+ * Networks with Limited Data", NeurIPS 2020) -------------------------------------------------------------------------------------
+ * Every transform of `policy` is applied to a sample with probability p, and p follows r = E[sign D(real)] towards a target.
+ * u7 stays reserved: the gates live in a buffer of their own, gate_u[n][4], fp32 uniforms in [0, 1) drawn by the caller; column 0
+ * gates COLOR, 1 TRANSLATION, 2 CUTOUT, column 3 is reserved and ignored.
+ *   rcgan_diffaugment_gated_fwd   sample i is transformed exactly as rcgan_diffaugment_fwd transforms it under
+ *       policy_i = policy & sum_t (gate_u[i][t] < *p_dev ? bit_t : 0)        (strict <, in fp32: p = 1 applies everything,
+ *       p = 0 nothing, a NaN p nothing), y and y_pool (may be NULL) get the same bits, and policy_i is written to sample_policy[i]
+ *       (DEVICE int32[n]).  p_dev is a DEVICE float*, read by the KERNEL: a captured launch sees the value of the moment it runs.
+ *   rcgan_diffaugment_sampled_bwd the adjoint under the policies the forward recorded: sample i gets the bits of
+ *       rcgan_diffaugment_bwd under sample_policy[i] (only its three RCGAN_AUG_* bits are looked at).  It takes neither gate_u nor
+ *       p, so a change of p between a forward and its backward cannot make the two disagree.
+ *   rcgan_ada_update              the controller, one single-workgroup launch.  logits is fp32 [n][ld]; the score of row i is
+ *       s_i = logits[i * ld + (labels ? labels[i] : 0)]; a row whose label is outside [0, ld) counts as ZERO (nothing is read for
+ *       it), though it still counts as an image.  sign(s) = (s > 0) - (s < 0): +-0 and NaN count 0, +-inf count +-1.
+ *       ada_state: DEVICE float[8] = {p, sign_sum, image_count, steps, r_last, updates, 0, 0}.  A call performs
+ *       sign_sum += sum_i sign(s_i), image_count += n, steps += 1, and when steps == interval then, in this order, all in fp32:
+ *       r_last = sign_sum / image_count;  p = clamp(p + sign(r_last - target) * image_count / images, 0, 1);  updates += 1;
+ *       sign_sum = image_count = steps = 0.  (The sum of signs is a sum of small integers: any reduction order is exact.)
+ * Besides the conditions of rcgan_diffaugment_fwd: gate_u, p_dev, sample_policy non-NULL and 4-byte aligned; for the update
+ * n >= 1, ld >= 1, interval >= 1, images > 0, logits / ada_state non-NULL and 4-byte aligned (labels 4-byte aligned).  Anything
+ * else is RCGAN_EINVALID_ARG and launches nothing. */
+int rcgan_diffaugment_gated_fwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* x, const float* u,
+                                const float* gate_u, const float* p_dev, void* y, void* y_pool, int32_t* sample_policy);
+int rcgan_diffaugment_sampled_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, const void* dy, const float* u,
+                                  const int32_t* sample_policy, void* dx, int accumulate);
+int rcgan_ada_update(rcgan_ctx* ctx, int n, const float* logits, int ld, const int32_t* labels, float* ada_state, float target,
+                     float images, int interval);
 
 /* ---- per-class moments of a feature stream (csrc/moments.hip; the Frechet distance of frechet.py) ------------------------------
  * state (caller-owned, zeroed once by the caller, rcgan_class_moments_bytes(d, n_classes) bytes, 8-byte aligned), all fp64:

@@ -235,6 +235,9 @@ SIGNATURES = {
     "rcgan_shortcut_a_bwd": (I, [P, I, I, I, I, I, P, P, I]),
     "rcgan_diffaugment_fwd": (I, [P, I, I, I, I, I, P, P, P, P]),
     "rcgan_diffaugment_bwd": (I, [P, I, I, I, I, I, P, P, P, I]),
+    "rcgan_diffaugment_gated_fwd": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P]),
+    "rcgan_diffaugment_sampled_bwd": (I, [P, I, I, I, I, P, P, P, P, I]),
+    "rcgan_ada_update": (I, [P, I, P, I, P, P, F, F, I]),
     "rcgan_class_moments_bytes": (SZ, [I, I]),
     "rcgan_class_moments_accum": (I, [P, I, I, I, P, P, P]),
     "rcgan_knn_radius": (I, [P, I, I, I, I, P, P, P]),

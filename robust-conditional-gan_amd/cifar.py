@@ -160,6 +160,31 @@ def parse_diffaugment(policy):
     return bits
 
 
+def check_ada(ada_target, ada_images, ada_interval, ada_p_init, diffaugment, world_size=1):
+    """The adaptive-augmentation arguments of CifarRCGAN / --ada_*: (Karras et al., NeurIPS 2020; DESIGN.md 3, "Adaptive augmentation
+    probability").  ada_target = 0 is off; on, it is the value of r = E[sign D(real)] in (-1, 1) that p is steered to.  ada_images:
+    images the critic must see for p to move from 0 to 1; ada_interval: critic steps per adjustment; ada_p_init in [0, 1].
+    The paper's defaults (0.6, 500 k images, 4 minibatches) are the defaults here and have NOT been tuned on CIFAR.
+    -> (target, images, interval, p_init), target 0.0 when off.  Raises ValueError; needs no GPU."""
+    target, images, p_init = float(ada_target), float(ada_images), float(ada_p_init)
+    if not (-1.0 < target < 1.0):          # (also refuses NaN)
+        raise ValueError("ada_target must lie in (-1, 1) (0 = off), got %r" % (ada_target,))
+    if not (images > 0.0 and np.isfinite(images)):
+        raise ValueError("ada_images must be positive, got %r" % (ada_images,))
+    if int(ada_interval) != ada_interval or int(ada_interval) < 1:
+        raise ValueError("ada_interval must be an integer >= 1, got %r" % (ada_interval,))
+    if not (0.0 <= p_init <= 1.0):
+        raise ValueError("ada_p_init must lie in [0, 1], got %r" % (ada_p_init,))
+    if target != 0.0:
+        if not parse_diffaugment(diffaugment):
+            raise ValueError("ada_target = %r needs a non-empty diffaugment policy: the probability gates its transforms" % (ada_target,))
+        if world_size > 1:
+            raise ValueError("ada_target = %r with world_size = %d: every rank would steer p by the r = E[sign D(real)] of its own "
+                             "shard, so the ranks would disagree on p; a reduction of r over the ranks has not been built because "
+                             "there is no multi-GPU machine to test it on" % (ada_target, world_size))
+    return target, images, int(ada_interval), p_init
+
+
 def confusion_logits_initial(confuse_init, confuse_init_diag, rs, n_classes=VOCAB_SIZE):
     """gan_resnet.py:499-520 with VOCAB_SIZE = n_classes (the reference's special case of 10 classes kept for K = 10 only)."""
     K = n_classes
@@ -437,9 +462,14 @@ class CifarRCGAN:
                  device=0, use_graphs=True, device_rng=True, arena_bytes=None, world_size=1, rank=0,
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
                  grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE,
-                 diffaugment=""):
+                 diffaugment="", ada_target=0.0, ada_images=500000, ada_interval=4, ada_p_init=0.0):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # the probability of every DiffAugment transform steered by r = E[sign D(real)] ("Adaptive augmentation
+        # probability"); target 0 = off.  Checked before any context exists.
+        self.ada_target, self.ada_images, self.ada_interval, self.ada_p_init = check_ada(
+            ada_target, ada_images, ada_interval, ada_p_init, diffaugment, world_size)
+        self.ada = self.ada_target != 0.0
         # DiffAugment of every image the critic sees ("Differentiable augmentation"): policy bits, 0 = off.  Checked
         # before any context exists.
         self.aug = parse_diffaugment(diffaugment)
@@ -562,9 +592,14 @@ class CifarRCGAN:
         # the augmentation's uniforms, one row of eight per image the critic sees: step inputs where the host draws (device_rng=False),
         # buffers the step's own launch fills otherwise (_draw_aug); absent with the option off
         aug_shapes = {"aug_u": (2 * B, 8), "aug_u_G": (GEN_BS_MULTIPLE * B, 8)} if self.aug else {}
+        # ... and with the adaptive probability one row of four gates per image (rcgan_diffaugment_gated_fwd)
+        gate_shapes = {"aug_gate": (2 * B, 4), "aug_gate_G": (GEN_BS_MULTIPLE * B, 4)} if self.ada else {}
         if self.aug and not device_rng:
             self.feed_layout["d"].append(("aug_u", aug_shapes["aug_u"], f32))
             self.feed_layout["g"].append(("aug_u_G", aug_shapes["aug_u_G"], f32))
+            if self.ada:
+                self.feed_layout["d"].append(("aug_gate", gate_shapes["aug_gate"], f32))
+                self.feed_layout["g"].append(("aug_gate_G", gate_shapes["aug_gate_G"], f32))
         self.feed, self.inp = {}, {}
         self._feed_ring = {}
         for key, fields in self.feed_layout.items():
@@ -590,8 +625,17 @@ class CifarRCGAN:
         self.inp.update(noise=P((B, OUTPUT_DIM), f32), z=P((B, Z_DIM), act), z_G=P((2 * B, Z_DIM), act),
                         z_all=P((N_CRITIC * B, Z_DIM), act),
                         arange=P((self.K,), i32), C_const=P((self.K, self.K), f32))
-        if self.aug and device_rng:
+        self._aug_draw = {}
+        if self.aug and device_rng and not self.ada:
             self.inp.update({name: P(shp, f32) for name, shp in aug_shapes.items()})
+        elif self.aug and device_rng:
+            # ONE buffer [n 12] per augmentation call, filled by ONE launch: u is its first n 8 floats, the gates its last n 4
+            for name, gname in (("aug_u", "aug_gate"), ("aug_u_G", "aug_gate_G")):
+                n = aug_shapes[name][0]
+                buf = P((n * 12,), f32)
+                self._aug_draw[name] = buf
+                self.inp[name] = DT(buf.ptr, (n, 8), f32, buf.base, name)
+                self.inp[gname] = DT(buf.ptr + 4 * n * 8, (n, 4), f32, buf.base, gname)
         ctx.view(self.inp["arange"]).copy_(torch.arange(self.K, dtype=torch.int32))
         ctx.view(self.inp["C_const"]).copy_(torch.from_numpy(C_ALPHA(alpha, self.K).astype(np.float32)))
         # the critic steps' generator forwards evaluated as one batch (prepare_critic_fakes): fakes of all N_CRITIC steps,
@@ -606,6 +650,11 @@ class CifarRCGAN:
         # the augmentation draws from a stream of its own: noise and z of a run do not move when the option is turned on.  Like
         # rng_state it is not part of state_dict.
         self.aug_rng_state = torch.zeros(2, dtype=torch.int64, device=ctx.device) if self.aug else None
+        # the controller of the augmentation probability lives on the device, inside the captured steps (rcgan_ada_update):
+        # {p, sign_sum, image_count, steps, r_last, updates, 0, 0}.  Part of state_dict ("_ada_state").
+        self.ada_state = (torch.tensor([self.ada_p_init] + [0.0] * 7, dtype=torch.float32, device=ctx.device) if self.ada else None)
+        # the logits rcgan_ada_update reads after the fused head (which otherwise keeps them on chip): head_logits if set, else this
+        self.ada_logits = P((2 * B, self.K), f32, fill=0.0) if (self.ada and self.fused_head) else None
         # (round 6) The critic steps' generator forwards on a SECOND stream.  The generator does not change during the N_CRITIC critic
         # updates of an iteration (gan_resnet.py:928-947), so step k + 1's Generator() call can run while critic step k does: a critic
         # step is a chain of ~26 small-grid launches that leaves half the chip idle most of the time, the generator forward is the
@@ -715,12 +764,32 @@ class CifarRCGAN:
 
     def _draw_aug(self, u):
         """The uniforms of one augmentation call: drawn here, by a launch of the step, on the device (fresh on every replay of a
-        captured step), or whatever the host has put into the step input."""
+        captured step), or whatever the host has put into the step input.  With the adaptive probability the same launch draws the
+        gates behind them (u and its gates are one buffer)."""
         if self.device_rng:
             ctx = self.ctx
+            if self.ada:
+                u = self._aug_draw[u.name]
             ctx.check(ctx.lib.rcgan_rng_fill(ctx.h, u.size, u.dtype, 0, 0.0, 1.0, self.seed * 1000003 + self.rank + 700001,
                                              C.c_void_p(self.aug_rng_state.data_ptr()), C.c_void_p(u.ptr)))
-        return u
+
+    def _augment(self, x, name, pool=False):
+        """DiffAugment of x from the step input `name` ("aug_u" / "aug_u_G"), every transform with probability p where the
+        adaptive probability is on (p is read on the device when the launch runs)."""
+        inp = self.inp
+        self._draw_aug(inp[name])
+        if not self.ada:
+            return O.diffaugment(self.ctx, x, inp[name], self.aug, pool=pool)
+        return O.diffaugment(self.ctx, x, inp[name], self.aug, pool=pool, gate=inp["aug_gate" + name[len("aug_u"):]], p=self.ada_state)
+
+    def _ada_update(self, logits, ld, labels):
+        """One call of the controller on the real rows' scores of this critic step (no-op with the option off and in forward-only
+        evaluations): one launch, inside the captured step."""
+        ctx = self.ctx
+        if not self.ada or not ctx.recording:
+            return
+        ctx.check(ctx.lib.rcgan_ada_update(ctx.h, self.B, C.c_void_p(logits.ptr), ld, None if labels is None else C.c_void_p(labels.ptr),
+                                           C.c_void_p(self.ada_state.data_ptr()), self.ada_target, self.ada_images, self.ada_interval))
 
     def _sn_entries(self, conv_update, proj_update):
         ents = []
@@ -867,7 +936,7 @@ class CifarRCGAN:
             # out of the same launch (the rider's pool is of the un-augmented images: where the rider runs it still fills its own
             # [2B, 16, 16, 3] buffer, part of its launch and 98 KB of arena at B = 64, which nothing reads).  perm_classifier below
             # keeps `real`.
-            d_in, g.image_pool = O.diffaugment(ctx, x_all, self._draw_aug(inp["aug_u"]), self.aug, pool=True)
+            d_in, g.image_pool = self._augment(x_all, "aug_u", pool=True)
         w = 1.0       # (the gradient scale of 16-bit activations is applied inside the loss kernels: rcgan_set_grad_scale)
         if self.fused_head:
             feat = Discriminator(d_in, None, update_collection=None, _head=False)         # :584
@@ -879,13 +948,17 @@ class CifarRCGAN:
                 parts = [(B, L.LOSS_HINGE_REAL, None, inp["inv_weights"]), (B, L.LOSS_HINGE_FAKE, inp["labels_random"], None)]
             else:                              # biased / rcgan (:585-606): labels_all = [labels ; labels_random | labels_biased]
                 parts = [(B, L.LOSS_HINGE_REAL, lab_r, None), (B, L.LOSS_HINGE_FAKE, lab_f, None)]
-            Discriminator_head(feat, parts, w, self.loss_d, update_collection=None, logits=self.head_logits)
+            head_logits = self.head_logits if self.head_logits is not None else self.ada_logits
+            Discriminator_head(feat, parts, w, self.loss_d, update_collection=None, logits=head_logits)
+            # real rows [0, B) of the [2B, K] logits at the row's given (noisy) label: the only non-zero column of a labelled part
+            self._ada_update(head_logits, self.K, lab_r if self.alg in ("biased", "rcgan") else inp["labels"])
         elif self.alg == "rcgan-u":
             feat_a, wgan_a = Discriminator(d_in, None, update_collection=None)
             feat, wgan = O.rows(ctx, feat_a, 0, B), O.rows(ctx, wgan_a, 0, B)
             feat_f, wgan_f = O.rows(ctx, feat_a, B, 2 * B), O.rows(ctx, wgan_a, B, 2 * B)
             emb = Discriminator_projection(inp["labels"], update_collection=None)
             disc_real = O.proj_logit(ctx, feat, wgan, emb)
+            self._ada_update(disc_real, 1, None)
             E = Discriminator_projection(inp["arange"], update_collection=None)
             disc_fake = O.proj_logit_all(ctx, feat_f, wgan_f, E)                         # :654-660
             y_conf = O.gather_rows(ctx, self.confusion_matrix(), inp["labels_random"], B)   # :682-683
@@ -896,6 +969,7 @@ class CifarRCGAN:
             if self.alg in ("biased", "rcgan"):
                 emb = Discriminator_projection(inp["labels_all"], update_collection=None)    # :585
                 disc_all = O.proj_logit(ctx, feat, wgan, emb)                            # :588
+                self._ada_update(disc_all, 1, None)                                      # (rows 0 .. B: the real ones)
                 O.loss_term(ctx, L.LOSS_HINGE_REAL, O.rows(ctx, disc_all, 0, B), w, self.loss_d)       # :604
                 O.loss_term(ctx, L.LOSS_HINGE_FAKE, O.rows(ctx, disc_all, B, 2 * B), w, self.loss_d)   # :605
             else:   # unbiased (:613-648): every label's projection once, real loss weighted by C^-1 rows
@@ -903,6 +977,7 @@ class CifarRCGAN:
                 feat_r, wgan_r = O.rows(ctx, feat, 0, B), O.rows(ctx, wgan, 0, B)
                 feat_f, wgan_f = O.rows(ctx, feat, B, 2 * B), O.rows(ctx, wgan, B, 2 * B)
                 disc_real_all = O.proj_logit_all(ctx, feat_r, wgan_r, E)                 # [B,10]
+                self._ada_update(disc_real_all, self.K, inp["labels"])
                 O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real_all, w, self.loss_d, wts=inp["inv_weights"])   # :647
                 emb_f = Discriminator_projection(inp["labels_random"], update_collection=None)
                 disc_fake = O.proj_logit(ctx, feat_f, wgan_f, emb_f)
@@ -940,7 +1015,8 @@ class CifarRCGAN:
         fake = Generator(n, inp["labels_random_G"], inp["z_G"])                                      # :719
         lab = inp["labels_random_G"] if self.alg in ("biased", "unbiased") else inp["labels_biased_G"]
         # (augmented between Generator and Discriminator, the adjoint on the tape; perm_classifier below keeps `fake`)
-        d_in = O.diffaugment(ctx, fake, self._draw_aug(inp["aug_u_G"]), self.aug) if self.aug else fake
+        # (... with probability p where that is adaptive: read here, updated by the critic steps only)
+        d_in = self._augment(fake, "aug_u_G") if self.aug else fake
         if self.fused_head:
             feat = Discriminator(d_in, lab, update_collection=NO_OPS, _head=False)                   # :721-730
             if self.alg == "rcgan-u":
@@ -1272,6 +1348,14 @@ class CifarRCGAN:
         s = self.ls_state.cpu().numpy()
         return dict(scale=float(s[0]), good_steps=int(s[1]), skipped_steps=int(s[3]))
 
+    def ada_report(self):
+        """{p, r_last, updates} of the adaptive augmentation probability as it stands on the stream now (synchronises)."""
+        if self.ada_state is None:
+            return dict(p=None, r_last=None, updates=0)
+        self.ctx.sync()
+        s = self.ada_state.cpu().numpy()
+        return dict(p=float(s[0]), r_last=float(s[4]), updates=int(s[5]))
+
     def losses(self):
         ctx = self.ctx
         return float(ctx.download(self.loss_d)[0]), float(ctx.download(self.loss_g)[0])
@@ -1352,6 +1436,9 @@ class CifarRCGAN:
             ([(self.PC.steps_applied(), 0.0, 0.9)] if self.PC is not None else [])
         if self.ls_state is not None:
             out["_loss_scale"] = self.ls_state.cpu().numpy().astype(np.float32)
+        if self.ada_state is not None:
+            self.ctx.sync()
+            out["_ada_state"] = self.ada_state.cpu().numpy().astype(np.float32)
         out.update(adam_power_tensors(opts))
         return out
 
@@ -1385,6 +1472,9 @@ class CifarRCGAN:
         if self.ls_state is not None and "_loss_scale" in sd:
             with torch.cuda.stream(self.ctx.stream):
                 self.ls_state.copy_(torch.from_numpy(np.asarray(sd["_loss_scale"], np.float32).reshape(4)))
+        if self.ada_state is not None and "_ada_state" in sd:
+            with torch.cuda.stream(self.ctx.stream):
+                self.ada_state.copy_(torch.from_numpy(np.asarray(sd["_ada_state"], np.float32).reshape(8)))
         if "_iteration" in sd:
             self.iteration = int(np.asarray(sd["_iteration"]).reshape(-1)[0])
         ctx = self.ctx

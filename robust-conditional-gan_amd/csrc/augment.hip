@@ -9,6 +9,11 @@
 // finished by block_sum256 (butterfly inside a wavefront, the four wavefronts in order): no atomics, the same bits every run.
 // (The flat loops carry "vectorize(disable)": left to itself the loop vectoriser interleaves eight iterations and takes the 16-byte
 // accesses apart into dword ones.)
+//
+// The adaptive probability (Karras et al., NeurIPS 2020) on top: rcgan_diffaugment_gated_fwd / rcgan_diffaugment_sampled_bwd are the
+// same two bodies with the policy as a per-workgroup value -- the launch's policy masked by gate_u[b][t] < *p_dev, p read on the
+// device when the launch runs, the result recorded per sample for the adjoint -- and rcgan_ada_update is the one-workgroup controller
+// that moves p by the sign of E[sign D(real)] - target.
 #include "common.h"
 
 namespace {
@@ -74,12 +79,11 @@ template <typename T> __device__ __forceinline__ float aug_round(float v);
 template <> __device__ __forceinline__ float aug_round<float>(float v) { return v; }
 template <> __device__ __forceinline__ float aug_round<bf16_t>(float v) { return bf16_to_f32(f32_to_bf16(v)); }
 
-// y[b] = A_u(x[b]); y_pool[b] = the 2x2 mean of the STORED y[b], summed as meanpool2_fwd_kernel sums it
+// y[b] = A_u(x[b]); y_pool[b] = the 2x2 mean of the STORED y[b], summed as meanpool2_fwd_kernel sums it.  The body of both forward
+// kernels: `policy` is a per-workgroup value (the launch's, or the sample's own in the gated form).
 template <typename T>
-__global__ __launch_bounds__(AUG_BLOCK) void diffaugment_fwd_kernel(int h, int w, int policy, const T* __restrict__ x,
-                                                                     const float* __restrict__ u, T* __restrict__ y, T* __restrict__ y_pool) {
-  extern __shared__ float4 aug_lds[];
-  __shared__ float red[4];
+__device__ __forceinline__ void diffaugment_fwd_body(float4* aug_lds, float* red, int h, int w, int policy, const T* __restrict__ x,
+                                                     const float* __restrict__ u, T* __restrict__ y, T* __restrict__ y_pool) {
   const int hw = h * w, cnt = hw * 3, tid = threadIdx.x;
   float* A = reinterpret_cast<float*>(aug_lds);      // the sample (after brightness and saturation); later the pooled output
   float* B = A + cnt;                                // the transformed sample as stored (cnt % 48 == 0: 16-byte aligned)
@@ -150,12 +154,39 @@ __global__ __launch_bounds__(AUG_BLOCK) void diffaugment_fwd_kernel(int h, int w
   for (int v = tid; v < cnt / 16; v += AUG_BLOCK) aug_st4(y_pool + 4 * v, aug_lds[v]);
 }
 
-// dx[b] (=|+=) A_u^T dy[b]: mask, shift back, then the adjoints of contrast and saturation (brightness adds a constant: no term)
 template <typename T>
-__global__ __launch_bounds__(AUG_BLOCK) void diffaugment_bwd_kernel(int h, int w, int policy, const T* __restrict__ dy,
-                                                                     const float* __restrict__ u, T* __restrict__ dx, int accumulate) {
+__global__ __launch_bounds__(AUG_BLOCK) void diffaugment_fwd_kernel(int h, int w, int policy, const T* __restrict__ x,
+                                                                     const float* __restrict__ u, T* __restrict__ y, T* __restrict__ y_pool) {
   extern __shared__ float4 aug_lds[];
   __shared__ float red[4];
+  diffaugment_fwd_body<T>(aug_lds, red, h, w, policy, x, u, y, y_pool);
+}
+
+// the gated form: the sample's policy is the launch's, masked by gate_u[b][t] < *p_dev (p read HERE, on the device, when the launch
+// runs), and is recorded for the adjoint.  !(g < p) is false for a NaN p: nothing is applied.
+template <typename T>
+__global__ __launch_bounds__(AUG_BLOCK) void diffaugment_gated_fwd_kernel(int h, int w, int policy, const T* __restrict__ x,
+                                                                           const float* __restrict__ u, const float* __restrict__ gate_u,
+                                                                           const float* __restrict__ p_dev, T* __restrict__ y,
+                                                                           T* __restrict__ y_pool, int* __restrict__ sample_policy) {
+  extern __shared__ float4 aug_lds[];
+  __shared__ float red[4];
+  const float p = *p_dev;
+  const float* g = gate_u + 4 * (size_t)blockIdx.x;
+  int mask = 0;
+  if (g[0] < p) mask |= RCGAN_AUG_COLOR;
+  if (g[1] < p) mask |= RCGAN_AUG_TRANSLATION;
+  if (g[2] < p) mask |= RCGAN_AUG_CUTOUT;
+  const int mine = __builtin_amdgcn_readfirstlane(policy & mask);      // the same in every lane: keep the branches on it scalar
+  if (threadIdx.x == 0) sample_policy[blockIdx.x] = mine;
+  diffaugment_fwd_body<T>(aug_lds, red, h, w, mine, x, u, y, y_pool);
+}
+
+// dx[b] (=|+=) A_u^T dy[b]: mask, shift back, then the adjoints of contrast and saturation (brightness adds a constant: no term).
+// The body of both backward kernels, `policy` per workgroup as above.
+template <typename T>
+__device__ __forceinline__ void diffaugment_bwd_body(float4* aug_lds, float* red, int h, int w, int policy, const T* __restrict__ dy,
+                                                     const float* __restrict__ u, T* __restrict__ dx, int accumulate) {
   const int hw = h * w, cnt = hw * 3, tid = threadIdx.x;
   float* A = reinterpret_cast<float*>(aug_lds);      // dy
   float* B = A + cnt;                                // the gradient at the input's pixels
@@ -206,6 +237,55 @@ __global__ __launch_bounds__(AUG_BLOCK) void diffaugment_bwd_kernel(int h, int w
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(AUG_BLOCK) void diffaugment_bwd_kernel(int h, int w, int policy, const T* __restrict__ dy,
+                                                                     const float* __restrict__ u, T* __restrict__ dx, int accumulate) {
+  extern __shared__ float4 aug_lds[];
+  __shared__ float red[4];
+  diffaugment_bwd_body<T>(aug_lds, red, h, w, policy, dy, u, dx, accumulate);
+}
+
+// the adjoint under the policy the gated forward recorded for the sample
+template <typename T>
+__global__ __launch_bounds__(AUG_BLOCK) void diffaugment_sampled_bwd_kernel(int h, int w, const T* __restrict__ dy, const float* __restrict__ u,
+                                                                             const int* __restrict__ sample_policy, T* __restrict__ dx,
+                                                                             int accumulate) {
+  extern __shared__ float4 aug_lds[];
+  __shared__ float red[4];
+  const int all = RCGAN_AUG_COLOR | RCGAN_AUG_TRANSLATION | RCGAN_AUG_CUTOUT;
+  const int mine = __builtin_amdgcn_readfirstlane(sample_policy[blockIdx.x] & all);
+  diffaugment_bwd_body<T>(aug_lds, red, h, w, mine, dy, u, dx, accumulate);
+}
+
+// The controller of the augmentation probability (the definition is in include/rcgan_hip.h).  One workgroup: a strided loop over the
+// rows, the signs summed by block_sum256 (a sum of small integers: exact in any order), the state written by thread 0.
+__global__ __launch_bounds__(AUG_BLOCK) void ada_update_kernel(int n, const float* __restrict__ logits, int ld, const int* __restrict__ labels,
+                                                                float* __restrict__ st, float target, float images, float interval) {
+  __shared__ float red[4];
+  float part = 0.f;
+  for (int i = threadIdx.x; i < n; i += AUG_BLOCK) {
+    const int c = labels ? labels[i] : 0;
+    if (c < 0 || c >= ld) continue;                      // a label outside the row: the row counts as zero
+    const float s = logits[(size_t)i * ld + c];
+    part += (float)((s > 0.f) - (s < 0.f));
+  }
+  const float sum = block_sum256(part, red);
+  if (threadIdx.x != 0) return;
+  float p = st[0], sign_sum = st[1] + sum, count = st[2] + (float)n, steps = st[3] + 1.f;
+  if (steps == interval) {
+    const float r = sign_sum / count, d = r - target;
+    p += (float)((d > 0.f) - (d < 0.f)) * count / images;
+    p = fminf(fmaxf(p, 0.f), 1.f);
+    st[0] = p;
+    st[4] = r;
+    st[5] += 1.f;
+    sign_sum = count = steps = 0.f;
+  }
+  st[1] = sign_sum;
+  st[2] = count;
+  st[3] = steps;
+}
+
 // the argument checks of both entry points; -> LDS bytes of a launch
 int aug_check(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* a, const void* u, const void* b, const void* pool, size_t* lds) {
   RC_REQUIRE(ctx, dtype == RCGAN_F32 || dtype == RCGAN_H16, "bad dtype %d", dtype);
@@ -252,6 +332,45 @@ int rcgan_diffaugment_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int po
   RC_DISPATCH_DTYPE(ctx, dtype, static bool raised = false; if (int rc = aug_lds_limit(ctx, diffaugment_bwd_kernel<T>, lds, &raised)) return rc;
                     hipLaunchKernelGGL(diffaugment_bwd_kernel<T>, dim3(n), dim3(AUG_BLOCK), lds, ctx->stream, h, w, policy,
                                                    (const T*)dy, u, (T*)dx, accumulate));
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_diffaugment_gated_fwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, int policy, const void* x, const float* u,
+                                const float* gate_u, const float* p_dev, void* y, void* y_pool, int32_t* sample_policy) {
+  size_t lds = 0;
+  if (int rc = aug_check(ctx, n, h, w, dtype, policy, x, u, y, y_pool, &lds)) return rc;
+  RC_REQUIRE(ctx, gate_u && p_dev && sample_policy, "null pointer");
+  RC_REQUIRE(ctx, (((uintptr_t)gate_u | (uintptr_t)p_dev | (uintptr_t)sample_policy) & 3) == 0, "gate_u, p_dev and sample_policy must be 4-byte aligned");
+  RC_DISPATCH_DTYPE(ctx, dtype, static bool raised = false; if (int rc = aug_lds_limit(ctx, diffaugment_gated_fwd_kernel<T>, lds, &raised)) return rc;
+                    hipLaunchKernelGGL(diffaugment_gated_fwd_kernel<T>, dim3(n), dim3(AUG_BLOCK), lds, ctx->stream, h, w, policy,
+                                                   (const T*)x, u, gate_u, p_dev, (T*)y, (T*)y_pool, (int*)sample_policy));
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_diffaugment_sampled_bwd(rcgan_ctx* ctx, int n, int h, int w, int dtype, const void* dy, const float* u,
+                                  const int32_t* sample_policy, void* dx, int accumulate) {
+  size_t lds = 0;
+  if (int rc = aug_check(ctx, n, h, w, dtype, 0, dy, u, dx, nullptr, &lds)) return rc;
+  RC_REQUIRE(ctx, sample_policy, "null pointer");
+  RC_REQUIRE(ctx, ((uintptr_t)sample_policy & 3) == 0, "sample_policy must be 4-byte aligned");
+  RC_DISPATCH_DTYPE(ctx, dtype, static bool raised = false; if (int rc = aug_lds_limit(ctx, diffaugment_sampled_bwd_kernel<T>, lds, &raised)) return rc;
+                    hipLaunchKernelGGL(diffaugment_sampled_bwd_kernel<T>, dim3(n), dim3(AUG_BLOCK), lds, ctx->stream, h, w,
+                                                   (const T*)dy, u, (const int*)sample_policy, (T*)dx, accumulate));
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_ada_update(rcgan_ctx* ctx, int n, const float* logits, int ld, const int32_t* labels, float* ada_state, float target,
+                     float images, int interval) {
+  RC_REQUIRE(ctx, n >= 1 && ld >= 1, "n = %d rows of %d logits: at least one of each", n, ld);
+  RC_REQUIRE(ctx, interval >= 1, "interval %d: at least one call per update", interval);
+  RC_REQUIRE(ctx, images > 0.f, "images %g: the adjustment speed must be positive", (double)images);
+  RC_REQUIRE(ctx, logits && ada_state, "null pointer");
+  RC_REQUIRE(ctx, (((uintptr_t)logits | (uintptr_t)ada_state | (uintptr_t)labels) & 3) == 0, "logits, labels and ada_state must be 4-byte aligned");
+  hipLaunchKernelGGL(ada_update_kernel, dim3(1), dim3(AUG_BLOCK), 0, ctx->stream, n, logits, ld, (const int*)labels, ada_state, target, images,
+                     (float)interval);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }

@@ -1063,11 +1063,16 @@ def dropout(ctx, x, keep_prob, seed, state):
     return y
 
 
-def diffaugment(ctx, x, u, policy, pool=False):
+def diffaugment(ctx, x, u, policy, pool=False, gate=None, p=None):
     """DiffAugment of NHWC images x [n, h, w, 3] (or their flattened rows [n, h*w*3] of square images) under the policy bits
     L.AUG_*: colour jitter, integer translation, cutout, each sample from its row of u [n, 8] (fp32 uniforms in [0, 1), drawn by the
     caller) -- rcgan_diffaugment_fwd, one launch, with its adjoint on the tape when x is tracked.  pool=True: also returns the 2x2
-    mean of the result out of the same launch (the bits of meanpool2 on it; not tracked: for a critic input that needs no gradient)."""
+    mean of the result out of the same launch (the bits of meanpool2 on it; not tracked: for a critic input that needs no gradient).
+    gate [n, 4] (fp32 uniforms) and p (a device fp32 scalar: a DT, a torch tensor or an address) together: every transform of the
+    policy is applied to a sample only where its gate is below p as p stands when the launch RUNS (rcgan_diffaugment_gated_fwd), and
+    the adjoint follows the per-sample policies that launch recorded (rcgan_diffaugment_sampled_bwd)."""
+    if (gate is None) != (p is None):
+        raise ValueError("diffaugment: gate and p come together")
     if len(x.shape) == 4:
         n, h, w, c = x.shape
     elif len(x.shape) == 2:
@@ -1081,6 +1086,20 @@ def diffaugment(ctx, x, u, policy, pool=False):
         raise ValueError("diffaugment: u must be fp32 [%d, 8], got %r" % (n, u.shape))
     y = ctx.empty(x.shape, x.dtype)
     yp = ctx.empty((n, h // 2, w // 2, 3), x.dtype) if pool else None
+    if gate is not None:
+        if tuple(gate.shape) != (n, 4) or gate.dtype != L.F32:
+            raise ValueError("diffaugment: gate must be fp32 [%d, 4], got %r" % (n, gate.shape))
+        pp = C.c_void_p(p.data_ptr() if isinstance(p, torch.Tensor) else p.ptr if isinstance(p, DT) else int(p))
+        sp = DT(ctx.arena.alloc(4 * n), (n,), "i32", ctx.arena.buf)       # in the step's arena, where the backward closure reads it
+        ctx.check(ctx.lib.rcgan_diffaugment_gated_fwd(ctx.h, n, h, w, x.dtype, policy, _p(x), _p(u), _p(gate), pp, _p(y), _p(yp), _p(sp)))
+        if _track(ctx, y, x):
+            def bw():
+                if y.grad is None:
+                    return
+                dx, acc = grad_of(ctx, x)
+                ctx.check(ctx.lib.rcgan_diffaugment_sampled_bwd(ctx.h, n, h, w, x.dtype, _p(y.grad), _p(u), _p(sp), _p(dx), acc))
+            ctx.record(bw)
+        return (y, yp) if pool else y
     ctx.check(ctx.lib.rcgan_diffaugment_fwd(ctx.h, n, h, w, x.dtype, policy, _p(x), _p(u), _p(y), _p(yp)))
     if _track(ctx, y, x):
         def bw():

@@ -68,6 +68,12 @@ def define_flags():
                     "rcgan_amd.train_classifier writes one for any class count); default: the built-in CIFAR-10 network")
     f.DEFINE_string("diffaugment", '', "differentiable augmentation of every image the critic sees: a comma-separated subset of "
                     "color,translation,cutout (empty: off)")
+    f.DEFINE_float("ada_target", 0.0, "with --diffaugment: apply every transform with a probability p steered so that "
+                   "r = E[sign D(real)] meets this target in (-1, 1) (Karras et al. 2020 use 0.6); 0: off, every transform always")
+    f.DEFINE_float("ada_images", 500000, "--ada_target: images the critic must see for p to move from 0 to 1 (the paper's default; "
+                   "not tuned on CIFAR here)")
+    f.DEFINE_integer("ada_interval", 4, "--ada_target: critic steps per adjustment of p")
+    f.DEFINE_float("ada_p_init", 0.0, "--ada_target: initial p in [0, 1]")
     M.define_flags(f)             # the sample-quality metrics' flags
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
@@ -132,8 +138,11 @@ def main(argv=None):
         if asset_classes != N_CLASSES:
             raise ValueError("--label_classifier %s classifies %d classes, this run has %d"
                              % (FLAGS.label_classifier, asset_classes, N_CLASSES))
-    from .cifar import parse_diffaugment
+    from .cifar import check_ada, parse_diffaugment
     parse_diffaugment(FLAGS.diffaugment)          # (a bad name fails here, before anything touches the GPU)
+    # ... and so do the adaptive probability's ranges, --ada_target without --diffaugment, and more than one rank
+    check_ada(FLAGS.ada_target, FLAGS.ada_images, FLAGS.ada_interval, FLAGS.ada_p_init, FLAGS.diffaugment,
+              int(os.environ.get("WORLD_SIZE", "1")))
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
@@ -141,6 +150,7 @@ def main(argv=None):
     C_ALPHA = D.C_ALPHA(ALPHA, N_CLASSES)
     logging.info('dataset = {} ({} classes)'.format(FLAGS.dataset, N_CLASSES))
     logging.info('diffaugment = {}'.format(FLAGS.diffaugment or 'off'))
+    logging.info('ada_target = {}'.format(FLAGS.ada_target or 'off'))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -187,7 +197,8 @@ def main(argv=None):
                    confuse_init=FLAGS.confuse_init, confuse_init_diag=FLAGS.confuse_init_diag,
                    confuse_multiplier=FLAGS.confuse_multiplier, confuse_lr_decay=FLAGS.confuse_lr_decay,
                    device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision,
-                   n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment)
+                   n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment, ada_target=FLAGS.ada_target, ada_images=FLAGS.ada_images,
+                   ada_interval=FLAGS.ada_interval, ada_p_init=FLAGS.ada_p_init)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     clean_train = None                 # (images, clean labels) of the training set: the real side of the sample-quality metrics
@@ -335,6 +346,10 @@ def main(argv=None):
             if dev_disc_costs:
                 plot.plot('dev_cost', mean_over_ranks(np.mean(dev_disc_costs), m.ctx.device))
             logging.info('finished calculating dev cost.')
+            if m.ada:                  # the augmentation probability and the overfitting signal r = E[sign D(real)] that steers it
+                ada = m.ada_report()
+                plot.plot('ada_p', ada["p"])
+                plot.plot('ada_r', ada["r_last"])
         if rank == 0 and SAMPLE_FREQUENCY and iteration % SAMPLE_FREQUENCY == SAMPLE_FREQUENCY - 1:
             samples = m.sample(fixed_labels, fixed_noise)
             samples = ((samples + 1.) * (255. / 2)).astype('int32')             # gan_resnet.py:831
