@@ -16,8 +16,9 @@ import torch
 
 from . import _lib as L
 from . import ops as O
+from . import runtime
 from .ops_cifar import NO_OPS, Conv2D, Linear, cond_batchnorm, embed_y, spectral_normed_weight
-from .runtime import DT, Context, ParamGroup, check_f32_matmul_precision
+from .runtime import DT, Context, ParamGroup, check_f32_matmul_precision, run_rehearsed
 from .variables import Graph, scoped, variable_scope
 
 Z_DIM = 128
@@ -31,6 +32,7 @@ OUTPUT_DIM = 3072
 N_CRITIC = 5
 GEN_BS_MULTIPLE = 2
 ALGORITHMS = ("rcgan", "rcgan-u", "biased", "unbiased")
+GROUP_NAMES = ("Generator", "Discriminator", "confusion")      # of self.groups, in checkpoints ("_opt/<name>/step")
 # The 8x8 discriminator stage -- D.Block.3 .. D.Block.6, eight 3x3 convolutions -- as one launch each way (ops.d_trunk /
 # conv_trunk.hip: a workgroup carries one image through all eight layers, activations in LDS, each wavefront's filters of a whole
 # layer in registers, filters re-laid fragment-major once per step).  Round 3, MI355X, n = 128: 49.6 us forward / 51.8 us data
@@ -1048,34 +1050,18 @@ class CifarRCGAN:
 
     # ---------------------------------------------------------------------------------- stepping
     def _run(self, key, body, ctx=None):
-        ctx = ctx or self.ctx
         if not self.use_graphs:
             body()
             return
-        if key not in self._graphs:
-            body()                      # eager warm-up (module loads, LDS attributes, self test)
-            ctx.sync()
-            ctx.graph_begin()
-            try:
-                body()
-                gid = ctx.graph_end()
-            except L.RcganError as e:
-                ctx.graph_abort()
-                if not (self.dp_active and e.code == L.RCGAN_ERCCL):
-                    raise
-                # a communicator whose collectives cannot be recorded: this step keeps running launch by launch (every rank runs
-                # the same software and takes the same branch, so the ranks stay in step)
-                warnings.warn("step %r: the all-reduce could not be captured (%s); running it uncaptured" % (key, e))
-                gid = None
-            except BaseException:
-                ctx.graph_abort()       # never leave the stream in capture mode (any later launch or sync would fail)
-                raise
-            self._graphs[key] = gid
-            return                      # the warm-up execution already did this step's work
-        if self._graphs[key] is None:
-            body()
-            return
-        ctx.graph_launch(self._graphs[key])
+
+        def uncapturable(e):
+            # a communicator whose collectives cannot be recorded: this step keeps running launch by launch (every rank runs
+            # the same software and takes the same branch, so the ranks stay in step)
+            if not (self.dp_active and e.code == L.RCGAN_ERCCL):
+                return False
+            warnings.warn("step %r: the all-reduce could not be captured (%s); running it uncaptured" % (key, e))
+            return True
+        run_rehearsed(self._graphs, key, body, ctx or self.ctx, uncapturable)
 
     # ---------------------------------------------------------------------------------- data parallel
     def _dp_early(self, grp):
@@ -1400,11 +1386,7 @@ class CifarRCGAN:
 
     # ---------------------------------------------------------------------------------- inspection
     def get_params(self):
-        out = {}
-        for grp in self.groups:
-            for n in grp.names:
-                out[n] = grp.get(n)
-        return out
+        return runtime.get_params(self.groups)
 
     def get_grads(self, group):
         """Gradients of the last step (the loss scale of the fp16 build divided out; a power of two, exact).  Under dynamic loss
@@ -1420,13 +1402,7 @@ class CifarRCGAN:
     def state_dict(self):
         """Everything tf.train.Saver would store (gan_resnet.py:906): variables, Adam slots (TF slot names
         "<var>/Adam", "<var>/Adam_1"), the optimisers' step counters and the SN ``u`` vectors."""
-        out = {}
-        for gname, grp in zip(("Generator", "Discriminator", "confusion"), self.groups):
-            for n in grp.names:
-                out[n] = grp.get(n)
-                out[n + "/Adam"] = grp.get(n, "m")
-                out[n + "/Adam_1"] = grp.get(n, "v")
-            out["_opt/%s/step" % gname] = np.array([grp.steps_applied()], np.int64)
+        out = runtime.groups_state_dict(GROUP_NAMES, self.groups)
         for k, v in self.get_state().items():
             out[k] = v
         out["_iteration"] = np.array([self.iteration], np.int64)
@@ -1451,22 +1427,7 @@ class CifarRCGAN:
         if self.overlap_gf:
             self.ctx2.sync()                 # (host-side writes to the parameters follow)
             self._gf_pending = [False] * N_CRITIC
-        for gname, grp in zip(("Generator", "Discriminator", "confusion"), self.groups):
-            for n in grp.names:
-                if n not in sd:
-                    raise KeyError("checkpoint is missing variable %s" % n)
-                grp.set(n, sd[n])
-                if n + "/Adam" in sd:
-                    grp.set(n, sd[n + "/Adam"], "m")
-                    grp.set(n, sd[n + "/Adam_1"], "v")
-            key = "_opt/%s/step" % gname
-            if key in sd:
-                grp.t = int(np.asarray(sd[key]).reshape(-1)[0])
-            else:                        # a bundle written by TensorFlow: recover the step from beta2_power
-                from .host import steps_from_beta_power
-                sfx = {"Discriminator": "", "Generator": "_1", "confusion": "_2"}[gname]
-                if "beta2_power" + sfx in sd:
-                    grp.t = steps_from_beta_power(float(np.asarray(sd["beta2_power" + sfx])), 0.9)
+        runtime.load_groups_state_dict(GROUP_NAMES, self.groups, sd, 0.9)
         for grp in self.groups:
             grp.t_dev = None                 # re-created from grp.t by the next dynamic-loss-scale update
         if self.ls_state is not None and "_loss_scale" in sd:

@@ -13,11 +13,13 @@ import torch
 
 from . import _lib as L
 from . import ops as O
+from . import runtime
 from .ops_mnist import batch_norm, conv2d, conv_cond_concat, deconv2d, linear, lrelu
-from .runtime import DT, Context, ParamGroup, check_f32_matmul_precision
+from .runtime import DT, Context, ParamGroup, check_f32_matmul_precision, run_rehearsed
 from .variables import Graph, variable_scope
 
 Y_DIM, Z_DIM, GF_DIM, DF_DIM, GFC_DIM, DFC_DIM = 10, 100, 64, 64, 1024, 1024
+GROUP_NAMES = ("generator", "discriminator", "confusion")      # of self.groups, in checkpoints ("_opt/<name>/step")
 
 
 def _trunc_normal(rs, size, stddev):
@@ -335,22 +337,10 @@ class MnistRCGAN:
         ctx.backward()
 
     def _run(self, key, body):
-        ctx = self.ctx
-        if not self.use_graphs:
+        if self.use_graphs:
+            run_rehearsed(self._graphs, key, body, self.ctx)
+        else:
             body()
-            return
-        if key not in self._graphs:
-            body()
-            ctx.sync()
-            ctx.graph_begin()
-            try:
-                body()
-            except BaseException:
-                ctx.graph_abort()       # never leave the stream in capture mode
-                raise
-            self._graphs[key] = ctx.graph_end()
-            return
-        ctx.graph_launch(self._graphs[key])
 
     def _allreduce(self, group):
         if self.world > 1:
@@ -471,28 +461,22 @@ class MnistRCGAN:
         self.g_step()
 
     def _run_once(self, key, body):
+        """body() exactly once per call, with no eager rehearsal: captured and launched the first time, replayed afterwards."""
         ctx = self.ctx
         if not self.use_graphs:
             body()
             return
         if key not in self._graphs:
-            # no eager rehearsal here: the hidden scratch of the fp32 entry points is sized up front (the capture contract of
-            # include/rcgan_hip.h) -- split reductions <= 16 MiB, narrow data gradient 4 B x batch x 14 x 14 x 25 x channels
-            ctx.reserve_scratch(max(16 << 20, 4 * self.B * 14 * 14 * 25 * 4))
-            ctx.graph_begin()
             try:
-                body()
+                # the hidden scratch of the fp32 entry points is sized up front (the capture contract of include/rcgan_hip.h) --
+                # split reductions <= 16 MiB, narrow data gradient 4 B x batch x 14 x 14 x 25 x channels
+                self._graphs[key] = ctx.capture(body, reserve=max(16 << 20, 4 * self.B * 14 * 14 * 25 * 4))
             except L.RcganError:
                 # a layer shape this bound does not cover wanted more hidden scratch than was reserved (hipErrorStreamCaptureUnsupported:
-                # nothing of the capture has run): drop the capture, run the body eagerly -- which grows the scratch -- as THIS step, and
-                # capture on the next call.  A genuine error raises again from the eager run.
-                ctx.graph_abort()
+                # nothing of the capture has run): the capture is dropped; run the body eagerly -- which grows the scratch -- as THIS
+                # step, and capture on the next call.  A genuine error raises again from the eager run.
                 body()
                 return
-            except BaseException:
-                ctx.graph_abort()
-                raise
-            self._graphs[key] = ctx.graph_end()
         ctx.graph_launch(self._graphs[key])
 
     # ------------------------------------------------------------------------------------ io
@@ -618,13 +602,7 @@ class MnistRCGAN:
     def state_dict(self):
         """TF variable names -> arrays: parameters, Adam slots ("<var>/Adam", "<var>/Adam_1"), optimiser steps,
         BN moving statistics and power-iteration vectors (what tf.train.Saver stores for DCGAN, model.py:845-854)."""
-        sd = {}
-        for gname, grp in zip(("generator", "discriminator", "confusion"), self.groups):
-            for n in grp.names:
-                sd[n] = grp.get(n)
-                sd[n + "/Adam"] = grp.get(n, "m")
-                sd[n + "/Adam_1"] = grp.get(n, "v")
-            sd["_opt/%s/step" % gname] = np.array([grp.t], np.int64)
+        sd = runtime.groups_state_dict(GROUP_NAMES, self.groups)
         sd.update(self.get_state())
         # AdamOptimizer's own step state, in the reference's creation order: d_optim, g_optim, c_optim (model.py:250-262)
         from .host import adam_power_tensors
@@ -635,22 +613,7 @@ class MnistRCGAN:
         return sd
 
     def load_state_dict(self, sd):
-        for gname, grp in zip(("generator", "discriminator", "confusion"), self.groups):
-            for n in grp.names:
-                if n not in sd:
-                    raise KeyError("checkpoint is missing variable %s" % n)
-                grp.set(n, sd[n])
-                if n + "/Adam" in sd:
-                    grp.set(n, sd[n + "/Adam"], "m")
-                    grp.set(n, sd[n + "/Adam_1"], "v")
-            key = "_opt/%s/step" % gname
-            if key in sd:
-                grp.t = int(np.asarray(sd[key]).reshape(-1)[0])
-            else:                        # a bundle written by TensorFlow: recover the step from beta2_power
-                from .host import steps_from_beta_power
-                sfx = {"discriminator": "", "generator": "_1", "confusion": "_2"}[gname]
-                if "beta2_power" + sfx in sd:
-                    grp.t = steps_from_beta_power(float(np.asarray(sd["beta2_power" + sfx])), 0.999)
+        runtime.load_groups_state_dict(GROUP_NAMES, self.groups, sd, 0.999)
         ctx = self.ctx
         with torch.cuda.stream(ctx.stream):
             for k, t in self.state.items():
@@ -659,11 +622,7 @@ class MnistRCGAN:
         ctx.sync()
 
     def get_params(self):
-        out = {}
-        for grp in self.groups:
-            for n in grp.names:
-                out[n] = grp.get(n)
-        return out
+        return runtime.get_params(self.groups)
 
     def get_grads(self, group):
         return {n: group.get(n, "grad") for n in group.names}

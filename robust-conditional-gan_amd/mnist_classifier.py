@@ -11,14 +11,14 @@ output ``pred_class`` -- the interface of the "deep MNIST" convnet, rebuilt here
 fp32 activations, single GPU.  The convolutions and dense layers are the fp32 gather GEMM, relu + max pool and dropout are
 rcgan_relu_maxpool2_* / rcgan_dropout_* (csrc/classifier.hip), the loss is the sparse softmax cross-entropy (plain or forward-corrected
 for noisy labels) and the optimiser the captured TF-form Adam.  ``MnistLabelClassifier(asset).predict`` is a ``predict_fn`` for
-``eval_mnist.generated_label_accuracy``."""
+``eval_mnist.generated_label_accuracy``.  What the trainer shares with the CIFAR one is ``label_trainer.LabelTrainer``."""
 import numpy as np
 import torch
 
 from . import _lib as L
 from . import ops as O
-from .data import check_confusion_matrix
-from .runtime import Context, ParamGroup, check_f32_matmul_precision
+from .label_trainer import LabelTrainer
+from .runtime import Context, check_f32_matmul_precision
 
 FEATURE_DIM = 1024
 FLAT = 7 * 7 * 64
@@ -100,59 +100,35 @@ def _softmax(ctx, w, images, batch):
     return np.concatenate(out, axis=0) if out else np.zeros((0, w["fc2/w"].shape[1]), np.float32)
 
 
-class MnistClassifierTrainer:
+class MnistClassifierTrainer(LabelTrainer):
+    SLABS = (("m", "m"), ("v", "v"))
+    _check_images = staticmethod(check_images)
+
     def __init__(self, n_classes=10, batch_size=128, keep_prob=0.5, beta1=0.9, beta2=0.999, eps=1e-8, device=0, seed=0, use_graphs=True,
                  variables=None, f32_matmul_precision="highest", confusion_matrix=None):
         """confusion_matrix: None trains on the labels as they are (sparse softmax cross-entropy).  A [K,K] row-stochastic matrix
         C[clean, noisy] declares the labels NOISY: the step then uses the forward-corrected loss -log((softmax(z) . C)[label]) (Patrini
         et al. 2017) and ``recover_labels`` becomes available -- the calls LabelClassifierTrainer makes."""
-        self.f32_matmul_precision = check_f32_matmul_precision(f32_matmul_precision, "f32")
+        check_f32_matmul_precision(f32_matmul_precision, "f32")
         if not 0.0 < float(keep_prob) <= 1.0:
             raise ValueError("keep_prob %r: (0, 1]" % (keep_prob,))
         specs = variables if variables is not None else create_mnist_classifier_variables(seed, n_classes)
         want = variable_shapes(n_classes)
         if [(n, tuple(s)) for n, s, _ in specs] != want:
             raise ValueError("variables %s, expected %s" % ([(n, tuple(s)) for n, s, _ in specs], want))
-        self.K, self.B = int(n_classes), int(batch_size)
         self.keep_prob, self.beta1, self.beta2, self.eps = float(keep_prob), float(beta1), float(beta2), float(eps)
-        self.seed, self.use_graphs = int(seed), bool(use_graphs)
+        self.seed = int(seed)
         # activations of a step at batch 128: ~30 MB with their gradients; evaluation at batch 1000: ~150 MB
-        self.ctx = ctx = Context(device, "f32", arena_bytes=1 << 30, ws_bytes=1 << 28)
-        ctx.set_f32_matmul_precision(self.f32_matmul_precision)
-        self.P = ParamGroup(ctx, specs)
-        self.w = {}
-        for n in self.P.names:
-            p = self.P.param(n)
-            p.req = True
-            self.w[n.replace("|", "/")] = p
-        B = self.B
+        super().__init__(specs, n_classes, batch_size, self.seed, use_graphs, f32_matmul_precision, confusion_matrix, device, 1 << 30)
+
+    def _make_buffers(self):
+        ctx, B = self.ctx, self.B
         self.x = ctx.persistent((B, 28, 28, 1), L.F32, fill=0.0)
         self.draws = ctx.persistent((2 * B,), "i32", fill=0)         # [index (B) | labels (B)]: one upload per step
         self.index, self.labels = self.draws.rows(0, B), self.draws.rows(B, 2 * B)
         with torch.cuda.stream(ctx.stream):
             self.rng_state = torch.zeros(2, dtype=torch.int64, device=ctx.device)      # the dropout stream's offset, in quads
         self.dropout_seed = self.seed * 1000003 + 900007
-        self.loss_acc, self.n_correct = self.P.scalar(0), self.P.scalar(1)
-        self.ct = self.confusion_matrix = None
-        if confusion_matrix is not None:
-            self.ct = ctx.persistent((self.K, self.K), L.F32, fill=0.0)
-            self.set_confusion_matrix(confusion_matrix)
-        self.images = self.labels_all = None
-        self.n_images = 0
-        self.rs = np.random.RandomState(self.seed + 1)              # the order of the batches
-        self._order, self._at = None, 0
-        self.steps = 0
-        self._graph, self._rehearsed = None, False
-        ctx.sync()
-
-    def set_confusion_matrix(self, C_matrix):
-        """Overwrite the confusion matrix in place (entries >= 0, rows summing to 1 within 1e-6); a captured step reads the new one from
-        its next launch on.  Only for a trainer that was built with one."""
-        if self.ct is None:
-            raise RuntimeError("this trainer was built without a confusion matrix (plain cross-entropy)")
-        Cm = check_confusion_matrix(C_matrix, self.K)
-        self.ctx.upload(np.ascontiguousarray(Cm.T), L.F32, out=self.ct)
-        self.confusion_matrix = Cm
 
     # ------------------------------------------------------------------------------------ data
     def load_data(self, images, labels):
@@ -166,28 +142,7 @@ class MnistClassifierTrainer:
             if img.max() > 255.0:
                 raise ValueError("images outside [0, 1] and [0, 255]")
             img = img / np.float32(255.0)
-        if lab.min() < 0 or lab.max() >= self.K:
-            raise ValueError("labels outside [0, %d)" % self.K)
-        if self._graph is not None:
-            self.ctx.check(self.ctx.lib.rcgan_graph_destroy(self.ctx.h, self._graph))      # the captured step addresses the old buffers
-            self._graph = None
-        with torch.cuda.stream(self.ctx.stream):
-            self.images = torch.from_numpy(np.ascontiguousarray(img, np.float32)).to(self.ctx.device)
-        self.labels_all = lab
-        self.n_images = len(lab)
-        self._order, self._at = None, 0
-        self.ctx.sync()
-
-    def _draw_index(self):
-        """The next batch of a shuffled pass over the training set (a fresh permutation per pass, the tail carried over)."""
-        out = []
-        while len(out) < self.B:
-            if self._order is None or self._at >= len(self._order):
-                self._order, self._at = self.rs.permutation(self.n_images), 0
-            take = self._order[self._at:self._at + self.B - len(out)]
-            self._at += len(take)
-            out.extend(take.tolist())
-        return np.asarray(out, np.int32)
+        self._install_data(np.ascontiguousarray(img, np.float32), lab, labels_on_device=False)
 
     # ------------------------------------------------------------------------------------ step
     def _body(self):
@@ -195,55 +150,20 @@ class MnistClassifierTrainer:
         ctx.new_step()
         self.P.zero_grad()
         ctx.check(ctx.lib.rcgan_gather_rows(ctx.h, B, 784, self.images.data_ptr(), self.index.ptr, self.x.ptr))
-        logits = mnist_classifier_logits(ctx, self.w, self.x, keep_prob=self.keep_prob, rng=(self.dropout_seed, self.rng_state))
-        if self.ct is None:
-            O.softmax_xent(ctx, logits, self.labels, 1.0, self.loss_acc, self.n_correct)
-        else:
-            O.softmax_xent_forward(ctx, logits, self.labels, self.ct, 1.0, self.loss_acc, self.n_correct)
+        self._loss(mnist_classifier_logits(ctx, self.w, self.x, keep_prob=self.keep_prob, rng=(self.dropout_seed, self.rng_state)))
         ctx.backward()
         self.P.adam_captured(self.beta1, self.beta2, self.eps)
 
     def step(self, lr, index=None):
         """One training step on the samples ``index`` [B] of the loaded set (drawn from the trainer's own numpy stream when not given).
         The dropout mask comes from the device stream (dropout_seed, rng_state), eager or replayed."""
-        ctx, B = self.ctx, self.B
-        if self.images is None:
-            raise RuntimeError("load_data() first")
-        index = self._draw_index() if index is None else np.asarray(index, np.int32).reshape(-1)
-        if index.shape != (B,):
-            raise ValueError("index %s for batch size %d" % (index.shape, B))
-        if index.min() < 0 or index.max() >= self.n_images:
-            raise ValueError("index outside [0, %d)" % self.n_images)
-        ctx.upload(np.concatenate([index, self.labels_all[index]]), out=self.draws)
+        index = self._step_index(index)
+        if index.shape != (self.B,):
+            raise ValueError("index %s for batch size %d" % (index.shape, self.B))
+        self._check_index_range(index)
+        self.ctx.upload(np.concatenate([index, self.labels_all[index]]), out=self.draws)
         self.P.set_hyper_device(lr, self.steps + 1)
-        if not self.use_graphs or not self._rehearsed:
-            # eager: always without graphs, and the very first step with them (module loads; it also grows the fp32 path's hidden scratch)
-            self._body()
-            self._rehearsed = True
-        else:
-            if self._graph is None:
-                # the fp32 convolutions keep split-reduction partials in a hidden scratch that cannot grow inside a capture: the
-                # documented upper bound of that scratch for ANY shape (16 MiB, include/rcgan_hip.h: capture contract) is reserved,
-                # so the capture does not hinge on the rehearsal.  (No layer here produces a gradient for <= 2 channels: the first
-                # convolution's input is the data.)
-                ctx.reserve_scratch(16 << 20)
-                ctx.graph_begin()
-                try:
-                    self._body()
-                except BaseException:
-                    ctx.graph_abort()
-                    raise
-                self._graph = ctx.graph_end()
-            ctx.graph_launch(self._graph)
-        self.P.version += 1
-        self.steps += 1
-
-    def losses(self):
-        """(mean loss, accuracy) of the last step's batch, both before its update and under its dropout mask."""
-        return float(self.ctx.download(self.loss_acc)[0]), float(self.ctx.download(self.n_correct)[0]) / self.B
-
-    def get_grads(self):
-        return {n: self.P.get(n, "grad") for n in self.P.names}
+        self._run_step()
 
     def rng_offset(self):
         """The dropout stream's offset (quads drawn so far)."""
@@ -253,57 +173,28 @@ class MnistClassifierTrainer:
         return int(v[0])
 
     # ------------------------------------------------------------------------------------ evaluation
+    def _forward_chunks(self, images, batch, fn):
+        _forward_chunks(self.ctx, self.w, images, batch, lambda logits, feat, lo, n: fn(logits, lo, n))
+
     def evaluate(self, images, labels, batch=1000):
         """(accuracy, softmax [n,K]) on float [n,28,28,1] images in [0, 1], ``batch`` at a time, no dropout: the launches of
         MnistLabelClassifier.softmax."""
         p = _softmax(self.ctx, self.w, images, batch)
         return float((np.argmax(p, axis=1) == np.asarray(labels).reshape(-1)).mean()), p
 
-    def recover_labels(self, images, noisy_labels, batch=1000):
-        """Label recovery: the posterior over the CLEAN label of each image given its noisy one, post[y] ~ softmax(z)[y] C[y, noisy], and
-        its arg-max (lowest index on ties) -> (recovered [n] int32, posterior [n,K] fp32).  A label outside [0, K), or one no class can
-        emit under C, gives recovered = -1 and a zero posterior row."""
-        if self.ct is None:
-            raise RuntimeError("recover_labels needs the confusion matrix the trainer was built with")
-        ctx = self.ctx
-        noisy = np.ascontiguousarray(np.asarray(noisy_labels).reshape(-1).astype(np.int32))
-        if len(noisy) != len(check_images(images)):
-            raise ValueError("%d labels for %d images" % (len(noisy), len(images)))
-        rec_out, post_out = [], []
-
-        def one(logits, feat, lo, n):
-            post, got = ctx.empty((n, self.K), L.F32), ctx.empty((n,), "i32")
-            O.softmax_xent_forward(ctx, logits, ctx.upload(noisy[lo:lo + n]), self.ct, 1.0, None, None, post, got)
-            rec_out.append(ctx.download(got).copy())
-            post_out.append(ctx.download(post).copy())
-        _forward_chunks(ctx, self.w, images, batch, one)
-        return np.concatenate(rec_out, axis=0), np.concatenate(post_out, axis=0)
-
     # ------------------------------------------------------------------------------------ io
     def state_dict(self):
-        g = lambda which: {n: self.P.get(n, which) for n in self.P.names}
-        return dict(value=g("value"), m=g("m"), v=g("v"), steps=self.steps, rng=self.rs.get_state(), rng_offset=self.rng_offset(),
-                    order=None if self._order is None else self._order.copy(), at=self._at)
+        return dict(super().state_dict(), rng_offset=self.rng_offset())
 
     def load_state_dict(self, sd):
-        for n in self.P.names:
-            self.P.set(n, sd["value"][n])
-            self.P.set(n, sd["m"][n], "m")
-            self.P.set(n, sd["v"][n], "v")
-        self.steps = int(sd["steps"])
-        self.rs.set_state(sd["rng"])
         with torch.cuda.stream(self.ctx.stream):
             self.rng_state.copy_(torch.tensor([int(sd["rng_offset"]), 0], dtype=torch.int64))
-        self._order, self._at = (None if sd["order"] is None else np.asarray(sd["order"]).copy()), int(sd["at"])
-        self.ctx.sync()
+        super().load_state_dict(sd)
 
     def save_asset(self, path):
         """The eight arrays under the asset's keys, as MnistLabelClassifier(path) reads them."""
         with open(path, "wb") as f:
             np.savez(f, **{n: self.P.get(n) for n in self.P.names})
-
-    def close(self):
-        self.ctx.close()
 
 
 def asset_n_classes(asset):

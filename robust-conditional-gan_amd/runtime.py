@@ -293,6 +293,21 @@ class Context:
         self.capturing = False
         self.check(self.lib.rcgan_graph_abort(self.h))
 
+    def capture(self, body, reserve=0):
+        """Record the launches of body() into a hipGraph WITHOUT running them -> graph id (graph_launch runs it).  reserve: bytes of
+        hidden scratch grown first (reserve_scratch).  Whatever body() or the end of the capture raises, the stream is taken out of
+        capture mode before the exception travels on: any later launch or sync would fail otherwise.  (rcgan_graph_abort is a no-op
+        when nothing is being captured.)  The one place of the package that begins, ends or aborts a capture."""
+        if reserve > 0:
+            self.reserve_scratch(reserve)
+        self.graph_begin()
+        try:
+            body()
+            return self.graph_end()
+        except BaseException:
+            self.graph_abort()
+            raise
+
     def graph_launch(self, gid):
         self.check(self.lib.rcgan_graph_launch(self.h, gid))
 
@@ -303,6 +318,26 @@ class Context:
         ms = C.c_float(0)
         self.check(self.lib.rcgan_event_elapsed_ms(self.h, a, b, C.byref(ms)))
         return ms.value
+
+
+def run_rehearsed(graphs, key, body, ctx, uncapturable=None):
+    """The rehearse-then-capture protocol of the GAN engines' steps (CifarRCGAN._run, MnistRCGAN._run); body() does the step's work
+    exactly once per call.  The first call under ``key`` runs it eagerly (module loads, LDS attributes, self test) and then captures it
+    without launching; later calls replay graphs[key].  uncapturable(e): which RcganError out of the capture means "this step cannot
+    be captured" -- graphs[key] becomes None and the step runs launch by launch from then on; every other exception travels on."""
+    if key not in graphs:
+        body()
+        ctx.sync()
+        try:
+            graphs[key] = ctx.capture(body)
+        except L.RcganError as e:
+            if uncapturable is None or not uncapturable(e):
+                raise
+            graphs[key] = None
+    elif graphs[key] is None:
+        body()
+    else:
+        ctx.graph_launch(graphs[key])
 
 
 class ParamGroup:
@@ -471,3 +506,46 @@ class ParamGroup:
                                          self.m.data_ptr() + o, self.v.data_ptr() + o, self._lr, self._t,
                                          beta1, beta2, eps, clip, grad_scale))
         self.version += 1
+
+
+# ---------------------------------------------------------------------- checkpoints of a model's parameter groups
+# beta2_power's suffix in a bundle written by TensorFlow, by the group's place in a model's ``groups`` (generator, critic,
+# confusion): the reference creates the critic's optimiser first, then the generator's, then the confusion matrix's.
+_TF_POWER_SUFFIX = ("_1", "", "_2")
+
+
+def get_params(groups):
+    """{variable name: value} over the groups."""
+    return {n: grp.get(n) for grp in groups for n in grp.names}
+
+
+def groups_state_dict(names, groups):
+    """What tf.train.Saver stores of the groups, under TF's names: every variable, its Adam slots "<var>/Adam" and "<var>/Adam_1", and
+    per group "_opt/<name>/step" (the updates applied: ParamGroup.steps_applied, which is ``t`` without dynamic loss scaling)."""
+    sd = {}
+    for gname, grp in zip(names, groups):
+        for n in grp.names:
+            sd[n] = grp.get(n)
+            sd[n + "/Adam"] = grp.get(n, "m")
+            sd[n + "/Adam_1"] = grp.get(n, "v")
+        sd["_opt/%s/step" % gname] = np.array([grp.steps_applied()], np.int64)
+    return sd
+
+
+def load_groups_state_dict(names, groups, sd, beta2):
+    """groups_state_dict's inverse.  Adam slots are optional; a bundle written by TensorFlow has no step entries, and the step is
+    recovered from its beta2_power (Adam's ``beta2``)."""
+    from .host import steps_from_beta_power
+    for gname, grp, sfx in zip(names, groups, _TF_POWER_SUFFIX):
+        for n in grp.names:
+            if n not in sd:
+                raise KeyError("checkpoint is missing variable %s" % n)
+            grp.set(n, sd[n])
+            if n + "/Adam" in sd:
+                grp.set(n, sd[n + "/Adam"], "m")
+                grp.set(n, sd[n + "/Adam_1"], "v")
+        key = "_opt/%s/step" % gname
+        if key in sd:
+            grp.t = int(np.asarray(sd[key]).reshape(-1)[0])
+        elif "beta2_power" + sfx in sd:
+            grp.t = steps_from_beta_power(float(np.asarray(sd["beta2_power" + sfx])), beta2)

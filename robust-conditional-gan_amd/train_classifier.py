@@ -11,15 +11,18 @@ the asset is still a drop-in for ``--label_classifier``; ``--recover_out`` then 
 a plain cross-entropy stage on the noisy labels, Patrini's anchor estimate from its soft-max over the training set, then the
 forward-corrected run from a fresh initialisation.  ``--alpha`` below 1 corrupts the training labels once (a stand-in for labels
 that arrive noisy); the clean ones are then kept for reporting only.
+
+The label-noise flags and their checks, the corruption, matrix loading, the training loop and the writer of ``--recover_out`` are
+``label_driver``'s, shared with ``train_mnist_classifier.py``.
 """
 import logging
 import os
 import sys
-import time
 
 import numpy as np
 
 from . import data as D
+from . import label_driver as V
 from .host import Flags
 from .train_cifar import DATA_DIR, dataset_setup
 
@@ -42,16 +45,10 @@ def define_flags():
     f.DEFINE_boolean("no_augment", False, "no random translation / mirror")
     f.DEFINE_integer("seed", 0, "seed of the initialisation and of the input pipeline")
     f.DEFINE_string("f32_matmul_precision", 'highest', "fp32 GEMMs [highest: fp32 matrix cores, high: split-bf16 matrix cores]")
-    f.DEFINE_float("alpha", 1.0, "< 1: corrupt the training labels once through the one-coin matrix C_ALPHA(alpha, K); 1.0: clean labels")
-    f.DEFINE_integer("label_seed", 0, "seed of the label corruption")
-    f.DEFINE_string("loss", 'ce', "[ce] sparse softmax cross-entropy, [forward] forward-corrected for noisy labels (needs --confusion_matrix)")
-    f.DEFINE_string("confusion_matrix", None, "with --loss forward: [known] C_ALPHA(alpha, K), [estimate] anchor estimate after a plain "
-                    "cross-entropy stage, or PATH.npy holding a [K,K] matrix C[clean, noisy]")
+    V.define_noise_flags(f, "K", "with --loss forward: [known] C_ALPHA(alpha, K), [estimate] anchor estimate after a plain "
+                         "cross-entropy stage, or PATH.npy holding a [K,K] matrix C[clean, noisy]")
     f.DEFINE_integer("estimate_steps", 0, "--confusion_matrix estimate: steps of the plain cross-entropy stage (0: as many as the main run)")
     f.DEFINE_float("anchor_quantile", 0.97, "--confusion_matrix estimate: the quantile of estimate_confusion_anchor (1.0: the arg-max sample)")
-    f.DEFINE_string("recover_out", None, "with --loss forward: where the recovered training labels (.npz) are written")
-    f.DEFINE_string("out", None, "where the weight asset (.npz) is written")
-    f.DEFINE_string("log_file", None, "logging file")
     return f
 
 
@@ -78,30 +75,13 @@ def lr_at(step, total, lr):
 
 def check_noise_flags(FLAGS):
     """The label-noise flags against each other, before anything is loaded.  -> the matrix source: None, 'known', 'estimate' or a path."""
-    if not 0.0 < FLAGS.alpha <= 1.0:
-        raise ValueError('flag alpha = %r: (0, 1]' % (FLAGS.alpha,))
-    if FLAGS.loss not in ('ce', 'forward'):
-        raise ValueError('flag loss = %r: ce or forward' % (FLAGS.loss,))
-    src = FLAGS.confusion_matrix
-    if FLAGS.loss == 'forward' and src is None:
-        raise ValueError('--loss forward needs --confusion_matrix [known, estimate, PATH.npy]')
-    if FLAGS.loss == 'ce' and src is not None:
-        raise ValueError('--confusion_matrix is read by --loss forward only')
-    if FLAGS.loss == 'ce' and FLAGS.recover_out is not None:
-        raise ValueError('--recover_out needs --loss forward')
-    if src is not None and src not in ('known', 'estimate') and not src.endswith('.npy'):
-        raise ValueError('flag confusion_matrix = %r: known, estimate or PATH.npy' % (src,))
+    V.check_alpha(FLAGS)
+    src = V.check_loss(FLAGS, ('known', 'estimate'))
     if FLAGS.estimate_steps < 0:
         raise ValueError('flag estimate_steps = %r' % (FLAGS.estimate_steps,))
     if not 0.0 < FLAGS.anchor_quantile <= 1.0:
         raise ValueError('flag anchor_quantile = %r: (0, 1]' % (FLAGS.anchor_quantile,))
     return src
-
-
-def _row_normalised(C):
-    """A matrix that was stored or computed in float32: rows brought to sum 1 in float64 (the trainer asks for 1e-6)."""
-    C = np.asarray(C, np.float64)
-    return C / C.sum(axis=1, keepdims=True)
 
 
 def _in_chunks(fn, images_chw_u8, *rest, chunk=10000):
@@ -116,23 +96,14 @@ def _in_chunks(fn, images_chw_u8, *rest, chunk=10000):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     FLAGS = define_flags().parse(argv)
-    if FLAGS.log_file is None:
-        raise ValueError('flag log_file is required')
-    if FLAGS.out is None:
-        raise ValueError('flag out is required')
+    V.check_outputs(FLAGS)
     source = check_noise_flags(FLAGS)
     n_classes, data_dir = dataset_setup(FLAGS)
     logging.basicConfig(filename=FLAGS.log_file, level=logging.INFO, format='%(asctime)s %(levelname)-8s %(message)s')
     logging.info('dataset = {} ({} classes)'.format(FLAGS.dataset, n_classes))
     tx, ty, vx, vy = load_clean(FLAGS, n_classes, data_dir)
     held = vx.reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
-    ty_clean = None
-    if FLAGS.alpha < 1.0:
-        # the training labels arrive noisy: corrupted once, the clean ones kept for reporting only (the held-out labels stay clean)
-        ty_clean = ty
-        ty = D.noisy_labels(ty_clean, D.C_ALPHA(FLAGS.alpha, n_classes), np.random.RandomState(FLAGS.label_seed))
-        logging.info('alpha = {}: training labels corrupted (label_seed {}), {:.4f} of them still agree with the clean ones'.format(
-            FLAGS.alpha, FLAGS.label_seed, float((ty == ty_clean).mean())))
+    ty, ty_clean = V.corrupt_labels(FLAGS, ty, n_classes)
     from .classifier import LabelClassifierTrainer
     B = FLAGS.batch_size
     per_epoch = max(len(ty) // B, 1)
@@ -145,34 +116,23 @@ def main(argv=None):
                                    pad=0 if FLAGS.no_augment else 4, seed=FLAGS.seed, f32_matmul_precision=FLAGS.f32_matmul_precision,
                                    device=int(os.environ.get("LOCAL_RANK", "0")), confusion_matrix=confusion_matrix)
         t.load_data(tx, ty)
-        t0 = time.time()
-        acc = None
-        for step in range(n_steps):
-            t.step(lr_at(step, n_steps, FLAGS.lr), shift_flip=no_flip)
-            if (step + 1) % per_epoch == 0 or step + 1 == n_steps:
-                loss, batch_acc = t.losses()
-                acc, _ = t.evaluate(held, vy)
-                logging.info('epoch {} step {} lr {:g} loss {:.4f} batch accuracy {:.4f} held-out accuracy {:.4f} ({:.0f} s)'.format(
-                    (step + 1) // per_epoch, step + 1, lr_at(step, n_steps, FLAGS.lr), loss, batch_acc, acc, time.time() - t0))
-        return t, acc
+        return t, V.train(t, n_steps, per_epoch, lambda step: lr_at(step, n_steps, FLAGS.lr), held, vy, shift_flip=no_flip)
 
     Cm = None
-    if source == 'known':
-        Cm = D.C_ALPHA(FLAGS.alpha, n_classes)
-    elif source == 'estimate':
+    if source == 'estimate':
         n_est = FLAGS.estimate_steps if FLAGS.estimate_steps > 0 else total
         logging.info('confusion matrix: {} steps of plain cross-entropy on the noisy labels, then the anchor estimate'.format(n_est))
         t, _ = run(n_est, None)
         probs = np.concatenate(_in_chunks(lambda x: t.evaluate(x, np.zeros(len(x), np.int64))[1], tx), axis=0)
         t.close()
-        Cm = _row_normalised(D.estimate_confusion_anchor(probs, FLAGS.anchor_quantile))
+        Cm = V.row_normalised(D.estimate_confusion_anchor(probs, FLAGS.anchor_quantile))
         logging.info('estimated confusion matrix (quantile {:g}): diagonal mean {:.4f}, min {:.4f}'.format(
             FLAGS.anchor_quantile, float(np.diag(Cm).mean()), float(np.diag(Cm).min())))
         if ty_clean is not None:
             logging.info('estimate against C_ALPHA({}): largest entry error {:.4f}'.format(
                 FLAGS.alpha, float(np.abs(Cm - D.C_ALPHA(FLAGS.alpha, n_classes)).max())))
     elif source is not None:
-        Cm = D.check_confusion_matrix(_row_normalised(np.load(source)), n_classes)
+        Cm = V.load_matrix(FLAGS, source, n_classes)
     if Cm is not None:
         logging.info('loss = forward, confusion matrix from {}'.format(source))
     t, acc = run(total, Cm)
@@ -181,17 +141,7 @@ def main(argv=None):
     if FLAGS.recover_out is not None:
         parts = _in_chunks(t.recover_labels, tx, ty)
         y_rec, post = np.concatenate([p[0] for p in parts], axis=0), np.concatenate([p[1] for p in parts], axis=0)
-        fields = dict(y_noisy=np.asarray(ty, np.int64), y_recover=y_rec.astype(np.int64), posterior=post, confusion_matrix=Cm)
-        if ty_clean is not None:
-            fields.update(recovery_accuracy=float((y_rec == ty_clean).mean()), noisy_agreement=float((ty == ty_clean).mean()))
-            logging.info('label recovery accuracy {:.4f} (noisy labels agree with clean: {:.4f})'.format(
-                fields['recovery_accuracy'], fields['noisy_agreement']))
-        else:
-            logging.info('label recovery: {:.4f} of the recovered labels differ from the given ones (no clean labels to score against)'.format(
-                float((y_rec != ty).mean())))
-        with open(FLAGS.recover_out, 'wb') as f:
-            np.savez(f, **fields)
-        logging.info('wrote {}'.format(FLAGS.recover_out))
+        V.write_recovered(FLAGS.recover_out, y_rec, post, ty, ty_clean, Cm)
     t.close()
     return acc
 

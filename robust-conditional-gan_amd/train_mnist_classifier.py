@@ -10,16 +10,18 @@ With only NOISY labels and a confusion matrix C: ``--loss forward`` trains on th
 -log((softmax(z) . C)[label]) (Patrini et al. 2017), so the asset is still a drop-in for ``--label_classifier``; ``--recover_out`` then
 writes the recovered training labels.  The matrix is ``known`` (the one-coin matrix of ``--alpha``) or a ``.npy`` file.  ``--alpha``
 below 1 corrupts the training labels once; the clean ones are then kept for reporting only.
+
+The label-noise flags and their checks, the corruption, matrix loading, the training loop and the writer of ``--recover_out`` are
+``label_driver``'s, shared with ``train_classifier.py``.
 """
 import logging
 import os
 import sys
-import time
 
 import numpy as np
 
-from . import data as D
 from . import data_mnist as DM
+from . import label_driver as V
 from .host import Flags
 
 N_CLASSES = DM.Y_DIM
@@ -37,42 +39,21 @@ def define_flags():
     f.DEFINE_float("lr", 1e-4, "Adam learning rate (constant)")
     f.DEFINE_float("keep_prob", 0.5, "dropout keep probability in front of the last dense layer, (0, 1]")
     f.DEFINE_integer("seed", 0, "seed of the initialisation, of the batch order and of the dropout stream")
-    f.DEFINE_float("alpha", 1.0, "< 1: corrupt the training labels once through the one-coin matrix C_ALPHA(alpha, 10); 1.0: clean labels")
-    f.DEFINE_integer("label_seed", 0, "seed of the label corruption")
-    f.DEFINE_string("loss", 'ce', "[ce] sparse softmax cross-entropy, [forward] forward-corrected for noisy labels (needs --confusion_matrix)")
-    f.DEFINE_string("confusion_matrix", None, "with --loss forward: [known] C_ALPHA(alpha, 10), or PATH.npy holding a [10,10] matrix C[clean, noisy]")
-    f.DEFINE_string("recover_out", None, "with --loss forward: where the recovered training labels (.npz) are written")
-    f.DEFINE_string("out", None, "where the weight asset (.npz) is written")
-    f.DEFINE_string("log_file", None, "logging file")
+    V.define_noise_flags(f, "10", "with --loss forward: [known] C_ALPHA(alpha, 10), or PATH.npy holding a [10,10] matrix C[clean, noisy]")
     return f
 
 
 def check_flags(FLAGS):
     """The flags against each other, before anything is loaded.  -> the matrix source: None, 'known' or a path."""
-    if FLAGS.log_file is None:
-        raise ValueError('flag log_file is required')
-    if FLAGS.out is None:
-        raise ValueError('flag out is required')
-    if not 0.0 < FLAGS.alpha <= 1.0:
-        raise ValueError('flag alpha = %r: (0, 1]' % (FLAGS.alpha,))
+    V.check_outputs(FLAGS)
+    V.check_alpha(FLAGS)
     if not 0.0 < FLAGS.keep_prob <= 1.0:
         raise ValueError('flag keep_prob = %r: (0, 1]' % (FLAGS.keep_prob,))
     if FLAGS.batch_size < 1 or FLAGS.epochs < 0 or FLAGS.max_steps < 0:
         raise ValueError('flags batch_size = %r, epochs = %r, max_steps = %r' % (FLAGS.batch_size, FLAGS.epochs, FLAGS.max_steps))
-    if FLAGS.loss not in ('ce', 'forward'):
-        raise ValueError('flag loss = %r: ce or forward' % (FLAGS.loss,))
-    src = FLAGS.confusion_matrix
-    if FLAGS.loss == 'forward' and src is None:
-        raise ValueError('--loss forward needs --confusion_matrix [known, PATH.npy]')
-    if FLAGS.loss == 'ce' and src is not None:
-        raise ValueError('--confusion_matrix is read by --loss forward only')
-    if FLAGS.loss == 'ce' and FLAGS.recover_out is not None:
-        raise ValueError('--recover_out needs --loss forward')
-    if src == 'estimate':
+    if FLAGS.loss == 'forward' and FLAGS.confusion_matrix == 'estimate':
         raise ValueError('--confusion_matrix estimate is not implemented for the MNIST classifier: known or PATH.npy')
-    if src is not None and src != 'known' and not src.endswith('.npy'):
-        raise ValueError('flag confusion_matrix = %r: known or PATH.npy' % (src,))
-    return src
+    return V.check_loss(FLAGS, ('known',))
 
 
 def load_clean(FLAGS):
@@ -98,19 +79,8 @@ def main(argv=None):
     tx, ty, vx, vy = load_clean(FLAGS)
     if tx.min() < 0.0 or tx.max() > 1.0:
         raise ValueError('images outside [0, 1] after scaling: [%g, %g]' % (tx.min(), tx.max()))
-    ty_clean = None
-    if FLAGS.alpha < 1.0:
-        # the training labels arrive noisy: corrupted once, the clean ones kept for reporting only (the held-out labels stay clean)
-        ty_clean = ty
-        ty = D.noisy_labels(ty_clean, D.C_ALPHA(FLAGS.alpha, N_CLASSES), np.random.RandomState(FLAGS.label_seed))
-        logging.info('alpha = {}: training labels corrupted (label_seed {}), {:.4f} of them still agree with the clean ones'.format(
-            FLAGS.alpha, FLAGS.label_seed, float((ty == ty_clean).mean())))
-    Cm = None
-    if source == 'known':
-        Cm = D.C_ALPHA(FLAGS.alpha, N_CLASSES)
-    elif source is not None:
-        Cm = np.asarray(np.load(source), np.float64)
-        Cm = D.check_confusion_matrix(Cm / Cm.sum(axis=1, keepdims=True), N_CLASSES)
+    ty, ty_clean = V.corrupt_labels(FLAGS, ty, N_CLASSES)
+    Cm = None if source is None else V.load_matrix(FLAGS, source, N_CLASSES)
     if Cm is not None:
         logging.info('loss = forward, confusion matrix from {}'.format(source))
     from .mnist_classifier import MnistClassifierTrainer
@@ -120,30 +90,12 @@ def main(argv=None):
     t = MnistClassifierTrainer(N_CLASSES, batch_size=B, keep_prob=FLAGS.keep_prob, seed=FLAGS.seed,
                                device=int(os.environ.get("LOCAL_RANK", "0")), confusion_matrix=Cm)
     t.load_data(tx, ty)
-    t0 = time.time()
-    acc = None
-    for step in range(total):
-        t.step(FLAGS.lr)
-        if (step + 1) % per_epoch == 0 or step + 1 == total:
-            loss, batch_acc = t.losses()
-            acc, _ = t.evaluate(vx, vy)
-            logging.info('epoch {} step {} lr {:g} loss {:.4f} batch accuracy {:.4f} held-out accuracy {:.4f} ({:.0f} s)'.format(
-                (step + 1) // per_epoch, step + 1, FLAGS.lr, loss, batch_acc, acc, time.time() - t0))
+    acc = V.train(t, total, per_epoch, lambda step: FLAGS.lr, vx, vy)
     t.save_asset(FLAGS.out)
     logging.info('wrote {} ({} classes, held-out accuracy {})'.format(FLAGS.out, N_CLASSES, acc))
     if FLAGS.recover_out is not None:
         y_rec, post = t.recover_labels(tx, ty)
-        fields = dict(y_noisy=np.asarray(ty, np.int64), y_recover=y_rec.astype(np.int64), posterior=post, confusion_matrix=Cm)
-        if ty_clean is not None:
-            fields.update(recovery_accuracy=float((y_rec == ty_clean).mean()), noisy_agreement=float((ty == ty_clean).mean()))
-            logging.info('label recovery accuracy {:.4f} (noisy labels agree with clean: {:.4f})'.format(
-                fields['recovery_accuracy'], fields['noisy_agreement']))
-        else:
-            logging.info('label recovery: {:.4f} of the recovered labels differ from the given ones (no clean labels to score against)'.format(
-                float((y_rec != ty).mean())))
-        with open(FLAGS.recover_out, 'wb') as f:
-            np.savez(f, **fields)
-        logging.info('wrote {}'.format(FLAGS.recover_out))
+        V.write_recovered(FLAGS.recover_out, y_rec, post, ty, ty_clean, Cm)
     t.close()
     return acc
 
