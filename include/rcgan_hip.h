@@ -554,6 +554,25 @@ int rcgan_dblock2_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, c
                       const float* bias1, const float* bias2, const float* bias_shortcut, void* h, void* xp, void* y);
 int rcgan_dblock2_bwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* dy, const void* h, const void* x, const void* conv1_frag,
                       const void* dblock2_frag, void* dh, void* dx);
+
+/* ---- the 32x32 input block's forward as one launch (csrc/conv_dblock1.hip) ---------------------------------------------------------
+ * D.Block.1 of the CIFAR critic (gan_resnet.py:331-353), 32 x 32 x 3 -> 16 x 16 x 128, four workgroups per image (bands of 4 pooled rows):
+ *   h = Conv1(x) + b1;  xp = meanpool2(x);  t = Shortcut(xp) + bs;  y = t + meanpool2(Conv2(relu(h)) + b2)
+ * with the 16-bit rounding points (h, xp, t, y) and the fp32 summation orders of the three launches it replaces (the image-end
+ * small-reduction kernel twice, the gather-form 64 x 64 tile kernel with one K group): every output has their bits.
+ * rcgan_dblock1_ok: 1 if d is Conv1's descriptor of exactly that block (3x3, stride 1, no flags, the build's 16-bit dtype, n >= 1) and
+ * the fragment copy exists.  dblock1_frag (rcgan_dblock1_fragment_bytes): written by rcgan_fragments_prepare_dblocks --
+ * rcgan_fragments_prepare_dblock2 with one more item in the same launch -- from block1_conv2_prepared = D.Block.1.Conv2's prepared filter
+ * under RCGAN_CONV_OUT_MEANPOOL2.  conv1_prepared / shortcut_prepared: rcgan_conv_prepare's buffers of Conv1 (d) and of the 1x1 shortcut
+ * (n x 16 x 16 x 3 -> 128), whose image-end rows are read in place.  h [n][32][32][128] and y [n][16][16][128] are written, and
+ * xp [n][16][16][3] unless it is NULL (the caller holds the pooled images): what the block's (unfused) backward pass reads. */
+int rcgan_dblock1_ok(const rcgan_conv_desc* d, const void* dblock1_frag);
+size_t rcgan_dblock1_fragment_bytes(void);
+int rcgan_fragments_prepare_dblocks(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
+                                    const void* const* prepared, void* const* frags, const void* conv2_prepared,
+                                    const void* shortcut_prepared, void* dblock2_frag, const void* block1_conv2_prepared, void* dblock1_frag);
+int rcgan_dblock1_fwd(rcgan_ctx* ctx, const rcgan_conv_desc* d, const void* x, const void* conv1_prepared, const void* shortcut_prepared,
+                      const void* dblock1_frag, const float* bias1, const float* bias2, const float* bias_shortcut, void* h, void* xp, void* y);
 /* Fused projection head: pooled features -> psi (D.Output, SN linear d -> 1), label embeddings E = table @ W_e / sigma_e + b_e
  * (embedding.py:29-51 + D.Embedding_y, gan_resnet.py:414-421), logits psi + <feat, E[l]> (:588, :654-660), loss terms and ALL
  * gradients in one launch.  Rows [0, rows_a) form part a, rows [rows_a, n) part b (real | fake of the critic step, :604-606);

@@ -222,6 +222,10 @@ SIGNATURES = {
     "rcgan_fragments_prepare_dblock2": (I, [P, P, P, I, C.POINTER(ConvDesc), P, P, P, P, P]),
     "rcgan_dblock2_fwd": (I, [P, C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P]),
     "rcgan_dblock2_bwd": (I, [P, C.POINTER(ConvDesc), P, P, P, P, P, P, P]),
+    "rcgan_dblock1_ok": (I, [C.POINTER(ConvDesc), P]),
+    "rcgan_dblock1_fragment_bytes": (SZ, []),
+    "rcgan_fragments_prepare_dblocks": (I, [P, P, P, I, C.POINTER(ConvDesc), P, P, P, P, P, P, P]),
+    "rcgan_dblock1_fwd": (I, [P, C.POINTER(ConvDesc), P, P, P, P, P, P, P, P, P, P]),
     "rcgan_dtrunk_fragment_bytes": (SZ, []),
     "rcgan_head_flush": (I, [P]),
     "rcgan_proj_head_fwd_bwd": (I, [P, C.POINTER(HeadDesc)] + [P] * 16 + [P, SZ]),

@@ -349,11 +349,24 @@ def Discriminator(inputs, labels, update_collection=None, _head=True):
             xp = getattr(Graph.current, "image_pool", None)
             if xp is not None and (x.req or xp.shape != (x.shape[0], x.shape[1] // 2, x.shape[2] // 2, x.shape[3])):
                 xp = None
-            t = Conv2D(xp if xp is not None else O.meanpool2(ctx, x), IMG_DIM, DIM_D, 1, 1, 'D.Block.1.Shortcut', he_init=False, **kw)
-            h = Conv2D(x, IMG_DIM, DIM_D, 3, 1, 'D.Block.1.Conv1', **kw)
-            x = Conv2D(h, DIM_D, DIM_D, 3, 1, 'D.Block.1.Conv2', _in_relu=True, _accumulate_into=t, _out_meanpool=True, **kw)
+            # D.Block.1: its forward as ONE launch where the step's fragment-major copy exists (ops.d_block1), else three (and the pool)
+            g = Graph.current
+            d1frag = getattr(g, "dblock1_frag", None)
+            if O.d_block1_ok(ctx, x, d1frag):
+                wb = []
+                for cv in ('Shortcut', 'Conv1', 'Conv2'):
+                    with variable_scope('D.Block.1.%s' % cv):
+                        fname = scoped('Filters')
+                        with variable_scope('filters'):
+                            wb.append(spectral_normed_weight(fname, update_collection=update_collection))
+                        wb.append(g.param(scoped('Biases')))
+                x = O.d_block1(ctx, x, *wb, frag=d1frag, pooled=xp)
+            else:
+                t = Conv2D(xp if xp is not None else O.meanpool2(ctx, x), IMG_DIM, DIM_D, 1, 1, 'D.Block.1.Shortcut', he_init=False, **kw)
+                h = Conv2D(x, IMG_DIM, DIM_D, 3, 1, 'D.Block.1.Conv1', **kw)
+                x = Conv2D(h, DIM_D, DIM_D, 3, 1, 'D.Block.1.Conv2', _in_relu=True, _accumulate_into=t, _out_meanpool=True, **kw)
             # D.Block.2 (down): its forward as ONE launch where the step's fragment-major copies exist (ops.d_block2), else four
-            g, wb = Graph.current, []
+            wb = []
             for cv in ('Shortcut', 'Conv1', 'Conv2'):
                 with variable_scope('D.Block.2.%s' % cv):
                     fname = scoped('Filters')
@@ -843,10 +856,13 @@ class CifarRCGAN:
         # every fragment-major filter copy of the critic: the 8x8 stage's (ops.d_trunk) and the register-filter layers' (ops.conv2d ->
         # rcgan_conv2d_rf: D.Block.2.Conv1, 16 x 16 x 128) -- one launch behind the preparation (rf_fragments_kernel); or, measured slower
         # and off by default (ops.FRAG_IN_PREPARE), fragment rows of the preparation launch itself.
-        g.trunk_frag = g.dblock2_frag = None
-        trunk, rf, db2 = None, [], None
+        g.trunk_frag = g.dblock2_frag = g.dblock1_frag = None
+        trunk, rf, db2, db1 = None, [], None, None
         if self.PD in which and self.ctx.act_dtype != L.F32 and (FUSED_TRUNK or O.RF_CONV):
             sn = lambda n: g.sn["Discriminator/%s/Filters" % n][0]
+            # the copy the 32x32 input block's fused forward reads (ops.d_block1): one more item of the fragment launch
+            if O.FUSED_DBLOCK1 and fused_pool_d(self.ctx, GEN_BS_MULTIPLE * self.B):
+                db1 = sn("D.Block.1.Conv2")
             trunk = [sn("D.Block.%d.%s" % (b, c)) for b in (3, 4, 5, 6) for c in ("Conv1", "Conv2")] if FUSED_TRUNK else None
             if O.RF_CONV:
                 d = L.ConvDesc(1, 16, 16, DIM_D, DIM_D, 3, 3, 1, self.ctx.act_dtype, L.CONV_IN_RELU)
@@ -866,7 +882,9 @@ class CifarRCGAN:
             # (the down block's copies are items of the separate fragment launch only: with the fragment rows its forward stays four launches)
         else:
             rode = g.prepare_convs(names, self.ctx.act_dtype, embed=embed, inputs=inputs)
-            if db2 is not None:
+            if db1 is not None:
+                g.trunk_frag, g.dblock2_frag, g.dblock1_frag = O.fragments_batch(self.ctx, trunk, rf, dblock2=db2, dblock1=db1)
+            elif db2 is not None:
                 g.trunk_frag, g.dblock2_frag = O.fragments_batch(self.ctx, trunk, rf, dblock2=db2)
             elif trunk or rf:
                 g.trunk_frag = O.fragments_batch(self.ctx, trunk, rf)

@@ -309,11 +309,22 @@ int rcgan_fragments_prepare(rcgan_ctx* ctx, const void* const* trunk_prepared, v
 int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
                                     const void* const* prepared, void* const* frags, const void* conv2_prepared,
                                     const void* shortcut_prepared, void* dblock2_frag) {
+  return rcgan_fragments_prepare_dblocks(ctx, trunk_prepared, trunk_frag, n, descs, prepared, frags, conv2_prepared, shortcut_prepared, dblock2_frag,
+                                         nullptr, nullptr);
+}
+
+// ... and the copy the 32x32 input block's fused forward reads (conv_dblock1.hip; rcgan_dblock1_fragment_bytes; one item):
+// block1_conv2_prepared = D.Block.1.Conv2's prepared filter under RCGAN_CONV_OUT_MEANPOOL2.  Both NULL: rcgan_fragments_prepare_dblock2.
+int rcgan_fragments_prepare_dblocks(rcgan_ctx* ctx, const void* const* trunk_prepared, void* trunk_frag, int n, const rcgan_conv_desc* descs,
+                                    const void* const* prepared, void* const* frags, const void* conv2_prepared,
+                                    const void* shortcut_prepared, void* dblock2_frag, const void* block1_conv2_prepared, void* dblock1_frag) {
   if (!ctx) return RCGAN_EINVALID_ARG;
+  RC_REQUIRE(ctx, (block1_conv2_prepared != nullptr) == (dblock1_frag != nullptr), "the input block's copy needs its prepared filter and a destination");
   RC_REQUIRE(ctx, n >= 0 && n <= 12 && (n == 0 || (descs && prepared && frags)) && (!trunk_prepared || trunk_frag), "bad arguments");
   RC_REQUIRE(ctx, (conv2_prepared != nullptr) == (dblock2_frag != nullptr) && (shortcut_prepared != nullptr) == (dblock2_frag != nullptr),
              "the down block's copies need both prepared filters and a destination");
-  RC_REQUIRE(ctx, (dblock2_frag ? DB2_FRAG_ITEMS : 0) + (trunk_prepared ? 16 : 0) + 2 * n <= (int)(sizeof(FragBatch::it) / sizeof(FragItem)),
+  RC_REQUIRE(ctx, (dblock2_frag ? DB2_FRAG_ITEMS : 0) + (dblock1_frag ? DB1_FRAG_ITEMS : 0) + (trunk_prepared ? 16 : 0) + 2 * n <=
+                      (int)(sizeof(FragBatch::it) / sizeof(FragItem)),
              "more fragment items than one launch holds");
   FragBatch b;
   int m = 0, maxchunks = 0;
@@ -326,6 +337,12 @@ int rcgan_fragments_prepare_dblock2(rcgan_ctx* ctx, const void* const* trunk_pre
                        (bf16_t*)dblock2_frag, b.it);
     m = DB2_FRAG_ITEMS;
     maxchunks = b.it[0].chunks;
+  }
+  if (dblock1_frag) {
+    const rcgan_conv_desc d2 = {1, 32, 32, 128, 128, 3, 3, 1, RCGAN_H16, RCGAN_CONV_OUT_MEANPOOL2};
+    dblock1_frag_items((const bf16_t*)block1_conv2_prepared + mfma_prepared_sum_fwd(&d2), (bf16_t*)dblock1_frag, b.it + m);
+    if (b.it[m].chunks > maxchunks) maxchunks = b.it[m].chunks;
+    m += DB1_FRAG_ITEMS;
   }
   if (trunk_prepared) {
     const long elems = 9L * 128 * 128;

@@ -36,6 +36,18 @@ __device__ __forceinline__ void rf_mfma_v(f32x4_t& acc, const i32x4_t& w, const 
 __device__ __forceinline__ void rf_mfma_a0(f32x4_t& acc, const i32x4_t& w, const bf16x8_t& x) {
   asm volatile(RF_MFMA " %0, %1, %2, 0" : "=v"(acc) : "a"(w), "v"(x) : "memory");
 }
+// ... the same where the operand registers die with this instruction (conv_dblock1.hip): early clobber, vDst must not be given SrcA's or SrcB's
+__device__ __forceinline__ void rf_mfma_a0e(f32x4_t& acc, const i32x4_t& w, const bf16x8_t& x) {
+  asm volatile(RF_MFMA " %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(x) : "memory");
+}
+// C = 0 with both operands in VGPRs: the one-MFMA image-end products of a kernel whose AccVGPRs hold a filter stream in flight (a builtin
+// MFMA lets the compiler put its result in AccVGPRs, and it moves what it believes lives there out of the way -- before the loads land).
+// The operands may come straight out of vector ALU instructions the compiler is free to place directly in front of this statement, and
+// its hazard recogniser does not look inside: the wait states sit in the statement itself (without them the first product of a tile
+// came out wrong).
+__device__ __forceinline__ void rf_mfma_vv0(f32x4_t& acc, const bf16x8_t& w, const bf16x8_t& x) {
+  asm volatile("s_nop 4\n\t" RF_MFMA " %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(x) : "memory");
+}
 __device__ __forceinline__ void rf_lds_read(bf16x8_t& dst, unsigned lds_byte_addr) {
   asm volatile("ds_read_b128 %0, %1" : "=v"(dst) : "v"(lds_byte_addr) : "memory");
 }
@@ -67,4 +79,13 @@ inline void dblock2_frag_items(const bf16_t* conv2_sum_fwd, const bf16_t* shortc
   it[1] = FragItem{shortcut_fwd, frag + DB2_FRAG_CONV2, 128, 2, 4, 1, (int)(DB2_FRAG_SHORT / 8)};
   it[2] = FragItem{conv2_sum_bwd, frag + DB2_FRAG_CONV2_BWD, 512, 2, 16, 1, (int)(DB2_FRAG_CONV2 / 8)};
   it[3] = FragItem{shortcut_rot, frag + DB2_FRAG_SHORT_BWD, 128, 2, 4, 1, (int)(DB2_FRAG_SHORT / 8)};
+}
+
+// The input block's fused forward (conv_dblock1.hip) reads one copy: [Conv2 summed filters: 4 blocks of 32 rows][64 K-steps][2 tiles], the
+// layout of the down block's first item.  (Its Conv1 and shortcut rows, [128][32], are read where conv_image.hip's preparation leaves them:
+// the 16 rows of a fragment are one contiguous KiB there already.)
+constexpr long DB1_FRAG_ELEMS = 16L * 128 * 128;
+constexpr int DB1_FRAG_ITEMS = 1;
+inline void dblock1_frag_items(const bf16_t* conv2_sum_fwd, bf16_t* frag, FragItem* it) {
+  it[0] = FragItem{conv2_sum_fwd, frag, 2048, 2, 64, 1, (int)(DB1_FRAG_ELEMS / 8)};
 }

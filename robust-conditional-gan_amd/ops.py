@@ -203,12 +203,14 @@ def fragment_requests(ctx, trunk, rf):
     return tf, reqs
 
 
-def fragments_batch(ctx, trunk, rf, dblock2=None):
+def fragments_batch(ctx, trunk, rf, dblock2=None, dblock1=None):
     """ONE launch writes every fragment-major filter copy of a step (rcgan_fragments_prepare): trunk = the 8x8 stage's eight Weights in
     forward order (or None) -> returns its fragment buffer (ops.d_trunk(frag=...)); rf = [(Weight, desc)] of the layers the
     register-filter kernel takes -> each Weight gets .rf_frag.  All filters must be prepared already (prepare_batch).
     dblock2 = (Weight Conv2, Weight Shortcut) of the 16x16 down block: the same launch also writes the copies its fused forward and
-    its fused data gradient read, two each (ops.d_block2) -> returns (trunk buffer, down-block buffer)."""
+    its fused data gradient read, two each (ops.d_block2) -> returns (trunk buffer, down-block buffer).
+    dblock1 = Weight Conv2 of the 32x32 input block: and the copy its fused forward reads (ops.d_block1) -> returns (trunk buffer,
+    down-block buffer or None, input-block buffer)."""
     tp = tf = None
     if trunk:
         tdesc = L.ConvDesc(1, 8, 8, 128, 128, 3, 3, 1, ctx.act_dtype, L.CONV_IN_RELU)
@@ -223,12 +225,21 @@ def fragments_batch(ctx, trunk, rf, dblock2=None):
         nb = ctx.lib.rcgan_conv_rf_fragment_bytes(C.byref(d))
         w.rf_frag = DT(ctx.arena.alloc(nb), (nb,), "u8", ctx.arena.buf)
         frags.append(w.rf_frag.ptr)
+    p2 = ps = df = None
     if dblock2 is not None:
         w2, ws = dblock2
         p2 = w2.prepared(L.ConvDesc(1, 8, 8, 128, 128, 3, 3, 1, ctx.act_dtype, L.CONV_OUT_MEANPOOL2))
         ps = ws.prepared(L.ConvDesc(1, 8, 8, 128, 128, 1, 1, 1, ctx.act_dtype, 0))
         nb = ctx.lib.rcgan_dblock2_fragment_bytes()
         df = DT(ctx.arena.alloc(nb), (nb,), "u8", ctx.arena.buf)
+    if dblock1 is not None:
+        p1 = dblock1.prepared(L.ConvDesc(1, 8, 8, 128, 128, 3, 3, 1, ctx.act_dtype, L.CONV_OUT_MEANPOOL2))
+        nb = ctx.lib.rcgan_dblock1_fragment_bytes()
+        d1f = DT(ctx.arena.alloc(nb), (nb,), "u8", ctx.arena.buf)
+        ctx.check(ctx.lib.rcgan_fragments_prepare_dblocks(ctx.h, tp, _p(tf), n, descs, preps, (C.c_void_p * max(n, 1))(*frags),
+                                                          _p(p2), _p(ps), _p(df), _p(p1), _p(d1f)))
+        return tf, df, d1f
+    if dblock2 is not None:
         ctx.check(ctx.lib.rcgan_fragments_prepare_dblock2(ctx.h, tp, _p(tf), n, descs, preps, (C.c_void_p * max(n, 1))(*frags),
                                                           _p(p2), _p(ps), _p(df)))
         return tf, df
@@ -618,6 +629,41 @@ def d_block2(ctx, x, ws, bs, w1, b1, w2, b2, frag, _saved=None):
 
 # ... and its data gradient as one launch in place of the four backward entries' (conv_dblock2_bwd.hip).  Read once; 0: the four entries.
 FUSED_DBLOCK2_BWD = os.environ.get("RCGAN_FUSED_DBLOCK2_BWD", "1") != "0"
+
+# The 32x32 input block's forward as one launch (conv_dblock1.hip).  Read once; 0: the three launches (the A/B, the tests' reference side).
+FUSED_DBLOCK1 = os.environ.get("RCGAN_FUSED_DBLOCK1", "1") != "0"
+
+
+def d_block1_ok(ctx, x, frag):
+    """rcgan_dblock1_ok for D.Block.1 on x: [n, 32, 32, 3] 16-bit images and the block's fragment copy (frag:
+    fragments_batch(dblock1=...)) written for this step's weights."""
+    if not FUSED_DBLOCK1 or frag is None or len(x.shape) != 4 or x.dtype == L.F32:
+        return False
+    n, h, w, c = x.shape
+    d = L.ConvDesc(n, h, w, c, 128, 3, 3, 1, x.dtype, 0)
+    return bool(ctx.lib.rcgan_dblock1_ok(C.byref(d), _p(frag)))
+
+
+def d_block1(ctx, x, ws, bs, w1, b1, w2, b2, frag, pooled=None, _saved=None):
+    """D.Block.1 of the CIFAR discriminator (gan_resnet.py:331-353), forward, as ONE launch (rcgan_dblock1_fwd):
+    y = Shortcut(meanpool2(x)) + ConvMeanPool(relu(Conv1(x))) with the 16-bit rounding points and the bits of the three launches it
+    replaces.  pooled: meanpool2(x) where the step has it already (the critic step's input rider) -- the launch then stores no pooled
+    image; else it stores the one it forms, and the meanpool2 launch disappears too.  The ops those launches belong to (meanpool2,
+    conv2d, conv2d, conv2d_meanpool) are each told their output exists already and record their backward entries as usual."""
+    n = x.shape[0]
+    d = L.ConvDesc(n, 32, 32, 3, 128, 3, 3, 1, x.dtype, 0)
+    ds = L.ConvDesc(n, 16, 16, 3, 128, 1, 1, 1, x.dtype, 0)
+    h = ctx.empty((n, 32, 32, 128), x.dtype)
+    y = ctx.empty((n, 16, 16, 128), x.dtype)
+    xp = ctx.empty((n, 16, 16, 3), x.dtype) if pooled is None else None
+    ctx.check(ctx.lib.rcgan_dblock1_fwd(ctx.h, C.byref(d), _p(x), _p(w1.prepared(d)), _p(ws.prepared(ds)), _p(frag), _p(b1), _p(b2), _p(bs),
+                                        _p(h), _p(xp), _p(y)))
+    xp = pooled if pooled is not None else meanpool2(ctx, x, _done=xp)
+    t = conv2d(ctx, xp, ws, bs, 1, _done=y)
+    h = conv2d(ctx, x, w1, b1, 3, _done=h)
+    if _saved is not None:
+        _saved += [h, xp]           # what the backward entries hold on to, for whoever wants to look (the tests)
+    return conv2d_meanpool(ctx, h, w2, b2, in_relu=True, accumulate_into=t, _done=True)
 
 
 def d_trunk_ok(ctx, x):
