@@ -611,6 +611,52 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
                             float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
                             float* db_e, void* ws, size_t ws_bytes);
 int rcgan_head_flush(rcgan_ctx* ctx);
+
+/* ---- LeCam regulariser of the critic's outputs (Tseng et al., "Regularizing Generative Adversarial Networks under Limited Data",
+ * CVPR 2021; the two-sided form) ----------------------------------------------------------------------------------------------------
+ * Critic cost L_D' = L_D + lambda R,  R = E_real[(D(x, y) - a_F)^2] + E_fake[(D(G(z), y) - a_R)^2], with a_R / a_F exponential moving
+ * averages (decay gamma) of the critic's mean output on the real / the fake rows, constants for differentiation.  Each part's
+ * expectation is taken exactly as that part's loss term takes it: per logit x the term of loss_kind(x) becomes
+ *     t = loss_kind(x) + lambda (x - a)^2,      dt/dx = loss_kind'(x) + 2 lambda (x - a)            (x - a: one fp32 subtraction)
+ * and is weighted as before -- the logit at the row's label for a labelled part, mean_rows sum_l w[s,l] (.) for a weight-row part
+ * (negative weights included), so every gradient the loss has, the term has (dlogit, dfeat, dx, the parameter gradients, and
+ * dwts = gw (loss_kind(x) + lambda (x - a)^2) / rows, gw = weight * gradient scale).
+ * rcgan_loss_reg -- all pointers DEVICE, read by the KERNEL: a replayed graph sees the values of the moment it runs:
+ *   weight    lambda
+ *   anchor_a  the anchor of part a (of the only part of rcgan_loss_reg_fwd_bwd); anchor_b that of part b (head only)
+ *   gate      the term is on iff *gate > 0 (NULL: always on); off, it contributes exactly nothing to any output
+ *   reg_acc   optional: += the unweighted R of the call (part a + part b, each the mean over its rows); loss_acc += weight * (L + lambda R)
+ * reg == NULL, lambda == 0 or a closed gate give the bits of rcgan_loss_fwd_bwd / rcgan_proj_head_fwd_bwd on every output, and those
+ * two entry points are the calls below with reg == NULL.  A non-NULL reg needs a finite lambda >= 0, non-NULL 4-byte-aligned anchors
+ * (anchor_b only where part b has rows) and 4-byte-aligned gate / reg_acc: anything else is RCGAN_EINVALID_ARG before any launch.
+ * The head with reg_acc uses max(256, 2 * cdiv(n, 4)) floats of workspace tail (rcgan_proj_head_workspace_bytes is still enough).
+ *
+ * rcgan_lecam_update: the controller, one single-workgroup launch after the head.  logits is fp32 [rows_a + rows_b][ld]; part a is
+ * rows [0, rows_a), part b the rest.  The score of a row is the logit itself (ld == 1, neither labels nor weights), the logit at its
+ * label (a label outside [0, ld) makes the row count as zero and read nothing; it stays in the denominator), or sum_l w[s,l] logit[s,l]
+ * (weight rows [rows][ld]).  m_a, m_b = the batch means of the scores: fp32 sums in a fixed order, no atomics.
+ * state: DEVICE float[8] = {a_R, a_F, updates, mean_real_last, mean_fake_last, skipped, 0, 0}; part a holds the real rows.  A call:
+ *   m_a or m_b not finite:  skipped += 1, nothing else changes;
+ *   updates == 0:           a_R = m_a, a_F = m_b;
+ *   otherwise:              a_R = decay * a_R + (1 - decay) * m_a (two products, one sum, in fp32), a_F likewise from m_b;
+ *   then mean_real_last = m_a, mean_fake_last = m_b, updates += 1.
+ * The real part's loss is pulled towards a_F (anchor = state + 1), the fake part's towards a_R (state + 0); gate = state + 2.
+ * rows_a, rows_b >= 1, ld >= 1, logits / state non-NULL, every pointer 4-byte aligned, per part at most one of labels / weights and
+ * exactly one when ld > 1, decay in [0, 1]: anything else is RCGAN_EINVALID_ARG and launches nothing. */
+typedef struct {
+  float weight;
+  const float* anchor_a; const float* anchor_b;
+  const float* gate;
+  float* reg_acc;
+} rcgan_loss_reg;
+int rcgan_loss_reg_fwd_bwd(rcgan_ctx* ctx, int kind, int rows, int cols, const float* x, const float* wts, float weight,
+                           float* loss_acc, float* dlogit, float* dwts, const rcgan_loss_reg* reg);
+int rcgan_proj_head_reg_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const float* feat, const float* w_out, const float* sigma_out,
+                                const float* b_out, const float* table, const float* w_e, const float* sigma_e, const float* b_e,
+                                float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
+                                float* db_e, void* ws, size_t ws_bytes, const rcgan_loss_reg* reg);
+int rcgan_lecam_update(rcgan_ctx* ctx, int rows_a, int rows_b, const float* logits, int ld, const int32_t* labels_a, const float* wts_a,
+                       const int32_t* labels_b, const float* wts_b, float* state, float decay);
 /* (bce_onehot: one workgroup, any rows x cols, labels in [0, cols); loss_acc and dx may be NULL.) */
 int rcgan_bce_onehot_fwd_bwd(rcgan_ctx* ctx, int rows, int cols, const float* x, const int32_t* labels,
                              float weight, float* loss_acc, float* dx);

@@ -72,6 +72,11 @@ class HeadDesc(C.Structure):
                 ("E_pre", C.c_void_p), ("defer_ws", C.c_void_p), ("defer_ws_bytes", C.c_size_t)]
 
 
+class LossReg(C.Structure):
+    """rcgan_loss_reg: the LeCam regulariser's arguments of the two regularised loss entry points (device pointers)."""
+    _fields_ = [("weight", C.c_float), ("anchor_a", C.c_void_p), ("anchor_b", C.c_void_p), ("gate", C.c_void_p), ("reg_acc", C.c_void_p)]
+
+
 class EmbedDesc(C.Structure):
     _fields_ = [("v", C.c_int), ("e_dim", C.c_int), ("d", C.c_int),
                 ("table", C.c_void_p), ("w_e", C.c_void_p), ("sigma_e", C.c_void_p), ("b_e", C.c_void_p), ("E", C.c_void_p)]
@@ -242,6 +247,9 @@ SIGNATURES = {
     "rcgan_diffaugment_gated_fwd": (I, [P, I, I, I, I, I, P, P, P, P, P, P, P]),
     "rcgan_diffaugment_sampled_bwd": (I, [P, I, I, I, I, P, P, P, P, I]),
     "rcgan_ada_update": (I, [P, I, P, I, P, P, F, F, I]),
+    "rcgan_loss_reg_fwd_bwd": (I, [P, I, I, I, P, P, F, P, P, P, C.POINTER(LossReg)]),
+    "rcgan_proj_head_reg_fwd_bwd": (I, [P, C.POINTER(HeadDesc)] + [P] * 16 + [P, SZ, C.POINTER(LossReg)]),
+    "rcgan_lecam_update": (I, [P, I, I, P, I, P, P, P, P, P, F]),
     "rcgan_class_moments_bytes": (SZ, [I, I]),
     "rcgan_class_moments_accum": (I, [P, I, I, I, P, P, P]),
     "rcgan_knn_radius": (I, [P, I, I, I, I, P, P, P]),

@@ -187,6 +187,22 @@ def check_ada(ada_target, ada_images, ada_interval, ada_p_init, diffaugment, wor
     return target, images, int(ada_interval), p_init
 
 
+def check_lecam(lecam, lecam_decay, world_size=1):
+    """The LeCam arguments of CifarRCGAN / --lecam*: (Tseng et al., CVPR 2021; DESIGN.md 3, "LeCam regulariser").  lecam = 0 is off; on,
+    it is the weight lambda >= 0 of R = E_real[(D - a_F)^2] + E_fake[(D - a_R)^2] in the critic cost.  lecam_decay in [0, 1): the decay
+    of the two moving averages.  Raises ValueError before any GPU work; returns (lambda, decay) as floats."""
+    lam, decay = float(lecam), float(lecam_decay)
+    if not (np.isfinite(lam) and lam >= 0.0):
+        raise ValueError("lecam must be finite and >= 0 (0 = off), got %r" % (lecam,))
+    if not (0.0 <= decay < 1.0):
+        raise ValueError("lecam_decay must lie in [0, 1), got %r" % (lecam_decay,))
+    if lam != 0.0 and world_size > 1:
+        raise ValueError("lecam = %r with world_size = %d: every rank would anchor its critic to the mean outputs of its own shard; "
+                         "the all-reduce of the two batch means that would fix it is not implemented, and there is no multi-GPU "
+                         "machine to test it on" % (lecam, world_size))
+    return lam, decay
+
+
 def confusion_logits_initial(confuse_init, confuse_init_diag, rs, n_classes=VOCAB_SIZE):
     """gan_resnet.py:499-520 with VOCAB_SIZE = n_classes (the reference's special case of 10 classes kept for K = 10 only)."""
     K = n_classes
@@ -440,7 +456,7 @@ def _head_weights(update_collection=None):
     return w_out, b_out, table, w_e, b_e
 
 
-def Discriminator_head(features, parts, weight, loss_acc, update_collection=None, logits=None):
+def Discriminator_head(features, parts, weight, loss_acc, update_collection=None, logits=None, reg=None):
     """The tail of Discriminator (D.Output, gan_resnet.py:408-411), Discriminator_projection (:414-421), the projection
     logit (:588; every label's logit :654-660) and the loss terms built on it (:604-606, :647, :673-684, :751-773) as ONE
     launch with all their gradients (ops.proj_head).  update_collection: that of D.Output's spectral norm (the projection's
@@ -448,7 +464,7 @@ def Discriminator_head(features, parts, weight, loss_acc, update_collection=None
     g = Graph.current
     w_out, b_out, table, w_e, b_e = _head_weights(update_collection)
     # (the label embeddings E = table @ W_e / sigma + b_e of this step, if _prepare_all let them ride in its launch)
-    O.proj_head(g.ctx, features, w_out, b_out, table, w_e, b_e, parts, weight, loss_acc, logits=logits, E_pre=getattr(g, "head_E", None))
+    O.proj_head(g.ctx, features, w_out, b_out, table, w_e, b_e, parts, weight, loss_acc, logits=logits, E_pre=getattr(g, "head_E", None), reg=reg)
 
 
 def perm_classifier(x, perm_type='linear'):
@@ -477,9 +493,12 @@ class CifarRCGAN:
                  device=0, use_graphs=True, device_rng=True, arena_bytes=None, world_size=1, rank=0,
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
                  grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE,
-                 diffaugment="", ada_target=0.0, ada_images=500000, ada_interval=4, ada_p_init=0.0):
+                 diffaugment="", ada_target=0.0, ada_images=500000, ada_interval=4, ada_p_init=0.0, lecam=0.0, lecam_decay=0.99):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # the critic's outputs anchored to moving averages of the other side's ("LeCam regulariser"); weight 0 = off.
+        # Checked before any context exists.
+        self.lecam, self.lecam_decay = check_lecam(lecam, lecam_decay, world_size)
         # the probability of every DiffAugment transform steered by r = E[sign D(real)] ("Adaptive augmentation
         # probability"); target 0 = off.  Checked before any context exists.
         self.ada_target, self.ada_images, self.ada_interval, self.ada_p_init = check_ada(
@@ -668,8 +687,14 @@ class CifarRCGAN:
         # the controller of the augmentation probability lives on the device, inside the captured steps (rcgan_ada_update):
         # {p, sign_sum, image_count, steps, r_last, updates, 0, 0}.  Part of state_dict ("_ada_state").
         self.ada_state = (torch.tensor([self.ada_p_init] + [0.0] * 7, dtype=torch.float32, device=ctx.device) if self.ada else None)
-        # the logits rcgan_ada_update reads after the fused head (which otherwise keeps them on chip): head_logits if set, else this
-        self.ada_logits = P((2 * B, self.K), f32, fill=0.0) if (self.ada and self.fused_head) else None
+        # the anchors of the LeCam regulariser, on the device for the same reason (rcgan_lecam_update):
+        # {a_R, a_F, updates, mean_real_last, mean_fake_last, skipped, 0, 0}.  Part of state_dict ("_lecam_state").  lecam_R: the
+        # unweighted R of the last critic step, a scalar behind the gradient slab (cleared with it).
+        self.lecam_state = torch.zeros(8, dtype=torch.float32, device=ctx.device) if self.lecam else None
+        self.lecam_R = self.PD.scalar(1) if self.lecam else None
+        # the logits rcgan_ada_update and rcgan_lecam_update read after the fused head (which otherwise keeps them on chip):
+        # head_logits if set, else this one buffer, shared by the two options
+        self.ada_logits = P((2 * B, self.K), f32, fill=0.0) if ((self.ada or self.lecam) and self.fused_head) else None
         # (round 6) The critic steps' generator forwards on a SECOND stream.  The generator does not change during the N_CRITIC critic
         # updates of an iteration (gan_resnet.py:928-947), so step k + 1's Generator() call can run while critic step k does: a critic
         # step is a chain of ~26 small-grid launches that leaves half the chip idle most of the time, the generator forward is the
@@ -805,6 +830,38 @@ class CifarRCGAN:
             return
         ctx.check(ctx.lib.rcgan_ada_update(ctx.h, self.B, C.c_void_p(logits.ptr), ld, None if labels is None else C.c_void_p(labels.ptr),
                                            C.c_void_p(self.ada_state.data_ptr()), self.ada_target, self.ada_images, self.ada_interval))
+
+    def _lecam_reg(self, part_a, part_b=None):
+        """The regulariser's arguments of a loss launch whose part a / part b are the "real" or the "fake" rows: the real part is pulled
+        towards a_F, the fake part towards a_R, gated by the update count.  None with the option off and in forward-only evaluations
+        (eval_d_cost is the plain dev cost)."""
+        if not self.lecam or not self.ctx.recording:
+            return None
+        base = self.lecam_state.data_ptr()
+        anchor = {"real": base + 4, "fake": base, None: None}
+        return O.lecam_reg(self.lecam, anchor[part_a], anchor[part_b], base + 8, self.lecam_R.ptr)
+
+    def _lecam_update(self, logits, ld, part_a, part_b):
+        """One controller launch behind the step's loss launches (use, then update): the anchors take this step's two batch means.
+        logits: fp32 [2B, ld], real rows first; part_a / part_b: (labels, wts) of the real / the fake rows, as their loss terms have
+        them.  Recorded steps only."""
+        ctx = self.ctx
+        if not self.lecam or not ctx.recording:
+            return
+        ptr = lambda t: None if t is None else C.c_void_p(t.ptr)
+        ctx.check(ctx.lib.rcgan_lecam_update(ctx.h, self.B, self.B, C.c_void_p(logits.ptr), ld, ptr(part_a[0]), ptr(part_a[1]),
+                                             ptr(part_b[0]), ptr(part_b[1]), C.c_void_p(self.lecam_state.data_ptr()), self.lecam_decay))
+
+    def _lecam_update_all_labels(self, feat, psi, E, part_a, part_b):
+        """The op-by-op routes whose two parts have logits of different shapes (rcgan-u, unbiased): every label's logit of all 2B rows
+        once more, for the controller alone (one extra forward launch on a route kept for comparison)."""
+        ctx = self.ctx
+        if not self.lecam or not ctx.recording:
+            return
+        buf = ctx.empty((2 * self.B, self.K), L.F32)
+        ctx.check(ctx.lib.rcgan_proj_logit_all_fwd(ctx.h, 2 * self.B, feat.shape[1], self.K, C.c_void_p(feat.ptr), C.c_void_p(psi.ptr),
+                                                   C.c_void_p(E.ptr), C.c_void_p(buf.ptr)))
+        self._lecam_update(buf, self.K, part_a, part_b)
 
     def _sn_entries(self, conv_update, proj_update):
         ents = []
@@ -969,9 +1026,11 @@ class CifarRCGAN:
             else:                              # biased / rcgan (:585-606): labels_all = [labels ; labels_random | labels_biased]
                 parts = [(B, L.LOSS_HINGE_REAL, lab_r, None), (B, L.LOSS_HINGE_FAKE, lab_f, None)]
             head_logits = self.head_logits if self.head_logits is not None else self.ada_logits
-            Discriminator_head(feat, parts, w, self.loss_d, update_collection=None, logits=head_logits)
+            Discriminator_head(feat, parts, w, self.loss_d, update_collection=None, logits=head_logits, reg=self._lecam_reg("real", "fake"))
             # real rows [0, B) of the [2B, K] logits at the row's given (noisy) label: the only non-zero column of a labelled part
             self._ada_update(head_logits, self.K, lab_r if self.alg in ("biased", "rcgan") else inp["labels"])
+            # both parts' scores formed as their loss terms form them (the parts' own labels / weight rows)
+            self._lecam_update(head_logits, self.K, parts[0][2:], parts[1][2:])
         elif self.alg == "rcgan-u":
             feat_a, wgan_a = Discriminator(d_in, None, update_collection=None)
             feat, wgan = O.rows(ctx, feat_a, 0, B), O.rows(ctx, wgan_a, 0, B)
@@ -982,26 +1041,29 @@ class CifarRCGAN:
             E = Discriminator_projection(inp["arange"], update_collection=None)
             disc_fake = O.proj_logit_all(ctx, feat_f, wgan_f, E)                         # :654-660
             y_conf = O.gather_rows(ctx, self.confusion_matrix(), inp["labels_random"], B)   # :682-683
-            O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d, wts=y_conf)   # :673,684
-            O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real, w, self.loss_d)               # :674
+            O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d, wts=y_conf, reg=self._lecam_reg("fake"))   # :673,684
+            O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real, w, self.loss_d, reg=self._lecam_reg("real"))               # :674
+            self._lecam_update_all_labels(feat_a, wgan_a, E, (inp["labels"], None), (None, y_conf))
         else:
             feat, wgan = Discriminator(d_in, None, update_collection=None)               # :584
             if self.alg in ("biased", "rcgan"):
                 emb = Discriminator_projection(inp["labels_all"], update_collection=None)    # :585
                 disc_all = O.proj_logit(ctx, feat, wgan, emb)                            # :588
                 self._ada_update(disc_all, 1, None)                                      # (rows 0 .. B: the real ones)
-                O.loss_term(ctx, L.LOSS_HINGE_REAL, O.rows(ctx, disc_all, 0, B), w, self.loss_d)       # :604
-                O.loss_term(ctx, L.LOSS_HINGE_FAKE, O.rows(ctx, disc_all, B, 2 * B), w, self.loss_d)   # :605
+                O.loss_term(ctx, L.LOSS_HINGE_REAL, O.rows(ctx, disc_all, 0, B), w, self.loss_d, reg=self._lecam_reg("real"))       # :604
+                O.loss_term(ctx, L.LOSS_HINGE_FAKE, O.rows(ctx, disc_all, B, 2 * B), w, self.loss_d, reg=self._lecam_reg("fake"))   # :605
+                self._lecam_update(disc_all, 1, (None, None), (None, None))
             else:   # unbiased (:613-648): every label's projection once, real loss weighted by C^-1 rows
                 E = Discriminator_projection(inp["arange"], update_collection=None)
                 feat_r, wgan_r = O.rows(ctx, feat, 0, B), O.rows(ctx, wgan, 0, B)
                 feat_f, wgan_f = O.rows(ctx, feat, B, 2 * B), O.rows(ctx, wgan, B, 2 * B)
                 disc_real_all = O.proj_logit_all(ctx, feat_r, wgan_r, E)                 # [B,10]
                 self._ada_update(disc_real_all, self.K, inp["labels"])
-                O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real_all, w, self.loss_d, wts=inp["inv_weights"])   # :647
+                O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real_all, w, self.loss_d, wts=inp["inv_weights"], reg=self._lecam_reg("real"))   # :647
                 emb_f = Discriminator_projection(inp["labels_random"], update_collection=None)
                 disc_fake = O.proj_logit(ctx, feat_f, wgan_f, emb_f)
-                O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d)           # :639,648
+                O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d, reg=self._lecam_reg("fake"))           # :639,648
+                self._lecam_update_all_labels(feat, wgan, E, (None, inp["inv_weights"]), (inp["labels_random"], None))
         if self.perm:
             logits = perm_classifier(real, self.perm_type)                               # :692
             O.bce_onehot_term(ctx, logits, inp["labels"], 1.0, self.loss_d)                          # :693-695
@@ -1360,6 +1422,17 @@ class CifarRCGAN:
         s = self.ada_state.cpu().numpy()
         return dict(p=float(s[0]), r_last=float(s[4]), updates=int(s[5]))
 
+    def lecam_report(self):
+        """{a_real, a_fake, mean_real, mean_fake, reg, updates, skipped} of the LeCam regulariser as it stands on the stream now
+        (synchronises): the anchors, the last update's batch means, the unweighted R of the last critic step (0 while the gate was
+        closed; a scalar of the step, so a forward-only eval_d_cost since then has cleared it), and the counts of updates and of updates skipped for a non-finite mean."""
+        if self.lecam_state is None:
+            return dict(a_real=None, a_fake=None, mean_real=None, mean_fake=None, reg=None, updates=0, skipped=0)
+        self.ctx.sync()
+        s = self.lecam_state.cpu().numpy()
+        return dict(a_real=float(s[0]), a_fake=float(s[1]), mean_real=float(s[3]), mean_fake=float(s[4]),
+                    reg=float(self.ctx.download(self.lecam_R)[0]), updates=int(s[2]), skipped=int(s[5]))
+
     def losses(self):
         ctx = self.ctx
         return float(ctx.download(self.loss_d)[0]), float(ctx.download(self.loss_g)[0])
@@ -1433,6 +1506,9 @@ class CifarRCGAN:
         if self.ada_state is not None:
             self.ctx.sync()
             out["_ada_state"] = self.ada_state.cpu().numpy().astype(np.float32)
+        if self.lecam_state is not None:
+            self.ctx.sync()
+            out["_lecam_state"] = self.lecam_state.cpu().numpy().astype(np.float32)
         out.update(adam_power_tensors(opts))
         return out
 
@@ -1454,6 +1530,9 @@ class CifarRCGAN:
         if self.ada_state is not None and "_ada_state" in sd:
             with torch.cuda.stream(self.ctx.stream):
                 self.ada_state.copy_(torch.from_numpy(np.asarray(sd["_ada_state"], np.float32).reshape(8)))
+        if self.lecam_state is not None and "_lecam_state" in sd:
+            with torch.cuda.stream(self.ctx.stream):
+                self.lecam_state.copy_(torch.from_numpy(np.asarray(sd["_lecam_state"], np.float32).reshape(8)))
         if "_iteration" in sd:
             self.iteration = int(np.asarray(sd["_iteration"]).reshape(-1)[0])
         ctx = self.ctx

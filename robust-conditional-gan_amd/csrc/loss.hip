@@ -3,6 +3,7 @@
 //   :654-660, :682-684, :751-760, :773 (losses), :522 (C = softmax(logits)), :692-695/:781-784 (perm BCE);
 //   mnist/model.py:135-145, 199-221, 679-685.
 // All of this is a few KB of fp32: each op is one small launch built on wavefront reductions.
+#include <cmath>
 #include "common.h"
 #include "small_gemm.h"
 
@@ -127,24 +128,45 @@ __device__ __forceinline__ void loss_term(int kind, float x, float* t, float* d)
 // gs_host * (*gs_dev): the gradient (loss) scale of 16-bit activations -- applied to the gradients only, the loss value stays unscaled
 __device__ __forceinline__ float grad_scale_of(float gs_host, const float* gs_dev) { return gs_dev ? gs_host * gs_dev[0] : gs_host; }
 
+// The LeCam regulariser (include/rcgan_hip.h): one more contribution wherever loss_term is consumed, t += lam (x - a)^2 and
+// d += 2 lam (x - a) with a = *anchor[part], under the gate.  A separate kernel parameter: HeadArgs is shared with the riders' translation
+// units.  lam == 0 (also: no descriptor) or a closed gate take no branch that touches t or d, so those calls keep the plain bits.
+struct LossReg { float lam; const float* anchor[2]; const float* gate; float* reg_acc; };
+__device__ __forceinline__ bool loss_reg_on(const LossReg& r) { return r.lam != 0.f && (r.gate ? r.gate[0] > 0.f : true); }
+// -> (x - a)^2, the unweighted term of R
+__device__ __forceinline__ float loss_reg_term(float lam, float an, float x, float* t, float* d) {
+  const float u = x - an, q = u * u;
+  *t += lam * q;
+  *d += 2.f * lam * u;
+  return q;
+}
+
 __global__ __launch_bounds__(256) void loss_kernel(int kind, int rows, int cols, const float* x, const float* wts, float weight,
-                                                    float* loss_acc, float* dlogit, float* dwts, float gs_host, const float* gs_dev) {
+                                                    float* loss_acc, float* dlogit, float* dwts, float gs_host, const float* gs_dev, LossReg r) {
   __shared__ float red[4];
+  const bool on = loss_reg_on(r);
+  const float an = on ? r.anchor[0][0] : 0.f;
   const float gw = weight * grad_scale_of(gs_host, gs_dev);
   const long total = (long)rows * cols;
   const float inv_rows = 1.f / (float)rows;
   const float inv_all = 1.f / (float)total;
-  float acc = 0.f;
+  float acc = 0.f, racc = 0.f;
   for (long i = threadIdx.x; i < total; i += 256) {
     float t, d;
-    loss_term(kind, x[i], &t, &d);
+    const float xi = x[i];
+    loss_term(kind, xi, &t, &d);
     float wf = wts ? wts[i] * inv_rows : inv_all;
+    if (on) racc += loss_reg_term(r.lam, an, xi, &t, &d) * wf;
     acc += t * wf;
     if (dlogit) dlogit[i] = gw * d * wf;
     if (dwts) dwts[i] = gw * t * inv_rows;
   }
   acc = block_sum256(acc, red);
   if (threadIdx.x == 0 && loss_acc) *loss_acc += weight * acc;
+  if (on && r.reg_acc) {                   // (uniform)
+    racc = block_sum256(racc, red);
+    if (threadIdx.x == 0) *r.reg_acc += racc;
+  }
 }
 
 __global__ __launch_bounds__(256) void bce_onehot_kernel(int rows, int cols, const float* x, const int32_t* labels, float weight,
@@ -253,11 +275,11 @@ __global__ __launch_bounds__(256) void head_smallgemm_kernel(SmallGemmArgs g) {
 
 // T: element type of a.x (ignored when a.x is null)
 template <typename T>
-__global__ __launch_bounds__(256) void head_logit_kernel(HeadArgs a, const float* Eg, float* dlg, float* losspart, unsigned* counter) {
+__global__ __launch_bounds__(256) void head_logit_kernel(HeadArgs a, const float* Eg, float* dlg, float* losspart, unsigned* counter, LossReg r) {
   extern __shared__ __attribute__((aligned(16))) float hs[];
   const int n = a.n, d = a.d, v = a.v, vp = v + 1;
   float* E = hs;                    // [v][d]
-  float* red = E + v * d;           // [4]
+  float* red = E + v * d;           // [4] loss, [4] regulariser
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   // one sample per wavefront; everything the sample needs from memory is requested before the first wait
   const int s = blockIdx.x * 4 + wave;
@@ -272,6 +294,8 @@ __global__ __launch_bounds__(256) void head_logit_kernel(HeadArgs a, const float
   float f[HEAD_MAX_D / 64], wo[HEAD_MAX_D / 64], df[HEAD_MAX_D / 64];
   int lab_pre = -1;
   float wt_pre = 0.f;
+  const bool reg_on = loss_reg_on(r);                     // (the gate and the anchor: requested with the sample's other loads)
+  const float an = reg_on ? r.anchor[p][0] : 0.f;
   const T* const xs = (const T*)a.x + (long)(s < n ? s : 0) * a.hw * d;
   const int xcp = (a.hw + HEAD_XC - 1) / HEAD_XC, nxc = xm ? xcp * (d / 128) : 0;
   float xa[HEAD_XC], xb[HEAD_XC];
@@ -320,7 +344,7 @@ __global__ __launch_bounds__(256) void head_logit_kernel(HeadArgs a, const float
   const float bo = a.b_out ? a.b_out[0] : 0.f;
   for (int i = t; i < v * d; i += 256) E[i] = Eg[i];
   __syncthreads();
-  float lacc = 0.f;
+  float lacc = 0.f, racc = 0.f;
   if (s < n) {
     const int lab = P.labels ? lab_pre : -1;
     float ps = 0.f;
@@ -342,6 +366,7 @@ __global__ __launch_bounds__(256) void head_logit_kernel(HeadArgs a, const float
         float tt, dd;
         loss_term(P.kind, x, &tt, &dd);
         const float wf = (P.wts ? __shfl(wt_pre, l) : 1.f) * inv_rows;
+        if (reg_on) racc += loss_reg_term(r.lam, an, x, &tt, &dd) * wf;
         lacc += tt * wf;
         g = gw * dd * wf;
 #pragma unroll
@@ -389,16 +414,25 @@ __global__ __launch_bounds__(256) void head_logit_kernel(HeadArgs a, const float
     }
   }
   // ---- loss: per-workgroup partial, summed in workgroup order by the last arrival (deterministic) -------------------
-  if (lane == 0) red[wave] = lacc;
+  // (the regulariser's unweighted terms the same way, in the gridDim.x floats behind the loss partials, when reg_acc is wanted)
+  const bool want_r = reg_on && r.reg_acc != nullptr;
+  if (lane == 0) { red[wave] = lacc; red[4 + wave] = racc; }
   __syncthreads();
   if (t == 0) {
     __hip_atomic_store(losspart + blockIdx.x, (red[0] + red[1]) + (red[2] + red[3]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (want_r)
+      __hip_atomic_store(losspart + gridDim.x + blockIdx.x, (red[4] + red[5]) + (red[6] + red[7]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const unsigned prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (prev == gridDim.x - 1u) {
       float tot = 0.f;
       for (unsigned w = 0; w < gridDim.x; ++w) tot += __hip_atomic_load(losspart + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (a.loss_acc) *a.loss_acc += a.weight * tot;
+      if (want_r) {
+        float totr = 0.f;
+        for (unsigned w = 0; w < gridDim.x; ++w) totr += __hip_atomic_load(losspart + gridDim.x + w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *r.reg_acc += totr;
+      }
       __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
@@ -433,7 +467,7 @@ __global__ __launch_bounds__(256) void head_wide_embed_kernel(int v, int e, int 
   E[i] = acc * (sigma ? 1.f / sigma[0] : 1.f) + (b ? b[j] : 0.f);
 }
 
-__global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const float* E, float* dlg, float* lossrow) {
+__global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const float* E, float* dlg, float* lossrow, LossReg r, float* regrow) {
   __shared__ float fs[4][HEAD_MAX_D];           // the wavefront's features
   __shared__ float gl[4][64];                   // dlogit of the current 64 labels
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -447,6 +481,9 @@ __global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const 
   const float gw = a.weight * grad_scale_of(a.gs_host, a.gs_dev);
   const float inv_so = a.sigma_out ? 1.f / a.sigma_out[0] : 1.f;
   const float bo = a.b_out ? a.b_out[0] : 0.f;
+  const bool reg_on = loss_reg_on(r);
+  const float an = reg_on ? r.anchor[p][0] : 0.f;
+  float racc = 0.f;                             // this lane's share of the sample's (x - a)^2 terms
   float f[HEAD_MAX_D / 64], wo[HEAD_MAX_D / 64], df[HEAD_MAX_D / 64];
   float ps = 0.f;
 #pragma unroll
@@ -470,12 +507,14 @@ __global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const 
     const float x = wave_sum(dot) + ps;
     float tt, dd;
     loss_term(P.kind, x, &tt, &dd);
+    float rq = 0.f;
+    if (reg_on) rq = loss_reg_term(r.lam, an, x, &tt, &dd);
     const float g = ok ? gw * dd * inv_rows : 0.f;
     if (ok) {
 #pragma unroll
       for (int q = 0; q < HEAD_MAX_D / 64; ++q) { const int j = lane + q * 64; df[q] += j < d ? g * E[(long)lab * d + j] : 0.f; }
     }
-    if (lane == 0 && ok) { lacc = tt * inv_rows; dsl = g; }
+    if (lane == 0 && ok) { lacc = tt * inv_rows; dsl = g; racc = rq * inv_rows; }
     for (int l = lane; l < v; l += 64) {
       dlg[(long)s * vp + l] = l == lab ? g : 0.f;
       if (a.logits) a.logits[(long)s * v + l] = l == lab ? x : 0.f;
@@ -494,6 +533,7 @@ __global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const 
       float tt, dd;
       loss_term(P.kind, x, &tt, &dd);
       const float wf = P.wts[(long)sr * v + l] * inv_rows;
+      if (reg_on) racc += loss_reg_term(r.lam, an, x, &tt, &dd) * wf;
       lacc += tt * wf;
       g = gw * dd * wf;
       dsl += g;
@@ -523,12 +563,13 @@ __global__ __launch_bounds__(256) void head_wide_logit_kernel(HeadArgs a, const 
 #pragma unroll
     for (int q = 0; q < HEAD_MAX_D / 64; ++q) { const int j = lane + q * 64; if (j < d) a.dfeat[(long)s * d + j] = df[q]; }
   }
-  if (lane == 0) { dlg[(long)s * vp + v] = dsum; lossrow[s] = lacc; }
+  if (regrow) racc = wave_sum(racc);
+  if (lane == 0) { dlg[(long)s * vp + v] = dsum; lossrow[s] = lacc; if (regrow) regrow[s] = racc; }
 }
 
 // dE [(v+1)][d] over cdiv((v+1)*d, 256) workgroups (0 when no parameter gradient is wanted) and one last workgroup for db_out / the loss
 __global__ __launch_bounds__(256) void head_wide_de_kernel(int n, int d, int v, const float* dlg, const float* feat, float* dE, float* db_out,
-                                                           const float* lossrow, float* loss_acc, float weight) {
+                                                           const float* lossrow, float* loss_acc, float weight, LossReg r, const float* regrow) {
   const int vp = v + 1;
   if (blockIdx.x == gridDim.x - 1) {
     if (threadIdx.x == 0) {
@@ -536,6 +577,11 @@ __global__ __launch_bounds__(256) void head_wide_de_kernel(int n, int d, int v, 
       for (int s = 0; s < n; ++s) { sb += dlg[(long)s * vp + v]; sl += lossrow[s]; }
       if (db_out) db_out[0] += sb;
       if (loss_acc) *loss_acc += weight * sl;
+      if (regrow && loss_reg_on(r)) {          // (regrow: reg_acc wanted)
+        float sr = 0.f;
+        for (int s = 0; s < n; ++s) sr += regrow[s];
+        *r.reg_acc += sr;
+      }
     }
     return;
   }
@@ -618,6 +664,47 @@ __global__ __launch_bounds__(256) void recover_sum_kernel(int n, const float* te
   if (threadIdx.x == 0) *loss = s;
 }
 
+// The controller of the LeCam anchors (the definition is in include/rcgan_hip.h).  One workgroup: per part a strided loop over the
+// rows (a thread's rows in order, a weight row's labels in order), block_sum256, the state written by thread 0 with ordinary stores.
+struct LecamPart { int rows; const int* labels; const float* wts; };
+__device__ __forceinline__ float lecam_part_mean(const LecamPart P, const float* __restrict__ logits, int ld, float* red) {
+  float part = 0.f;
+  for (int i = threadIdx.x; i < P.rows; i += 256) {
+    const float* row = logits + (size_t)i * ld;
+    if (P.wts) {
+      const float* w = P.wts + (size_t)i * ld;
+      float sc = 0.f;
+#pragma unroll 8
+      for (int l = 0; l < ld; ++l) sc += w[l] * row[l];
+      part += sc;
+    } else {
+      const int c = P.labels ? P.labels[i] : 0;
+      if (c >= 0 && c < ld) part += row[c];              // a label outside the row: the row counts as zero
+    }
+  }
+  return block_sum256(part, red) / (float)P.rows;
+}
+
+__global__ __launch_bounds__(256) void lecam_update_kernel(LecamPart A, LecamPart B, const float* __restrict__ logits, int ld, float* st, float decay) {
+  __shared__ float red[4];
+  const float ma = lecam_part_mean(A, logits, ld, red);
+  const float mb = lecam_part_mean(B, logits + (size_t)A.rows * ld, ld, red);
+  if (threadIdx.x != 0) return;
+  if (!(fabsf(ma) < INFINITY && fabsf(mb) < INFINITY)) { st[5] += 1.f; return; }      // inf or NaN: skipped
+  const float upd = st[2];
+  if (upd == 0.f) {
+    st[0] = ma;
+    st[1] = mb;
+  } else {
+    const float keep = 1.f - decay;
+    st[0] = decay * st[0] + keep * ma;
+    st[1] = decay * st[1] + keep * mb;
+  }
+  st[2] = upd + 1.f;
+  st[3] = ma;
+  st[4] = mb;
+}
+
 // What the unfused head / loss entry points refuse before they launch anything: a non-positive dimension, a NULL tensor they would touch.
 #define HL_SHAPE(ctx, ok, ...) RC_REQUIRE(ctx, ok, "bad shape: " __VA_ARGS__)
 #define HL_TENSORS(ctx, ok) RC_REQUIRE(ctx, ok, "null tensor")
@@ -693,15 +780,34 @@ int rcgan_proj_logit_all_bwd(rcgan_ctx* ctx, int n, int d, int v, const float* f
   return RCGAN_OK;
 }
 
-int rcgan_loss_fwd_bwd(rcgan_ctx* ctx, int kind, int rows, int cols, const float* x, const float* wts, float weight,
-                       float* loss_acc, float* dlogit, float* dwts) {
+// the regulariser's descriptor -> the kernels' parameter (all zero without one); parts_b: part b has rows
+static int loss_reg_args(rcgan_ctx* ctx, const rcgan_loss_reg* reg, bool part_b, LossReg* out) {
+  *out = LossReg{0.f, {nullptr, nullptr}, nullptr, nullptr};
+  if (!reg) return RCGAN_OK;
+  RC_REQUIRE(ctx, reg->weight >= 0.f && std::isfinite(reg->weight), "regulariser weight %g: finite and >= 0", (double)reg->weight);
+  RC_REQUIRE(ctx, reg->anchor_a && (reg->anchor_b || !part_b), "regulariser: null anchor");
+  RC_REQUIRE(ctx, (((uintptr_t)reg->anchor_a | (uintptr_t)reg->anchor_b | (uintptr_t)reg->gate | (uintptr_t)reg->reg_acc) & 3) == 0,
+             "regulariser: anchors, gate and reg_acc must be 4-byte aligned");
+  *out = LossReg{reg->weight, {reg->anchor_a, reg->anchor_b ? reg->anchor_b : reg->anchor_a}, reg->gate, reg->reg_acc};
+  return RCGAN_OK;
+}
+
+int rcgan_loss_reg_fwd_bwd(rcgan_ctx* ctx, int kind, int rows, int cols, const float* x, const float* wts, float weight,
+                           float* loss_acc, float* dlogit, float* dwts, const rcgan_loss_reg* reg) {
   RC_REQUIRE(ctx, kind >= 0 && kind <= RCGAN_LOSS_CE_ZEROS, "kind %d", kind);
   HL_SHAPE(ctx, rows >= 1 && cols >= 1, "rows %d cols %d", rows, cols);
   HL_TENSORS(ctx, x != nullptr);
+  LossReg r;
+  if (int rc = loss_reg_args(ctx, reg, false, &r)) return rc;
   hipLaunchKernelGGL(loss_kernel, dim3(1), dim3(256), 0, ctx->stream, kind, rows, cols, x, wts, weight, loss_acc, dlogit, dwts, ctx->gscale_host,
-                     ctx->gscale_dev);
+                     ctx->gscale_dev, r);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
+}
+
+int rcgan_loss_fwd_bwd(rcgan_ctx* ctx, int kind, int rows, int cols, const float* x, const float* wts, float weight,
+                       float* loss_acc, float* dlogit, float* dwts) {
+  return rcgan_loss_reg_fwd_bwd(ctx, kind, rows, cols, x, wts, weight, loss_acc, dlogit, dwts, nullptr);
 }
 
 // dE[l] = sum_s dlogit[s,l] feat[s]  (row v: the psi column -> dw_out; its sum over the samples -> db_out)
@@ -743,15 +849,18 @@ bool head_take_wgrad(rcgan_ctx* ctx, HeadWgradRider* out) {
 
 // v > HEAD_MAX_V: the unridden launches above; defer_ws is ignored (the parameter gradients are complete when the call returns).
 // ws: E [v][d] | dlogit [n][v+1] | dE [v+1][d] | loss rows [n] | (pooling inside the head) dfeat [n][d] floats
-static int head_wide(rcgan_ctx* ctx, HeadArgs& a, const rcgan_head_desc* hd, void* ws, size_t ws_bytes) {
+// (+ n floats behind those when the regulariser's reg_acc is wanted: its per-sample rows)
+static int head_wide(rcgan_ctx* ctx, HeadArgs& a, const rcgan_head_desc* hd, void* ws, size_t ws_bytes, const LossReg& r) {
   const int vp = a.v + 1;
   const bool pool_grad = a.x && a.dx;
-  const size_t need = ((size_t)a.v * a.d + (size_t)a.n * vp + (size_t)vp * a.d + a.n + (pool_grad ? (size_t)a.n * a.d : 0)) * sizeof(float);
+  const bool want_r = r.lam != 0.f && r.reg_acc;
+  const size_t need = ((size_t)a.v * a.d + (size_t)a.n * vp + (size_t)vp * a.d + a.n + (pool_grad ? (size_t)a.n * a.d : 0) + (want_r ? a.n : 0)) * sizeof(float);
   if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
   float* Eg = (float*)ws;
   float* dlg = Eg + (size_t)a.v * a.d;
   float* dEg = dlg + (size_t)a.n * vp;
   float* lossrow = dEg + (size_t)vp * a.d;
+  float* regrow = want_r ? lossrow + a.n + (pool_grad ? (size_t)a.n * a.d : 0) : nullptr;
   if (ctx->head_stage) {            // an earlier head's deferred launches were never carried: they go first
     int rc = rcgan_head_flush(ctx);
     if (rc) return rc;
@@ -768,12 +877,12 @@ static int head_wide(rcgan_ctx* ctx, HeadArgs& a, const rcgan_head_desc* hd, voi
                        a.sigma_e, a.b_e, Eg);
     RC_LAUNCH_CHECK(ctx);
   }
-  hipLaunchKernelGGL(head_wide_logit_kernel, dim3(cdiv(a.n, 4)), dim3(256), 0, ctx->stream, a, (const float*)Eg, dlg, lossrow);
+  hipLaunchKernelGGL(head_wide_logit_kernel, dim3(cdiv(a.n, 4)), dim3(256), 0, ctx->stream, a, (const float*)Eg, dlg, lossrow, r, regrow);
   RC_LAUNCH_CHECK(ctx);
   const bool want_params = a.dw_out || a.db_out || a.dtable || a.dw_e || a.db_e;
   const int nde = want_params ? (int)cdiv((long)vp * a.d, 256) : 0;
   hipLaunchKernelGGL(head_wide_de_kernel, dim3(nde + 1), dim3(256), 0, ctx->stream, a.n, a.d, a.v, (const float*)dlg, (const float*)a.feat, dEg,
-                     a.db_out, (const float*)lossrow, a.loss_acc, a.weight);
+                     a.db_out, (const float*)lossrow, a.loss_acc, a.weight, r, (const float*)regrow);
   RC_LAUNCH_CHECK(ctx);
   if (want_params && (a.dw_out || a.dtable || a.dw_e || a.db_e)) {
     hipLaunchKernelGGL(head_wide_wgrad_kernel, dim3(g1((long)a.e_dim * a.d + (long)a.v * a.e_dim + a.d)), dim3(256), 0, ctx->stream, a,
@@ -791,7 +900,7 @@ static int head_wide(rcgan_ctx* ctx, HeadArgs& a, const rcgan_head_desc* hd, voi
 // rows + pooled dfeat for the wide route).
 size_t rcgan_proj_head_workspace_bytes(int n, int d, int v) {
   if (n < 1 || d < 1 || v < 1) return 0;
-  const size_t tail = std::max((size_t)256, (size_t)n + (size_t)n * d);
+  const size_t tail = std::max((size_t)256, 2 * (size_t)n + (size_t)n * d);
   return ((size_t)v * d + (size_t)n * (v + 1) + (size_t)(v + 1) * d + tail) * sizeof(float);
 }
 
@@ -799,6 +908,14 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
                             const float* b_out, const float* table, const float* w_e, const float* sigma_e, const float* b_e,
                             float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
                             float* db_e, void* ws, size_t ws_bytes) {
+  return rcgan_proj_head_reg_fwd_bwd(ctx, hd, feat, w_out, sigma_out, b_out, table, w_e, sigma_e, b_e, loss_acc, logits, dfeat, dw_out, db_out,
+                                     dtable, dw_e, db_e, ws, ws_bytes, nullptr);
+}
+
+int rcgan_proj_head_reg_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const float* feat, const float* w_out, const float* sigma_out,
+                                const float* b_out, const float* table, const float* w_e, const float* sigma_e, const float* b_e,
+                                float* loss_acc, float* logits, float* dfeat, float* dw_out, float* db_out, float* dtable, float* dw_e,
+                                float* db_e, void* ws, size_t ws_bytes, const rcgan_loss_reg* reg) {
   RC_REQUIRE(ctx, hd && feat && w_out && table && w_e, "null argument");
   RC_REQUIRE(ctx, hd->n >= 1 && hd->n <= HEAD_MAX_N && hd->d >= 1 && hd->d <= HEAD_MAX_D && hd->v >= 1 && hd->v <= HEAD_MAX_V_WIDE && hd->e_dim >= 1,
              "head shape n %d d %d v %d e %d", hd->n, hd->d, hd->v, hd->e_dim);
@@ -821,9 +938,13 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
     RC_REQUIRE(ctx, hd->x_dtype == RCGAN_F32 || hd->x_dtype == RCGAN_H16, "bad x dtype");
     a.feat_out = (float*)feat;      // the features become an OUTPUT (read by the parameter-gradient kernels)
   }
-  if (a.v > HEAD_MAX_V) return head_wide(ctx, a, hd, ws, ws_bytes);
+  LossReg r;
+  if (int rc = loss_reg_args(ctx, reg, a.part[1].rows > 0, &r)) return rc;
+  if (a.v > HEAD_MAX_V) return head_wide(ctx, a, hd, ws, ws_bytes, r);
   const int vp = a.v + 1;
-  const size_t need = ((size_t)a.v * a.d + (size_t)a.n * vp + (size_t)vp * a.d + 256) * sizeof(float);
+  // (the tail: the workgroups' loss partials, and behind them the regulariser's when reg_acc is wanted)
+  const size_t tail = (r.lam != 0.f && r.reg_acc) ? std::max(256, 2 * cdiv(a.n, 4)) : 256;
+  const size_t need = ((size_t)a.v * a.d + (size_t)a.n * vp + (size_t)vp * a.d + tail) * sizeof(float);
   if (ws_bytes < need) RC_FAIL(ctx, RCGAN_EWORKSPACE_TOO_SMALL, "need %zu have %zu", need, ws_bytes);
   float* Eg = (float*)ws;
   float* dlg = Eg + (size_t)a.v * a.d;
@@ -851,11 +972,11 @@ int rcgan_proj_head_fwd_bwd(rcgan_ctx* ctx, const rcgan_head_desc* hd, const flo
   }
   const int nwg = cdiv(a.n, 4);
   RC_REQUIRE(ctx, nwg <= 256, "too many rows for the loss partials");
-  const size_t lds = ((size_t)a.v * a.d + 4) * sizeof(float);
+  const size_t lds = ((size_t)a.v * a.d + 8) * sizeof(float);
   if (a.x && hd->x_dtype == RCGAN_H16)
-    hipLaunchKernelGGL(head_logit_kernel<bf16_t>, dim3(nwg), dim3(256), lds, ctx->stream, a, (const float*)Eg, dlg, losspart, ctx->counters() + RC_COUNTER_HEAD);
+    hipLaunchKernelGGL(head_logit_kernel<bf16_t>, dim3(nwg), dim3(256), lds, ctx->stream, a, (const float*)Eg, dlg, losspart, ctx->counters() + RC_COUNTER_HEAD, r);
   else
-    hipLaunchKernelGGL(head_logit_kernel<float>, dim3(nwg), dim3(256), lds, ctx->stream, a, (const float*)Eg, dlg, losspart, ctx->counters() + RC_COUNTER_HEAD);
+    hipLaunchKernelGGL(head_logit_kernel<float>, dim3(nwg), dim3(256), lds, ctx->stream, a, (const float*)Eg, dlg, losspart, ctx->counters() + RC_COUNTER_HEAD, r);
   RC_LAUNCH_CHECK(ctx);
   if (defer) {
     HeadDeferred* h = (HeadDeferred*)ctx->head_blob;
@@ -898,6 +1019,21 @@ int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, c
   HL_SHAPE(ctx, rows >= 1 && cols >= 1, "rows %d cols %d", rows, cols);
   HL_TENSORS(ctx, p && dp && dl);
   hipLaunchKernelGGL(softmax_rows_bwd_kernel, dim3(cdiv(rows, 64)), dim3(64), 0, ctx->stream, rows, cols, p, dp, dl, accumulate);
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_lecam_update(rcgan_ctx* ctx, int rows_a, int rows_b, const float* logits, int ld, const int32_t* labels_a, const float* wts_a,
+                       const int32_t* labels_b, const float* wts_b, float* state, float decay) {
+  RC_REQUIRE(ctx, rows_a >= 1 && rows_b >= 1 && ld >= 1, "rows %d + %d of %d logits: at least one of each", rows_a, rows_b, ld);
+  RC_REQUIRE(ctx, logits && state, "null pointer");
+  RC_REQUIRE(ctx, (((uintptr_t)logits | (uintptr_t)state | (uintptr_t)labels_a | (uintptr_t)wts_a | (uintptr_t)labels_b | (uintptr_t)wts_b) & 3) == 0,
+             "logits, labels, weights and state must be 4-byte aligned");
+  RC_REQUIRE(ctx, !(labels_a && wts_a) && !(labels_b && wts_b), "a part takes labels or weight rows, not both");
+  RC_REQUIRE(ctx, ld == 1 || ((labels_a || wts_a) && (labels_b || wts_b)), "%d logits per row: every part needs labels or weight rows", ld);
+  RC_REQUIRE(ctx, decay >= 0.f && decay <= 1.f, "decay %g: in [0, 1]", (double)decay);
+  const LecamPart A = {rows_a, (const int*)labels_a, wts_a}, B = {rows_b, (const int*)labels_b, wts_b};
+  hipLaunchKernelGGL(lecam_update_kernel, dim3(1), dim3(256), 0, ctx->stream, A, B, logits, ld, state, decay);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }

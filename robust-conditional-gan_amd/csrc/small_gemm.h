@@ -59,8 +59,8 @@ __device__ __forceinline__ void small_gemm_body(const SmallGemmArgs& g, int bx, 
   for (int l = 0; l <= HEAD_MAX_V; ++l)
     if (l < L) red[kl][l][jj] = acc[l];
   __syncthreads();
-  if (t < L * 16) {
-    const int l = t >> 4;
+  for (int tl = t; tl < L * 16; tl += 256) {    // (L = HEAD_MAX_V + 1 rows -- dE of a 16-class head -- are 272 items: a second pass)
+    const int l = tl >> 4;
     float s0 = 0.f, s1 = 0.f;
 #pragma unroll
     for (int q = 0; q < 16; q += 2) { s0 += red[q][l][jj]; s1 += red[q + 1][l][jj]; }

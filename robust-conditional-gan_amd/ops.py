@@ -1407,12 +1407,19 @@ HEAD_MAX_D = 256
 HEAD_RIDERS = os.environ.get("RCGAN_HEAD_RIDERS", "1") != "0"
 
 
-def proj_head(ctx, feat, w_out, b_out, table, w_e, b_e, parts, weight, loss_acc, logits=None, E_pre=None):
+def lecam_reg(weight, anchor_a, anchor_b, gate, reg_acc=None):
+    """rcgan_loss_reg of the regularised loss entry points (include/rcgan_hip.h, "LeCam regulariser"): lambda and the DEVICE ADDRESSES
+    (ints) of part a's and part b's anchor, of the gate and of the optional accumulator of the unweighted term."""
+    return L.LossReg(float(weight), anchor_a, anchor_b, gate, reg_acc)
+
+
+def proj_head(ctx, feat, w_out, b_out, table, w_e, b_e, parts, weight, loss_acc, logits=None, E_pre=None, reg=None):
     """The whole projection head in one launch (rcgan_proj_head_fwd_bwd): psi = Linear_SN(feat) (gan_resnet.py:408-411),
     E = Linear_SN(embed_y(l)) for every label l (:414-421), logit[s,l] = psi[s] + <feat[s], E[l]> (:588, :654-660), the loss terms
     and every gradient.  w_out / w_e: Weight handles (sigma fused); table: the embedding_map parameter.
     parts: one or two (rows, kind, labels, wts) tuples covering feat's rows in order -- labels: int32 DT [rows] (one-hot
     weighting) or wts: fp32 DT [rows, v] (may require a gradient).  Adds weight * (mean over each part's rows) to loss_acc.
+    reg: an optional lecam_reg(...) -- the call is then rcgan_proj_head_reg_fwd_bwd.
     Like loss_term this computes its gradients in the forward launch: feat (and a wts that requires one) get their .grad
     here; the parameter gradients are accumulated into the step's zeroed buffers by two launches that are DEFERRED (HEAD_RIDERS:
     they ride in the 8x8 stage's backward launch and the grouped filter-gradient launch) -- complete after Context.flush_wgrads() /
@@ -1462,14 +1469,18 @@ def proj_head(ctx, feat, w_out, b_out, table, w_e, b_e, parts, weight, loss_acc,
     db_out = b_out.grad if (b_out is not None and b_out.req) else None
     db_e = b_e.grad if (b_e is not None and b_e.req) else None
     dtable = table.grad if table.req else None
-    ctx.check(ctx.lib.rcgan_proj_head_fwd_bwd(
-        ctx.h, C.byref(hd), _p(feat), _p(w_out.param), _p(w_out.sigma), _p(b_out), _p(table), _p(w_e.param), _p(w_e.sigma), _p(b_e),
-        _p(loss_acc), _p(logits), _p(dfeat), pg(dw_out), pg(db_out), pg(dtable), pg(dw_e), pg(db_e), C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
+    args = (ctx.h, C.byref(hd), _p(feat), _p(w_out.param), _p(w_out.sigma), _p(b_out), _p(table), _p(w_e.param), _p(w_e.sigma), _p(b_e),
+            _p(loss_acc), _p(logits), _p(dfeat), pg(dw_out), pg(db_out), pg(dtable), pg(dw_e), pg(db_e), C.c_void_p(ctx.ws_ptr), ctx.ws_bytes)
+    if reg is None:
+        ctx.check(ctx.lib.rcgan_proj_head_fwd_bwd(*args))
+    else:
+        ctx.check(ctx.lib.rcgan_proj_head_reg_fwd_bwd(*args, C.byref(reg)))
 
 
-def loss_term(ctx, kind, x, weight, loss_acc, wts=None):
+def loss_term(ctx, kind, x, weight, loss_acc, wts=None, reg=None):
     """Adds weight * L(x) to the device scalar loss_acc; the gradient weight*dL/dx is computed in the
-    same launch (the total cost is a weighted sum of such terms, so no upstream gradient is needed)."""
+    same launch (the total cost is a weighted sum of such terms, so no upstream gradient is needed).
+    reg: an optional lecam_reg(...) whose anchor_a is this term's anchor -- the call is then rcgan_loss_reg_fwd_bwd."""
     if len(x.shape) == 1:
         r, c = x.shape[0], 1
     else:
@@ -1482,7 +1493,10 @@ def loss_term(ctx, kind, x, weight, loss_acc, wts=None):
     dw = None
     if wts is not None and wts.req and ctx.recording:
         dw, _ = grad_of(ctx, wts)
-    ctx.check(ctx.lib.rcgan_loss_fwd_bwd(ctx.h, kind, r, c, _p(x), _p(wts), float(weight), _p(loss_acc), _p(dx), _p(dw)))
+    if reg is None:
+        ctx.check(ctx.lib.rcgan_loss_fwd_bwd(ctx.h, kind, r, c, _p(x), _p(wts), float(weight), _p(loss_acc), _p(dx), _p(dw)))
+    else:
+        ctx.check(ctx.lib.rcgan_loss_reg_fwd_bwd(ctx.h, kind, r, c, _p(x), _p(wts), float(weight), _p(loss_acc), _p(dx), _p(dw), C.byref(reg)))
 
 
 def bce_onehot_term(ctx, x, labels, weight, loss_acc):

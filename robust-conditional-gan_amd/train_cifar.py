@@ -74,6 +74,9 @@ def define_flags():
                    "not tuned on CIFAR here)")
     f.DEFINE_integer("ada_interval", 4, "--ada_target: critic steps per adjustment of p")
     f.DEFINE_float("ada_p_init", 0.0, "--ada_target: initial p in [0, 1]")
+    f.DEFINE_float("lecam", 0.0, "weight of the LeCam regulariser of the critic's outputs (Tseng et al. 2021): the real logits are pulled "
+                   "towards a moving average of the fake ones and the reverse; 0: off (not tuned on CIFAR here)")
+    f.DEFINE_float("lecam_decay", 0.99, "--lecam: decay in [0, 1) of the two moving averages (not tuned on CIFAR here)")
     M.define_flags(f)             # the sample-quality metrics' flags
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
@@ -138,11 +141,12 @@ def main(argv=None):
         if asset_classes != N_CLASSES:
             raise ValueError("--label_classifier %s classifies %d classes, this run has %d"
                              % (FLAGS.label_classifier, asset_classes, N_CLASSES))
-    from .cifar import check_ada, parse_diffaugment
+    from .cifar import check_ada, check_lecam, parse_diffaugment
     parse_diffaugment(FLAGS.diffaugment)          # (a bad name fails here, before anything touches the GPU)
     # ... and so do the adaptive probability's ranges, --ada_target without --diffaugment, and more than one rank
     check_ada(FLAGS.ada_target, FLAGS.ada_images, FLAGS.ada_interval, FLAGS.ada_p_init, FLAGS.diffaugment,
               int(os.environ.get("WORLD_SIZE", "1")))
+    check_lecam(FLAGS.lecam, FLAGS.lecam_decay, int(os.environ.get("WORLD_SIZE", "1")))
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
@@ -151,6 +155,7 @@ def main(argv=None):
     logging.info('dataset = {} ({} classes)'.format(FLAGS.dataset, N_CLASSES))
     logging.info('diffaugment = {}'.format(FLAGS.diffaugment or 'off'))
     logging.info('ada_target = {}'.format(FLAGS.ada_target or 'off'))
+    logging.info('lecam = {}'.format(FLAGS.lecam or 'off'))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -198,7 +203,7 @@ def main(argv=None):
                    confuse_multiplier=FLAGS.confuse_multiplier, confuse_lr_decay=FLAGS.confuse_lr_decay,
                    device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision,
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment, ada_target=FLAGS.ada_target, ada_images=FLAGS.ada_images,
-                   ada_interval=FLAGS.ada_interval, ada_p_init=FLAGS.ada_p_init)
+                   ada_interval=FLAGS.ada_interval, ada_p_init=FLAGS.ada_p_init, lecam=FLAGS.lecam, lecam_decay=FLAGS.lecam_decay)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     clean_train = None                 # (images, clean labels) of the training set: the real side of the sample-quality metrics
@@ -338,6 +343,11 @@ def main(argv=None):
             # dev cost (gan_resnet.py:972-990): disc_cost, forward only, over the whole dev set; every rank evaluates its
             # shard of every dev batch (the pass updates the spectral-norm u vectors exactly as the reference's does, so all
             # ranks have to make it), the cost is the mean over towers and batches
+            if m.lecam:                # the regulariser's anchors and the unweighted term R of the last critic step (read before the
+                lecam = m.lecam_report()                  # forward-only passes below clear the step's scalars)
+                plot.plot('lecam_a_real', lecam["a_real"])
+                plot.plot('lecam_a_fake', lecam["a_fake"])
+                plot.plot('lecam_reg', lecam["reg"])
             logging.info('starting calculating dev cost.')
             dev_disc_costs = []
             for batch in dev_gen():
