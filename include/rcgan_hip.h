@@ -673,6 +673,33 @@ int rcgan_softmax_rows_fwd(rcgan_ctx* ctx, int rows, int cols, const float* logi
 int rcgan_softmax_rows_bwd(rcgan_ctx* ctx, int rows, int cols, const float* p, const float* dp, float* dlogits,
                            int accumulate);
 
+/* ---- diversity-sensitive generator term on same-label pairs (csrc/diversity.hip; Yang et al., "Diversity-Sensitive Conditional
+ * GANs", ICLR 2019; Mao et al., "Mode Seeking GANs", CVPR 2019; the linear clamped form, as StarGAN v2 uses it) ---------------------
+ * x [2P, D] and z [2P, Z] in `dtype` (RCGAN_F32 or the library's 16-bit type); pair i is rows (i, i + P).  One launch, one workgroup
+ * per pair:
+ *   dI_i = (1/D) sum_k |x[i,k] - x[i+P,k]|,   dz_i = (1/Z) sum_k |z[i,k] - z[i+P,k]|,   r_i = dI_i / dz_i      (fp32)
+ *   m_i  = 0 if labels != NULL and labels[i] != labels[i+P], or if dz_i == 0; else 1
+ *   *loss_acc   += -(weight / P) sum_i m_i min(r_i, tau)      the divisor is always P: masked pairs stay in the denominator
+ *   ratio_out[i] = r_i, or exactly -1 for a masked pair
+ *   c_i = m_i [r_i < tau] weight g / (P D dz_i),  g = the scale of rcgan_set_grad_scale (host value times the device value, read by
+ *         the kernel); the loss VALUE is never scaled
+ *   dx[i,k] (= | +=) -c_i sgn(x[i,k] - x[i+P,k]),  dx[i+P,k] (= | +=) +c_i sgn(x[i,k] - x[i+P,k]),  sgn(0) = 0
+ * A pair at or above the clamp and a masked pair write zeros with accumulate = 0 and leave dx bit for bit untouched with
+ * accumulate = 1.  z gets no gradient.  tau = +inf: no clamp.  loss_acc, dx, ratio_out and labels may each be NULL.
+ * Both rows of a pair are read once and their differences stay in registers (16-byte loads and stores: a row is a whole number of
+ * 16-byte chunks, at most 1024 of them, and x and dx are 16-byte aligned) or, on the element-wise route every other case takes,
+ * their signs stay in LDS (D <= 61440 there; longer rows: RCGAN_EUNSUPPORTED_SHAPE).  The sums are fixed-order block reductions; the P
+ * loss terms are per-pair floats in ws, summed in pair order by the last workgroup to arrive: no floating-point atomics, the same
+ * bits on every run, eager or replayed.  ws: rcgan_pair_diversity_workspace_bytes(P), needed only with a loss_acc
+ * (RCGAN_EWORKSPACE_TOO_SMALL otherwise).
+ * P, D, Z >= 1; x, z non-NULL and element-aligned, dx element-aligned; labels, loss_acc, ratio_out, ws 4-byte aligned; weight finite
+ * and >= 0; tau > 0 (not NaN); a known dtype: anything else is RCGAN_EINVALID_ARG before any launch.  weight == 0 launches nothing and
+ * touches nothing. */
+size_t rcgan_pair_diversity_workspace_bytes(int pairs);
+int rcgan_pair_diversity_fwd_bwd(rcgan_ctx* ctx, int pairs, int d, int zdim, int dtype, const void* x, const void* z, const int32_t* labels,
+                                 float weight, float tau, float* loss_acc, void* dx, int accumulate, float* ratio_out, void* ws,
+                                 size_t ws_bytes);
+
 /* ---- training the generated-label-accuracy classifier (csrc/classifier.hip; fp32 model, classifier.py) -------------------- */
 /* Sparse softmax cross-entropy (tf.nn.sparse_softmax_cross_entropy_with_logits + reduce_mean), one launch:
  *   *loss_acc      += weight * mean_rows(-log softmax(logits)[label])

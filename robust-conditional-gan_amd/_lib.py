@@ -250,6 +250,8 @@ SIGNATURES = {
     "rcgan_loss_reg_fwd_bwd": (I, [P, I, I, I, P, P, F, P, P, P, C.POINTER(LossReg)]),
     "rcgan_proj_head_reg_fwd_bwd": (I, [P, C.POINTER(HeadDesc)] + [P] * 16 + [P, SZ, C.POINTER(LossReg)]),
     "rcgan_lecam_update": (I, [P, I, I, P, I, P, P, P, P, P, F]),
+    "rcgan_pair_diversity_workspace_bytes": (SZ, [I]),
+    "rcgan_pair_diversity_fwd_bwd": (I, [P, I, I, I, I, P, P, P, F, F, P, P, I, P, P, SZ]),
     "rcgan_class_moments_bytes": (SZ, [I, I]),
     "rcgan_class_moments_accum": (I, [P, I, I, I, P, P, P]),
     "rcgan_knn_radius": (I, [P, I, I, I, I, P, P, P]),

@@ -203,6 +203,35 @@ def check_lecam(lecam, lecam_decay, world_size=1):
     return lam, decay
 
 
+def check_diversity(diversity, diversity_tau, world_size=1):
+    """The arguments of the diversity-sensitive generator term, CifarRCGAN(diversity=, diversity_tau=) / --diversity* (Yang et al.,
+    ICLR 2019; Mao et al., CVPR 2019; DESIGN.md 3, "Diversity-sensitive generator term").  diversity = 0 is off; on, it is the weight
+    lambda >= 0 of -(1/B) sum_i min(r_i, tau) in the generator cost, r_i the image distance per unit of latent distance of the
+    same-label pair (i, i + B).  diversity_tau > 0, inf allowed: the clamp.  Raises ValueError before any GPU work; returns
+    (lambda, tau) as floats."""
+    lam, tau = float(diversity), float(diversity_tau)
+    if not (np.isfinite(lam) and lam >= 0.0):
+        raise ValueError("diversity must be finite and >= 0 (0 = off), got %r" % (diversity,))
+    if not tau > 0.0:                  # (false for a NaN too)
+        raise ValueError("diversity_tau must be > 0 (inf: no clamp), got %r" % (diversity_tau,))
+    if lam != 0.0 and world_size > 1:
+        raise ValueError("diversity = %r with world_size = %d: the term pairs rows i and i + B of one rank's generator batch, which "
+                         "needs the generator labels paired per shard; that has not been run on more than one GPU, and there is no "
+                         "multi-GPU machine to test it on" % (diversity, world_size))
+    return lam, tau
+
+
+def pair_generator_labels(rnd, bia, B):
+    """The generator step's two [2B] label arrays for the diversity-sensitive term: rows B..2B of labels_random_G replaced by rows
+    0..B, so that fakes i and i + B are two draws of z under ONE label.  The biased labels stay as drawn: the critic's noisy label of
+    each fake remains an independent draw.  Plain numpy; returns new arrays."""
+    rnd, bia = np.array(rnd), np.array(bia)
+    if rnd.shape != (2 * B,) or bia.shape != (2 * B,):
+        raise ValueError("pair_generator_labels: two label arrays of shape (%d,), got %r and %r" % (2 * B, rnd.shape, bia.shape))
+    rnd[B:] = rnd[:B]
+    return rnd, bia
+
+
 def confusion_logits_initial(confuse_init, confuse_init_diag, rs, n_classes=VOCAB_SIZE):
     """gan_resnet.py:499-520 with VOCAB_SIZE = n_classes (the reference's special case of 10 classes kept for K = 10 only)."""
     K = n_classes
@@ -493,9 +522,13 @@ class CifarRCGAN:
                  device=0, use_graphs=True, device_rng=True, arena_bytes=None, world_size=1, rank=0,
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
                  grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE,
-                 diffaugment="", ada_target=0.0, ada_images=500000, ada_interval=4, ada_p_init=0.0, lecam=0.0, lecam_decay=0.99):
+                 diffaugment="", ada_target=0.0, ada_images=500000, ada_interval=4, ada_p_init=0.0, lecam=0.0, lecam_decay=0.99,
+                 diversity=0.0, diversity_tau=float("inf")):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # the generator rewarded for image distance per unit of latent distance on same-label pairs ("Diversity-sensitive
+        # generator term"); weight 0 = off.  Checked before any context exists.
+        self.diversity, self.diversity_tau = check_diversity(diversity, diversity_tau, world_size)
         # the critic's outputs anchored to moving averages of the other side's ("LeCam regulariser"); weight 0 = off.
         # Checked before any context exists.
         self.lecam, self.lecam_decay = check_lecam(lecam, lecam_decay, world_size)
@@ -695,6 +728,9 @@ class CifarRCGAN:
         # the logits rcgan_ada_update and rcgan_lecam_update read after the fused head (which otherwise keeps them on chip):
         # head_logits if set, else this one buffer, shared by the two options
         self.ada_logits = P((2 * B, self.K), f32, fill=0.0) if ((self.ada or self.lecam) and self.fused_head) else None
+        # the ratios r_i of the last generator step's B pairs (-1: a masked pair), written by rcgan_pair_diversity_fwd_bwd; read by
+        # diversity_report().  The term has no state: nothing of it is in state_dict.
+        self.diversity_ratio = P((B,), f32, fill=0.0) if self.diversity else None
         # (round 6) The critic steps' generator forwards on a SECOND stream.  The generator does not change during the N_CRITIC critic
         # updates of an iteration (gan_resnet.py:928-947), so step k + 1's Generator() call can run while critic step k does: a critic
         # step is a chain of ~26 small-grid launches that leaves half the chip idle most of the time, the generator forward is the
@@ -1112,6 +1148,11 @@ class CifarRCGAN:
         if self.perm:
             logits = perm_classifier(fake, self.perm_type)                                           # :781
             O.bce_onehot_term(ctx, logits, inp["labels_random_G"], self.perm_mult, self.loss_g)      # :782-784
+        if self.diversity:
+            # rows i and i + B of the UNAUGMENTED fakes: one more consumer of `fake`, whose gradient is added to the critic's (or the
+            # augmentation adjoint's) and the permutation classifier's
+            O.pair_diversity(ctx, fake, inp["z_G"], inp["labels_random_G"], self.diversity, self.diversity_tau, self.loss_g,
+                             ratio_out=self.diversity_ratio)
         ctx.backward()
         self._dp_finish([self.PG] + ([self.PC] if self.PC is not None else []))
 
@@ -1421,6 +1462,18 @@ class CifarRCGAN:
         self.ctx.sync()
         s = self.ada_state.cpu().numpy()
         return dict(p=float(s[0]), r_last=float(s[4]), updates=int(s[5]))
+
+    def diversity_report(self):
+        """{ratio_mean, clamped, masked} of the diversity-sensitive term's last generator step (synchronises): the mean ratio r_i over
+        the unmasked pairs (None when there is none, or with the option off), the share of the B pairs at or above the clamp, and the
+        share that was masked (labels of rows i and i + B unequal, or identical latents) -- 0 in a correct run."""
+        if self.diversity_ratio is None:
+            return dict(ratio_mean=None, clamped=0.0, masked=0.0)
+        r = self.ctx.download(self.diversity_ratio).astype(np.float64)
+        live = r >= 0.0
+        return dict(ratio_mean=float(r[live].mean()) if live.any() else None,
+                    clamped=float(np.count_nonzero(live & (r >= self.diversity_tau))) / r.size,
+                    masked=float(np.count_nonzero(~live)) / r.size)
 
     def lecam_report(self):
         """{a_real, a_fake, mean_real, mean_fake, reg, updates, skipped} of the LeCam regulariser as it stands on the stream now

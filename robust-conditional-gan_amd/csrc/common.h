@@ -81,6 +81,7 @@ struct rcgan_ctx {
 #define RC_COUNTER_HEAD 500    // loss partials of the fused projection head
 #define RC_COUNTER_INPUTS 501  // the step-input rider of the filter preparation (step_inputs.h)
 #define RC_COUNTER_XENT 502    // row sums of the sparse softmax cross-entropy (classifier.hip)
+#define RC_COUNTER_DIVERSITY 503   // per-pair loss terms of the diversity-sensitive generator term (diversity.hip)
 
 // grow-only scratch (*buf, *cap) of at least `need` bytes; never inside a capture, and an outgrown buffer stays allocated (a graph
 // captured earlier replays launches that address it)

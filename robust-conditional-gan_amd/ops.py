@@ -1508,6 +1508,27 @@ def bce_onehot_term(ctx, x, labels, weight, loss_acc):
     ctx.check(ctx.lib.rcgan_bce_onehot_fwd_bwd(ctx.h, r, c, _p(x), _p(labels), float(weight), _p(loss_acc), _p(dx)))
 
 
+def pair_diversity(ctx, x, z, labels, weight, tau, loss_acc, ratio_out=None):
+    """The diversity-sensitive generator term on the pairs (i, i + P) of x's 2P rows (rcgan_pair_diversity_fwd_bwd, include/rcgan_hip.h):
+    adds -(weight / P) sum_i m_i min(r_i, tau) to the device scalar loss_acc, r_i = mean|x_i - x_{i+P}| / mean|z_i - z_{i+P}|, pairs
+    with unequal labels (int32 DT [2P] or None) or identical latents masked.  x [2P, D] and z [2P, Z] in the activation dtype;
+    ratio_out: fp32 [P], r_i or -1 for a masked pair.  Like loss_term the gradient is produced in the forward launch -- but ADDED to
+    whatever x.grad holds already (grad_of's accumulate flag), so x may have other consumers, whose backward entries accumulate as
+    they do for any tensor with a gradient.  z gets none."""
+    n, d = x.shape
+    if n < 2 or n % 2 or tuple(z.shape[:1]) != (n,) or len(z.shape) != 2 or z.dtype != x.dtype:
+        raise ValueError("pair_diversity: x [2P, D] and z [2P, Z] of one dtype, got %r %s and %r %s" % (x.shape, x.dtype, z.shape, z.dtype))
+    if labels is not None and tuple(labels.shape) != (n,):
+        raise ValueError("pair_diversity: labels must be int32 [%d], got %r" % (n, labels.shape))
+    if ratio_out is not None and (tuple(ratio_out.shape) != (n // 2,) or ratio_out.dtype != L.F32):
+        raise ValueError("pair_diversity: ratio_out must be fp32 [%d], got %r" % (n // 2, ratio_out.shape))
+    dx, acc = None, 0
+    if x.req and ctx.recording:
+        dx, acc = grad_of(ctx, x)
+    ctx.check(ctx.lib.rcgan_pair_diversity_fwd_bwd(ctx.h, n // 2, d, z.shape[1], x.dtype, _p(x), _p(z), _p(labels), float(weight), float(tau),
+                                                   _p(loss_acc), _p(dx), acc, _p(ratio_out), C.c_void_p(ctx.ws_ptr), ctx.ws_bytes))
+
+
 def softmax_xent(ctx, logits, labels, weight, loss_acc, n_correct=None):
     """weight * reduce_mean(sparse_softmax_cross_entropy_with_logits(logits, labels)) added to the device scalar loss_acc, the number
     of rows classified correctly added to n_correct (fp32 device scalar, optional).  Like loss_term the gradient is written in the

@@ -77,6 +77,10 @@ def define_flags():
     f.DEFINE_float("lecam", 0.0, "weight of the LeCam regulariser of the critic's outputs (Tseng et al. 2021): the real logits are pulled "
                    "towards a moving average of the fake ones and the reverse; 0: off (not tuned on CIFAR here)")
     f.DEFINE_float("lecam_decay", 0.99, "--lecam: decay in [0, 1) of the two moving averages (not tuned on CIFAR here)")
+    f.DEFINE_float("diversity", 0.0, "weight of the diversity-sensitive generator term (Yang et al. 2019, Mao et al. 2019): the generator "
+                   "is rewarded for image distance per unit of latent distance between two fakes of one label; 0: off (not tuned on "
+                   "CIFAR here)")
+    f.DEFINE_float("diversity_tau", float("inf"), "--diversity: clamp of the distance ratio, > 0; inf: none (not tuned on CIFAR here)")
     M.define_flags(f)             # the sample-quality metrics' flags
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
@@ -141,12 +145,13 @@ def main(argv=None):
         if asset_classes != N_CLASSES:
             raise ValueError("--label_classifier %s classifies %d classes, this run has %d"
                              % (FLAGS.label_classifier, asset_classes, N_CLASSES))
-    from .cifar import check_ada, check_lecam, parse_diffaugment
+    from .cifar import check_ada, check_diversity, check_lecam, pair_generator_labels, parse_diffaugment
     parse_diffaugment(FLAGS.diffaugment)          # (a bad name fails here, before anything touches the GPU)
     # ... and so do the adaptive probability's ranges, --ada_target without --diffaugment, and more than one rank
     check_ada(FLAGS.ada_target, FLAGS.ada_images, FLAGS.ada_interval, FLAGS.ada_p_init, FLAGS.diffaugment,
               int(os.environ.get("WORLD_SIZE", "1")))
     check_lecam(FLAGS.lecam, FLAGS.lecam_decay, int(os.environ.get("WORLD_SIZE", "1")))
+    check_diversity(FLAGS.diversity, FLAGS.diversity_tau, int(os.environ.get("WORLD_SIZE", "1")))
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
@@ -156,6 +161,7 @@ def main(argv=None):
     logging.info('diffaugment = {}'.format(FLAGS.diffaugment or 'off'))
     logging.info('ada_target = {}'.format(FLAGS.ada_target or 'off'))
     logging.info('lecam = {}'.format(FLAGS.lecam or 'off'))
+    logging.info('diversity = {}'.format('{} (tau {})'.format(FLAGS.diversity, FLAGS.diversity_tau) if FLAGS.diversity else 'off'))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -203,7 +209,8 @@ def main(argv=None):
                    confuse_multiplier=FLAGS.confuse_multiplier, confuse_lr_decay=FLAGS.confuse_lr_decay,
                    device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision,
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment, ada_target=FLAGS.ada_target, ada_images=FLAGS.ada_images,
-                   ada_interval=FLAGS.ada_interval, ada_p_init=FLAGS.ada_p_init, lecam=FLAGS.lecam, lecam_decay=FLAGS.lecam_decay)
+                   ada_interval=FLAGS.ada_interval, ada_p_init=FLAGS.ada_p_init, lecam=FLAGS.lecam, lecam_decay=FLAGS.lecam_decay,
+                   diversity=FLAGS.diversity, diversity_tau=FLAGS.diversity_tau)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     clean_train = None                 # (images, clean labels) of the training set: the real side of the sample-quality metrics
@@ -309,7 +316,10 @@ def main(argv=None):
             np.set_printoptions()
         if 0 < iteration:
             _random_labels_G, _labels_biased_G = next(gen_G)
-            m.feed_host("g", labels_random_G=sh(_random_labels_G), labels_biased_G=sh(_labels_biased_G))
+            g_rnd, g_bia = sh(_random_labels_G), sh(_labels_biased_G)
+            if m.diversity:            # fakes i and i + B of this rank's shard under one label: the pairs of the diversity-sensitive term
+                g_rnd, g_bia = pair_generator_labels(g_rnd, g_bia, m.B)
+            m.feed_host("g", labels_random_G=g_rnd, labels_biased_G=g_bia)
             m.g_step(iteration=iteration)
         # the generator is fixed during the critic updates: their N_CRITIC Generator() forwards run as one pass
         # (prepare_critic_fakes), then every critic step consumes its slice
@@ -348,6 +358,12 @@ def main(argv=None):
                 plot.plot('lecam_a_real', lecam["a_real"])
                 plot.plot('lecam_a_fake', lecam["a_fake"])
                 plot.plot('lecam_reg', lecam["reg"])
+            if m.diversity and iteration > 0:      # the last generator step's pairs (iteration 0 has no generator step)
+                div = m.diversity_report()
+                if div["ratio_mean"] is not None:
+                    plot.plot('diversity_ratio', div["ratio_mean"])
+                plot.plot('diversity_clamped', div["clamped"])
+                plot.plot('diversity_masked', div["masked"])
             logging.info('starting calculating dev cost.')
             dev_disc_costs = []
             for batch in dev_gen():
