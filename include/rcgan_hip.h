@@ -700,6 +700,33 @@ int rcgan_pair_diversity_fwd_bwd(rcgan_ctx* ctx, int pairs, int d, int zdim, int
                                  float weight, float tau, float* loss_acc, void* dx, int accumulate, float* ratio_out, void* ws,
                                  size_t ws_bytes);
 
+/* ---- balanced consistency regularisation of the critic (csrc/loss.hip; Zhang et al., "Consistency Regularization for Generative
+ * Adversarial Networks", ICLR 2020; Zhao et al., "Improved Consistency Regularization for GANs", 2020: the balanced form, bCR) -------
+ * With the option on a critic step evaluates the trunk on 4B rows: rows [0, 2B) are the [real ; fake] the critic sees anyway (through
+ * DiffAugment or its gated form where those are on), rows [2B, 4B) are rcgan_diffaugment_fwd(x_all, u_bcr, bcr_policy) of the
+ * UN-augmented [real ; fake]: always applied (no gate), one independent row of u_bcr per image.  The critic cost gains
+ *     L_bcr = lam_real * mean_{i < B} c_i  +  lam_fake * mean_{B <= i < 2B} c_i,
+ * c_i the squared difference of row i's score and row (i + 2B)'s, both scores formed at row i's own label or weight row, exactly as
+ * that part's loss term forms its expectation (the rule of the LeCam section above):
+ *     labelled part   c_i = (logit[i, y_i] - logit[i + 2B, y_i])^2
+ *     weighted part   c_i = sum_l w[i, l] (logit[i, l] - logit[i + 2B, l])^2        (negative weights included)
+ * Both members of a pair get a gradient, and so do weight rows that require one.  The term has no state.
+ *
+ * rcgan_pair_consistency_fwd_bwd: ONE part per call, one single-workgroup launch.  x and x_aug are fp32 [pairs][cols]: cols == 1 for
+ * a labelled part whose logit is already taken at the label, the class count for a weighted one.  wts: fp32 [pairs][cols], or NULL
+ * (every weight 1).  With e = x[i,l] - x_aug[i,l] (one fp32 subtraction), w = wts[i,l] or 1:
+ *     m = (1 / pairs) sum_i sum_l w e^2            (fp32, a thread's elements in order, then a fixed-order block sum: no atomics)
+ *     *loss_acc += lam * m;    *term_acc += m      (the unweighted mean, for reports; may be NULL, as loss_acc may)
+ *     dx[i,l]    (= | +=)  g lam 2 w e / pairs     (accumulate = 0 | 1: the hinge terms have already WRITTEN x's gradient)
+ *     dx_aug[i,l] =       -g lam 2 w e / pairs     (always written whole)
+ *     dwts[i,l] +=         g lam e^2 / pairs       (always accumulated)
+ * g = the scale of rcgan_set_grad_scale (host value times the device value, read by the kernel); the loss VALUE is never scaled.
+ * dx, dx_aug and dwts may each be NULL (dwts needs wts).  Identical rows give exactly 0 everywhere.  The same bits on every run, eager
+ * or replayed.  pairs >= 1, cols >= 1, pairs * cols <= 2^20 (one workgroup serves them all); x and x_aug non-NULL; every pointer 4-byte aligned; lam finite and >= 0:
+ * anything else is RCGAN_EINVALID_ARG before any launch.  lam == 0 launches nothing and touches nothing. */
+int rcgan_pair_consistency_fwd_bwd(rcgan_ctx* ctx, int pairs, int cols, const float* x, const float* x_aug, const float* wts, float lam,
+                                   float* loss_acc, float* term_acc, float* dx, int accumulate, float* dx_aug, float* dwts);
+
 /* ---- training the generated-label-accuracy classifier (csrc/classifier.hip; fp32 model, classifier.py) -------------------- */
 /* Sparse softmax cross-entropy (tf.nn.sparse_softmax_cross_entropy_with_logits + reduce_mean), one launch:
  *   *loss_acc      += weight * mean_rows(-log softmax(logits)[label])

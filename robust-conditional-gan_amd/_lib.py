@@ -252,6 +252,7 @@ SIGNATURES = {
     "rcgan_lecam_update": (I, [P, I, I, P, I, P, P, P, P, P, F]),
     "rcgan_pair_diversity_workspace_bytes": (SZ, [I]),
     "rcgan_pair_diversity_fwd_bwd": (I, [P, I, I, I, I, P, P, P, F, F, P, P, I, P, P, SZ]),
+    "rcgan_pair_consistency_fwd_bwd": (I, [P, I, I, P, P, P, F, P, P, P, I, P, P]),
     "rcgan_class_moments_bytes": (SZ, [I, I]),
     "rcgan_class_moments_accum": (I, [P, I, I, I, P, P, P]),
     "rcgan_knn_radius": (I, [P, I, I, I, I, P, P, P]),

@@ -203,6 +203,30 @@ def check_lecam(lecam, lecam_decay, world_size=1):
     return lam, decay
 
 
+def check_bcr(bcr_real, bcr_fake, bcr_policy, world_size=1):
+    """The arguments of balanced consistency regularisation, CifarRCGAN(bcr_real=, bcr_fake=, bcr_policy=) / --bcr_* (Zhang et al.,
+    ICLR 2020; Zhao et al. 2020; DESIGN.md 3, "Balanced consistency regularisation").  The two weights, finite and >= 0, of the mean
+    squared difference of the critic's score of a real / a fake image and of its augmented copy; both 0 is off.  bcr_policy: a
+    diffaugment policy (parse_diffaugment), non-empty where a weight is positive.  Raises ValueError before any GPU work; returns
+    (lam_real, lam_fake, policy bits), the bits 0 when off."""
+    lam_r, lam_f = float(bcr_real), float(bcr_fake)
+    if not (np.isfinite(lam_r) and lam_r >= 0.0):
+        raise ValueError("bcr_real must be finite and >= 0 (0 = off), got %r" % (bcr_real,))
+    if not (np.isfinite(lam_f) and lam_f >= 0.0):
+        raise ValueError("bcr_fake must be finite and >= 0 (0 = off), got %r" % (bcr_fake,))
+    bits = parse_diffaugment(bcr_policy)
+    if lam_r == 0.0 and lam_f == 0.0:
+        return 0.0, 0.0, 0
+    if not bits:
+        raise ValueError("bcr_real = %r, bcr_fake = %r need a non-empty bcr_policy: the transform the critic is to be consistent under"
+                         % (bcr_real, bcr_fake))
+    if world_size > 1:
+        raise ValueError("bcr_real = %r, bcr_fake = %r with world_size = %d: the 4B-row critic pass and its two reported means have "
+                         "not been run on more than one GPU, and there is no multi-GPU machine to test it on"
+                         % (bcr_real, bcr_fake, world_size))
+    return lam_r, lam_f, bits
+
+
 def check_diversity(diversity, diversity_tau, world_size=1):
     """The arguments of the diversity-sensitive generator term, CifarRCGAN(diversity=, diversity_tau=) / --diversity* (Yang et al.,
     ICLR 2019; Mao et al., CVPR 2019; DESIGN.md 3, "Diversity-sensitive generator term").  diversity = 0 is off; on, it is the weight
@@ -523,9 +547,13 @@ class CifarRCGAN:
                  variables=None, loss_scale=None, dynamic_loss_scale=None, loss_scale_growth_interval=2000, comm=None,
                  grad_bucket_dtype=None, stub_model=None, f32_matmul_precision="highest", n_classes=VOCAB_SIZE,
                  diffaugment="", ada_target=0.0, ada_images=500000, ada_interval=4, ada_p_init=0.0, lecam=0.0, lecam_decay=0.99,
-                 diversity=0.0, diversity_tau=float("inf")):
+                 diversity=0.0, diversity_tau=float("inf"), bcr_real=0.0, bcr_fake=0.0, bcr_policy="translation"):
         if algorithm not in ALGORITHMS:
             raise ValueError("Unknown algorithm %s" % algorithm)
+        # the critic penalised for scoring an image and its augmented copy differently ("Balanced consistency
+        # regularisation"); both weights 0 = off.  Checked before any context exists.
+        self.bcr_real, self.bcr_fake, self.bcr_policy = check_bcr(bcr_real, bcr_fake, bcr_policy, world_size)
+        self.bcr = bool(self.bcr_policy)
         # the generator rewarded for image distance per unit of latent distance on same-label pairs ("Diversity-sensitive
         # generator term"); weight 0 = off.  Checked before any context exists.
         self.diversity, self.diversity_tau = check_diversity(diversity, diversity_tau, world_size)
@@ -555,7 +583,8 @@ class CifarRCGAN:
         if arena_bytes is None:
             # ~20 MB/sample with 16-bit activations (the five-step generator pass at 5B samples is the high-water mark), twice
             # that in fp32, + slack
-            arena_bytes = int(2.5e6 * 4 * self.B * (4 if dtype == "f32" else 2)) + (1 << 30)
+            # ... and with the consistency term the critic step's pass over 4B rows, with its backward, on top
+            arena_bytes = int(2.5e6 * (8 if self.bcr else 4) * self.B * (4 if dtype == "f32" else 2)) + (1 << 30)
         self.ctx = Context(device, dtype, arena_bytes=arena_bytes)
         ctx = self.ctx
         ctx.set_f32_matmul_precision(self.f32_matmul_precision)
@@ -667,6 +696,10 @@ class CifarRCGAN:
             if self.ada:
                 self.feed_layout["d"].append(("aug_gate", gate_shapes["aug_gate"], f32))
                 self.feed_layout["g"].append(("aug_gate_G", gate_shapes["aug_gate_G"], f32))
+        # the consistency term's uniforms, one row per image of [real ; fake]: a step input likewise, or a buffer the step fills
+        # (_bcr_second_half); absent with the option off
+        if self.bcr and not device_rng:
+            self.feed_layout["d"].append(("bcr_u", (2 * B, 8), f32))
         self.feed, self.inp = {}, {}
         self._feed_ring = {}
         for key, fields in self.feed_layout.items():
@@ -703,12 +736,17 @@ class CifarRCGAN:
                 self._aug_draw[name] = buf
                 self.inp[name] = DT(buf.ptr, (n, 8), f32, buf.base, name)
                 self.inp[gname] = DT(buf.ptr + 4 * n * 8, (n, 4), f32, buf.base, gname)
+        if self.bcr and device_rng:
+            self.inp["bcr_u"] = P((2 * B, 8), f32)
         ctx.view(self.inp["arange"]).copy_(torch.arange(self.K, dtype=torch.int32))
         ctx.view(self.inp["C_const"]).copy_(torch.from_numpy(C_ALPHA(alpha, self.K).astype(np.float32)))
         # the critic steps' generator forwards evaluated as one batch (prepare_critic_fakes): fakes of all N_CRITIC steps,
         # and the discriminator input [real ; fake] of a step at a fixed address the fake rows are copied into
         self.fakes_all = P((N_CRITIC * B, OUTPUT_DIM), act)
-        self.x_all = P((2 * B, OUTPUT_DIM), act)
+        # (with the consistency term: the first 2B rows of the 4B-row critic input, whose last 2B rows the term's augmentation fills)
+        # (under DiffAugment the 4B-row input is the augmentation's output: no persistent one)
+        self.x_all4 = P((4 * B, OUTPUT_DIM), act) if (self.bcr and not self.aug) else None
+        self.x_all = self.x_all4.rows(0, 2 * B) if self.x_all4 is not None else P((2 * B, OUTPUT_DIM), act)
         self._fakes_left = 0
         # loss accumulators: scalars behind the gradient slabs, cleared by the step's zero_grad()
         self.loss_d = self.PD.scalar(0)
@@ -717,6 +755,8 @@ class CifarRCGAN:
         # the augmentation draws from a stream of its own: noise and z of a run do not move when the option is turned on.  Like
         # rng_state it is not part of state_dict.
         self.aug_rng_state = torch.zeros(2, dtype=torch.int64, device=ctx.device) if self.aug else None
+        # ... and so does the consistency term's augmentation: no other draw of a run moves when it is turned on
+        self.bcr_rng_state = torch.zeros(2, dtype=torch.int64, device=ctx.device) if self.bcr else None
         # the controller of the augmentation probability lives on the device, inside the captured steps (rcgan_ada_update):
         # {p, sign_sum, image_count, steps, r_last, updates, 0, 0}.  Part of state_dict ("_ada_state").
         self.ada_state = (torch.tensor([self.ada_p_init] + [0.0] * 7, dtype=torch.float32, device=ctx.device) if self.ada else None)
@@ -728,6 +768,9 @@ class CifarRCGAN:
         # the logits rcgan_ada_update and rcgan_lecam_update read after the fused head (which otherwise keeps them on chip):
         # head_logits if set, else this one buffer, shared by the two options
         self.ada_logits = P((2 * B, self.K), f32, fill=0.0) if ((self.ada or self.lecam) and self.fused_head) else None
+        # the unweighted consistency means of the last critic step's real and fake pairs: two scalars behind the gradient slab (cleared
+        # with it); read by bcr_report().  The term has no state: nothing of it is in state_dict.
+        self.bcr_terms = (self.PD.scalar(2), self.PD.scalar(3)) if self.bcr else None
         # the ratios r_i of the last generator step's B pairs (-1: a masked pair), written by rcgan_pair_diversity_fwd_bwd; read by
         # diversity_report().  The term has no state: nothing of it is in state_dict.
         self.diversity_ratio = P((B,), f32, fill=0.0) if self.diversity else None
@@ -849,14 +892,40 @@ class CifarRCGAN:
             ctx.check(ctx.lib.rcgan_rng_fill(ctx.h, u.size, u.dtype, 0, 0.0, 1.0, self.seed * 1000003 + self.rank + 700001,
                                              C.c_void_p(self.aug_rng_state.data_ptr()), C.c_void_p(u.ptr)))
 
-    def _augment(self, x, name, pool=False):
+    def _augment(self, x, name, pool=False, **out):
         """DiffAugment of x from the step input `name` ("aug_u" / "aug_u_G"), every transform with probability p where the
-        adaptive probability is on (p is read on the device when the launch runs)."""
+        adaptive probability is on (p is read on the device when the launch runs).  out: ops.diffaugment's out / pool_out."""
         inp = self.inp
         self._draw_aug(inp[name])
         if not self.ada:
-            return O.diffaugment(self.ctx, x, inp[name], self.aug, pool=pool)
-        return O.diffaugment(self.ctx, x, inp[name], self.aug, pool=pool, gate=inp["aug_gate" + name[len("aug_u"):]], p=self.ada_state)
+            return O.diffaugment(self.ctx, x, inp[name], self.aug, pool=pool, **out)
+        return O.diffaugment(self.ctx, x, inp[name], self.aug, pool=pool, gate=inp["aug_gate" + name[len("aug_u"):]], p=self.ada_state, **out)
+
+    def _bcr_second_half(self, x_all, d4, pool4):
+        """Rows [2B, 4B) of the critic input d4 [4B, 3072] of a step with the consistency term, and of its pooled copy pool4 (or None):
+        bcr_policy applied to the UN-augmented x_all, always (no gate), from uniforms of their own -- drawn here on the device, or the
+        step input bcr_u.  The launch writes where the trunk reads: nothing is copied."""
+        ctx, B, u = self.ctx, self.B, self.inp["bcr_u"]
+        if self.device_rng:
+            ctx.check(ctx.lib.rcgan_rng_fill(ctx.h, u.size, u.dtype, 0, 0.0, 1.0, self.seed * 1000003 + self.rank + 900001,
+                                             C.c_void_p(self.bcr_rng_state.data_ptr()), C.c_void_p(u.ptr)))
+        O.diffaugment(ctx, x_all, u, self.bcr_policy, pool=pool4 is not None, out=d4.rows(2 * B, 4 * B),
+                      pool_out=pool4.rows(2 * B, 4 * B) if pool4 is not None else None)
+
+    def _bcr_part(self, feat, wgan, lo, x, labels, wts, lam, term_acc):
+        """The consistency term of the part whose B rows start at row lo of the first half: the scores of rows lo + 2B .. lo + 3B formed
+        as the part's loss term forms x -- the logit at the row's label (labels) or every label's logit (wts) -- from a projection of
+        their own (proj_logit and proj_logit_all write their embeddings' gradient, so each call brings its embeddings), then the pair
+        kernel behind the loss term that has written x's gradient."""
+        if lam == 0.0:
+            return
+        ctx, B = self.ctx, self.B
+        f, psi = O.rows(ctx, feat, lo + 2 * B, lo + 3 * B), O.rows(ctx, wgan, lo + 2 * B, lo + 3 * B)
+        if wts is None:
+            x_aug = O.proj_logit(ctx, f, psi, Discriminator_projection(labels, update_collection=None))
+        else:
+            x_aug = O.proj_logit_all(ctx, f, psi, Discriminator_projection(self.inp["arange"], update_collection=None))
+        O.pair_consistency(ctx, x, x_aug, lam, self.loss_d, wts=wts, term_acc=term_acc)
 
     def _ada_update(self, logits, ld, labels):
         """One call of the controller on the real rows' scores of this critic step (no-op with the option off and in forward-only
@@ -1015,12 +1084,19 @@ class CifarRCGAN:
         # only -- noise, preprocessing, the image pool of D.Block.1's shortcut, the zero-fill -- rides in the filter-preparation
         # launch (rcgan_conv_prepare_batch_riders) instead of five launches in front of the first convolution.
         ride = fakes_ready and self._rides_inputs()
-        x_all = self.x_all if fakes_ready else ctx.empty((2 * B, OUTPUT_DIM))
+        # the consistency term (recorded steps only: eval_d_cost is the plain dev cost).  Without DiffAugment [real ; fake] ARE the first
+        # 2B rows of the 4B-row critic input, and their pooled copy the first 2B rows of a 4B-row pool; with it the 4B-row buffers
+        # are the first augmentation's outputs, allocated there
+        bcr = self.bcr and ctx.recording
+        x4 = None
+        if bcr and not self.aug:
+            x4 = self.x_all4 if fakes_ready else ctx.empty((4 * B, OUTPUT_DIM))
+        x_all = self.x_all if fakes_ready else (x4.rows(0, 2 * B) if x4 is not None else ctx.empty((2 * B, OUTPUT_DIM)))
         real, fake_dst = x_all.rows(0, B), x_all.rows(B, 2 * B)
         si = None
         if ride:
             fptr, fcount = self.PD.zero_grad(defer=True)
-            g.image_pool = ctx.empty((2 * B, 16, 16, 3), x_all.dtype)
+            g.image_pool = ctx.empty(((4 if x4 is not None else 2) * B, 16, 16, 3), x_all.dtype)
             si = L.StepInputsDesc(B, real.dtype, inp["images"].ptr, x_all.ptr, g.image_pool.ptr,
                                   0.0, 1.0 / 128, self.seed * 1000003 + self.rank, self.rng_state.data_ptr(), fptr, fcount,
                                   self.fakes_all.ptr, self.slice_ctr.data_ptr(), N_CRITIC)       # the launch also fetches its fake batch
@@ -1032,7 +1108,8 @@ class CifarRCGAN:
                 if not fakes_ready:
                     self._rng(inp["z"], 1, 0.0, 1.0)
         g.prefetch_sn(self._sn_entries(True, True))
-        rode = self._prepare_all((self.PD,) if fakes_ready else (self.PG, self.PD), head_update=None, inputs=si)
+        # (a step with the consistency term takes the op-by-op head: no label embeddings ride in the preparation)
+        rode = self._prepare_all((self.PD,) if fakes_ready else (self.PG, self.PD), head_update=False if bcr else None, inputs=si)
         assert rode or si is None, "the step-input rider needs the batched filter preparation"
         # [real ; fake] is ONE discriminator pass for every algorithm: there is no norm layer in D and the spectral-norm
         # weights of a step are computed once (prefetch_sn above), so D(real) and D(fake) of the reference's rcgan-u graph
@@ -1049,9 +1126,16 @@ class CifarRCGAN:
             # out of the same launch (the rider's pool is of the un-augmented images: where the rider runs it still fills its own
             # [2B, 16, 16, 3] buffer, part of its launch and 98 KB of arena at B = 64, which nothing reads).  perm_classifier below
             # keeps `real`.
-            d_in, g.image_pool = self._augment(x_all, "aug_u", pool=True)
+            if bcr:
+                x4, g.image_pool = ctx.empty((4 * B, OUTPUT_DIM)), ctx.empty((4 * B, 16, 16, 3), x_all.dtype)
+                self._augment(x_all, "aug_u", pool=True, out=x4.rows(0, 2 * B), pool_out=g.image_pool.rows(0, 2 * B))
+            else:
+                d_in, g.image_pool = self._augment(x_all, "aug_u", pool=True)
+        if bcr:
+            self._bcr_second_half(x_all, x4, g.image_pool)
+            d_in = x4
         w = 1.0       # (the gradient scale of 16-bit activations is applied inside the loss kernels: rcgan_set_grad_scale)
-        if self.fused_head:
+        if self.fused_head and not bcr:
             feat = Discriminator(d_in, None, update_collection=None, _head=False)         # :584
             lab_r, lab_f = inp["labels_all"].rows(0, B), inp["labels_all"].rows(B, 2 * B)
             if self.alg == "rcgan-u":          # fake logits for every label, weighted by the confusion rows (:654-684)
@@ -1080,15 +1164,24 @@ class CifarRCGAN:
             O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d, wts=y_conf, reg=self._lecam_reg("fake"))   # :673,684
             O.loss_term(ctx, L.LOSS_HINGE_REAL, disc_real, w, self.loss_d, reg=self._lecam_reg("real"))               # :674
             self._lecam_update_all_labels(feat_a, wgan_a, E, (inp["labels"], None), (None, y_conf))
+            if bcr:
+                self._bcr_part(feat_a, wgan_a, 0, disc_real, inp["labels"], None, self.bcr_real, self.bcr_terms[0])
+                self._bcr_part(feat_a, wgan_a, B, disc_fake, None, y_conf, self.bcr_fake, self.bcr_terms[1])
         else:
             feat, wgan = Discriminator(d_in, None, update_collection=None)               # :584
             if self.alg in ("biased", "rcgan"):
                 emb = Discriminator_projection(inp["labels_all"], update_collection=None)    # :585
-                disc_all = O.proj_logit(ctx, feat, wgan, emb)                            # :588
+                # (with the consistency term feat has 4B rows: the loss terms and the controllers keep rows [0, 2B))
+                feat2, wgan2 = (O.rows(ctx, feat, 0, 2 * B), O.rows(ctx, wgan, 0, 2 * B)) if bcr else (feat, wgan)
+                disc_all = O.proj_logit(ctx, feat2, wgan2, emb)                          # :588
                 self._ada_update(disc_all, 1, None)                                      # (rows 0 .. B: the real ones)
                 O.loss_term(ctx, L.LOSS_HINGE_REAL, O.rows(ctx, disc_all, 0, B), w, self.loss_d, reg=self._lecam_reg("real"))       # :604
                 O.loss_term(ctx, L.LOSS_HINGE_FAKE, O.rows(ctx, disc_all, B, 2 * B), w, self.loss_d, reg=self._lecam_reg("fake"))   # :605
                 self._lecam_update(disc_all, 1, (None, None), (None, None))
+                if bcr:
+                    lab = inp["labels_all"]
+                    self._bcr_part(feat, wgan, 0, O.rows(ctx, disc_all, 0, B), lab.rows(0, B), None, self.bcr_real, self.bcr_terms[0])
+                    self._bcr_part(feat, wgan, B, O.rows(ctx, disc_all, B, 2 * B), lab.rows(B, 2 * B), None, self.bcr_fake, self.bcr_terms[1])
             else:   # unbiased (:613-648): every label's projection once, real loss weighted by C^-1 rows
                 E = Discriminator_projection(inp["arange"], update_collection=None)
                 feat_r, wgan_r = O.rows(ctx, feat, 0, B), O.rows(ctx, wgan, 0, B)
@@ -1100,6 +1193,9 @@ class CifarRCGAN:
                 disc_fake = O.proj_logit(ctx, feat_f, wgan_f, emb_f)
                 O.loss_term(ctx, L.LOSS_HINGE_FAKE, disc_fake, w, self.loss_d, reg=self._lecam_reg("fake"))           # :639,648
                 self._lecam_update_all_labels(feat, wgan, E, (None, inp["inv_weights"]), (inp["labels_random"], None))
+                if bcr:
+                    self._bcr_part(feat, wgan, 0, disc_real_all, None, inp["inv_weights"], self.bcr_real, self.bcr_terms[0])
+                    self._bcr_part(feat, wgan, B, disc_fake, inp["labels_random"], None, self.bcr_fake, self.bcr_terms[1])
         if self.perm:
             logits = perm_classifier(real, self.perm_type)                               # :692
             O.bce_onehot_term(ctx, logits, inp["labels"], 1.0, self.loss_d)                          # :693-695
@@ -1474,6 +1570,14 @@ class CifarRCGAN:
         return dict(ratio_mean=float(r[live].mean()) if live.any() else None,
                     clamped=float(np.count_nonzero(live & (r >= self.diversity_tau))) / r.size,
                     masked=float(np.count_nonzero(~live)) / r.size)
+
+    def bcr_report(self):
+        """{real, fake}: the unweighted consistency means of the last critic step's real and fake pairs (synchronises) -- the mean over
+        the part's rows of the squared difference between the score of an image and of its augmented copy, scalars of the step, so a
+        forward-only eval_d_cost since then has cleared them.  None with the option off."""
+        if self.bcr_terms is None:
+            return dict(real=None, fake=None)
+        return dict(real=float(self.ctx.download(self.bcr_terms[0])[0]), fake=float(self.ctx.download(self.bcr_terms[1])[0]))
 
     def lecam_report(self):
         """{a_real, a_fake, mean_real, mean_fake, reg, updates, skipped} of the LeCam regulariser as it stands on the stream now

@@ -705,6 +705,79 @@ __global__ __launch_bounds__(256) void lecam_update_kernel(LecamPart A, LecamPar
   st[4] = mb;
 }
 
+// The balanced-consistency term of one part (the definition is in include/rcgan_hip.h).  One workgroup, as loss_kernel: a strided loop
+// over the pairs * cols elements -- consecutive threads read consecutive elements of x, x_aug and wts, 16 bytes each where the
+// buffers allow it (V = 4) -- every gradient written in the same pass, one fixed-order block sum for the value.
+struct PairConsArgs {
+  const float* x; const float* xa; const float* wts;
+  float* loss_acc; float* term_acc; float* dx; float* dxa; float* dwts;
+  int total, pairs, accumulate;
+  float lam;
+};
+
+// one element: e = x - x_aug; -> w e^2; *q = cx w e (the gradient of x, minus that of x_aug), *qw = cw e^2 (that of the weight)
+__device__ __forceinline__ float pair_cons_elem(float x, float xa, float w, float cx, float cw, float* q, float* qw) {
+  const float e = x - xa, e2 = e * e;
+  *q = cx * w * e;
+  *qw = cw * e2;
+  return w * e2;
+}
+
+template <int V> __device__ __forceinline__ void pair_cons_load(float* r, const float* p) {
+  if constexpr (V == 4) {
+    const float4 v = *(const float4*)p;
+    r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
+  } else {
+    r[0] = p[0];
+  }
+}
+template <int V> __device__ __forceinline__ void pair_cons_store(float* p, const float* r) {
+  if constexpr (V == 4) *(float4*)p = make_float4(r[0], r[1], r[2], r[3]);
+  else p[0] = r[0];
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void pair_consistency_kernel(PairConsArgs a, float gs_host, const float* gs_dev) {
+  __shared__ float red[4];
+  const float gs = grad_scale_of(gs_host, gs_dev);
+  const float inv_pairs = 1.f / (float)a.pairs;
+  const float cx = (2.f * a.lam * inv_pairs) * gs, cw = (a.lam * inv_pairs) * gs;
+  float acc = 0.f;
+  for (int i = threadIdx.x * V; i < a.total; i += 256 * V) {
+    float x[V], xa[V], w[V], q[V], qw[V];
+    pair_cons_load<V>(x, a.x + i);
+    pair_cons_load<V>(xa, a.xa + i);
+    if (a.wts) pair_cons_load<V>(w, a.wts + i);
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc += pair_cons_elem(x[k], xa[k], a.wts ? w[k] : 1.f, cx, cw, &q[k], &qw[k]);
+    // (total is a multiple of V on the V = 4 route: no element past the end)
+    if (a.dx) {
+      float o[V];
+      if (a.accumulate) pair_cons_load<V>(o, a.dx + i);
+#pragma unroll
+      for (int k = 0; k < V; ++k) o[k] = a.accumulate ? o[k] + q[k] : q[k];
+      pair_cons_store<V>(a.dx + i, o);
+    }
+    if (a.dxa) {
+#pragma unroll
+      for (int k = 0; k < V; ++k) q[k] = -q[k];
+      pair_cons_store<V>(a.dxa + i, q);
+    }
+    if (a.dwts) {
+      float o[V];
+      pair_cons_load<V>(o, a.dwts + i);
+#pragma unroll
+      for (int k = 0; k < V; ++k) o[k] += qw[k];
+      pair_cons_store<V>(a.dwts + i, o);
+    }
+  }
+  acc = block_sum256(acc, red) * inv_pairs;
+  if (threadIdx.x == 0) {
+    if (a.loss_acc) *a.loss_acc += a.lam * acc;
+    if (a.term_acc) *a.term_acc += acc;
+  }
+}
+
 // What the unfused head / loss entry points refuse before they launch anything: a non-positive dimension, a NULL tensor they would touch.
 #define HL_SHAPE(ctx, ok, ...) RC_REQUIRE(ctx, ok, "bad shape: " __VA_ARGS__)
 #define HL_TENSORS(ctx, ok) RC_REQUIRE(ctx, ok, "null tensor")
@@ -1034,6 +1107,29 @@ int rcgan_lecam_update(rcgan_ctx* ctx, int rows_a, int rows_b, const float* logi
   RC_REQUIRE(ctx, decay >= 0.f && decay <= 1.f, "decay %g: in [0, 1]", (double)decay);
   const LecamPart A = {rows_a, (const int*)labels_a, wts_a}, B = {rows_b, (const int*)labels_b, wts_b};
   hipLaunchKernelGGL(lecam_update_kernel, dim3(1), dim3(256), 0, ctx->stream, A, B, logits, ld, state, decay);
+  RC_LAUNCH_CHECK(ctx);
+  return RCGAN_OK;
+}
+
+int rcgan_pair_consistency_fwd_bwd(rcgan_ctx* ctx, int pairs, int cols, const float* x, const float* x_aug, const float* wts, float lam,
+                                   float* loss_acc, float* term_acc, float* dx, int accumulate, float* dx_aug, float* dwts) {
+  RC_REQUIRE(ctx, pairs >= 1 && cols >= 1 && (long)pairs * cols <= (1L << 20), "%d pairs of %d columns: at least one of each, at most 2^20 elements (one workgroup serves them)",
+             pairs, cols);
+  RC_REQUIRE(ctx, x && x_aug, "null pointer");
+  RC_REQUIRE(ctx, !dwts || wts, "a weight gradient needs the weights");
+  const uintptr_t all = (uintptr_t)x | (uintptr_t)x_aug | (uintptr_t)wts | (uintptr_t)loss_acc | (uintptr_t)term_acc | (uintptr_t)dx |
+                        (uintptr_t)dx_aug | (uintptr_t)dwts;
+  RC_REQUIRE(ctx, (all & 3) == 0, "logits, weights, accumulators and gradients must be 4-byte aligned");
+  RC_REQUIRE(ctx, lam >= 0.f && std::isfinite(lam), "lam %g: finite and >= 0", (double)lam);
+  if (lam == 0.f) return RCGAN_OK;
+  const int total = pairs * cols;
+  const PairConsArgs a = {x, x_aug, wts, loss_acc, term_acc, dx, dx_aug, dwts, total, pairs, accumulate ? 1 : 0, lam};
+  // 16-byte loads and stores where every tensor starts on a 16-byte boundary and the elements are a whole number of quads
+  const uintptr_t tensors = (uintptr_t)x | (uintptr_t)x_aug | (uintptr_t)wts | (uintptr_t)dx | (uintptr_t)dx_aug | (uintptr_t)dwts;
+  if ((tensors & 15) == 0 && total % 4 == 0)
+    hipLaunchKernelGGL(pair_consistency_kernel<4>, dim3(1), dim3(256), 0, ctx->stream, a, ctx->gscale_host, ctx->gscale_dev);
+  else
+    hipLaunchKernelGGL(pair_consistency_kernel<1>, dim3(1), dim3(256), 0, ctx->stream, a, ctx->gscale_host, ctx->gscale_dev);
   RC_LAUNCH_CHECK(ctx);
   return RCGAN_OK;
 }

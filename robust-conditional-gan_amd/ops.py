@@ -1109,14 +1109,16 @@ def dropout(ctx, x, keep_prob, seed, state):
     return y
 
 
-def diffaugment(ctx, x, u, policy, pool=False, gate=None, p=None):
+def diffaugment(ctx, x, u, policy, pool=False, gate=None, p=None, out=None, pool_out=None):
     """DiffAugment of NHWC images x [n, h, w, 3] (or their flattened rows [n, h*w*3] of square images) under the policy bits
     L.AUG_*: colour jitter, integer translation, cutout, each sample from its row of u [n, 8] (fp32 uniforms in [0, 1), drawn by the
     caller) -- rcgan_diffaugment_fwd, one launch, with its adjoint on the tape when x is tracked.  pool=True: also returns the 2x2
     mean of the result out of the same launch (the bits of meanpool2 on it; not tracked: for a critic input that needs no gradient).
     gate [n, 4] (fp32 uniforms) and p (a device fp32 scalar: a DT, a torch tensor or an address) together: every transform of the
     policy is applied to a sample only where its gate is below p as p stands when the launch RUNS (rcgan_diffaugment_gated_fwd), and
-    the adjoint follows the per-sample policies that launch recorded (rcgan_diffaugment_sampled_bwd)."""
+    the adjoint follows the per-sample policies that launch recorded (rcgan_diffaugment_sampled_bwd).
+    out / pool_out: buffers of x's dtype and element count / of the pooled result's that the launch writes instead of fresh ones (rows
+    of a larger batch)."""
     if (gate is None) != (p is None):
         raise ValueError("diffaugment: gate and p come together")
     if len(x.shape) == 4:
@@ -1130,8 +1132,10 @@ def diffaugment(ctx, x, u, policy, pool=False, gate=None, p=None):
         raise ValueError("diffaugment: 3-channel images, got %d channels" % c)
     if tuple(u.shape) != (n, 8) or u.dtype != L.F32:
         raise ValueError("diffaugment: u must be fp32 [%d, 8], got %r" % (n, u.shape))
-    y = ctx.empty(x.shape, x.dtype)
-    yp = ctx.empty((n, h // 2, w // 2, 3), x.dtype) if pool else None
+    y = ctx.empty(x.shape, x.dtype) if out is None else out.reshape(x.shape)
+    yp = (ctx.empty((n, h // 2, w // 2, 3), x.dtype) if pool_out is None else pool_out.reshape((n, h // 2, w // 2, 3))) if pool else None
+    if y.dtype != x.dtype or (yp is not None and yp.dtype != x.dtype):
+        raise ValueError("diffaugment: out and pool_out must have the dtype of x")
     if gate is not None:
         if tuple(gate.shape) != (n, 4) or gate.dtype != L.F32:
             raise ValueError("diffaugment: gate must be fp32 [%d, 4], got %r" % (n, gate.shape))
@@ -1497,6 +1501,28 @@ def loss_term(ctx, kind, x, weight, loss_acc, wts=None, reg=None):
         ctx.check(ctx.lib.rcgan_loss_fwd_bwd(ctx.h, kind, r, c, _p(x), _p(wts), float(weight), _p(loss_acc), _p(dx), _p(dw)))
     else:
         ctx.check(ctx.lib.rcgan_loss_reg_fwd_bwd(ctx.h, kind, r, c, _p(x), _p(wts), float(weight), _p(loss_acc), _p(dx), _p(dw), C.byref(reg)))
+
+
+def pair_consistency(ctx, x, x_aug, lam, loss_acc, wts=None, term_acc=None):
+    """The balanced-consistency term of one part (rcgan_pair_consistency_fwd_bwd, include/rcgan_hip.h): adds
+    lam * mean_i sum_l w[i,l] (x[i,l] - x_aug[i,l])^2 to the device scalar loss_acc and the unweighted mean to term_acc.  x and x_aug:
+    fp32 [pairs] (the logit at the row's label) or [pairs, cols] with wts [pairs, cols].  Like loss_term the gradients are produced in
+    the forward launch; unlike it they are ADDED to what x.grad (and wts.grad) hold already, so the term goes BEHIND the loss terms
+    that write them.  x_aug.grad is written whole: this term is x_aug's only consumer."""
+    if tuple(x_aug.shape) != tuple(x.shape) or (wts is not None and tuple(wts.shape) != tuple(x.shape)):
+        raise ValueError("pair_consistency: x, x_aug and wts of one shape, got %r, %r and %r"
+                         % (x.shape, x_aug.shape, None if wts is None else wts.shape))
+    r, c = (x.shape[0], 1) if len(x.shape) == 1 else x.shape
+    rec = ctx.recording and float(lam) != 0.0        # (lam == 0 launches nothing: no gradient buffer is created for it)
+    dx, acc = grad_of(ctx, x) if (x.req and rec) else (None, 0)
+    dxa = grad_of(ctx, x_aug)[0] if (x_aug.req and rec) else None
+    dw = None
+    if wts is not None and wts.req and rec:
+        if wts.grad is None:
+            wts.grad = zeros_like_grad(ctx, wts)
+        dw = wts.grad
+    ctx.check(ctx.lib.rcgan_pair_consistency_fwd_bwd(ctx.h, r, c, _p(x), _p(x_aug), _p(wts), float(lam), _p(loss_acc), _p(term_acc),
+                                                     _p(dx), acc, _p(dxa), _p(dw)))
 
 
 def bce_onehot_term(ctx, x, labels, weight, loss_acc):

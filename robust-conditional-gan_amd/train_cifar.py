@@ -81,6 +81,12 @@ def define_flags():
                    "is rewarded for image distance per unit of latent distance between two fakes of one label; 0: off (not tuned on "
                    "CIFAR here)")
     f.DEFINE_float("diversity_tau", float("inf"), "--diversity: clamp of the distance ratio, > 0; inf: none (not tuned on CIFAR here)")
+    f.DEFINE_float("bcr_real", 0.0, "weight of balanced consistency regularisation on the real images (Zhang et al. 2020, Zhao et al. "
+                   "2020): the critic is penalised for scoring an image and its --bcr_policy copy differently; 0: off (the papers' "
+                   "CIFAR value is 10 for both weights; not tuned here)")
+    f.DEFINE_float("bcr_fake", 0.0, "the same weight on the generated images; 0: off")
+    f.DEFINE_string("bcr_policy", 'translation', "--bcr_real / --bcr_fake: the transform, a comma-separated subset of "
+                    "color,translation,cutout")
     M.define_flags(f)             # the sample-quality metrics' flags
     f.DEFINE_integer("sample_every", 0, "if > 0: overrides --sample_freq (dev cost + sample grid period)")
     f.DEFINE_integer("early_checkpoint_every", 1, "checkpoint period during the first 500 iterations (the reference: every one)")
@@ -145,13 +151,14 @@ def main(argv=None):
         if asset_classes != N_CLASSES:
             raise ValueError("--label_classifier %s classifies %d classes, this run has %d"
                              % (FLAGS.label_classifier, asset_classes, N_CLASSES))
-    from .cifar import check_ada, check_diversity, check_lecam, pair_generator_labels, parse_diffaugment
+    from .cifar import check_ada, check_bcr, check_diversity, check_lecam, pair_generator_labels, parse_diffaugment
     parse_diffaugment(FLAGS.diffaugment)          # (a bad name fails here, before anything touches the GPU)
     # ... and so do the adaptive probability's ranges, --ada_target without --diffaugment, and more than one rank
     check_ada(FLAGS.ada_target, FLAGS.ada_images, FLAGS.ada_interval, FLAGS.ada_p_init, FLAGS.diffaugment,
               int(os.environ.get("WORLD_SIZE", "1")))
     check_lecam(FLAGS.lecam, FLAGS.lecam_decay, int(os.environ.get("WORLD_SIZE", "1")))
     check_diversity(FLAGS.diversity, FLAGS.diversity_tau, int(os.environ.get("WORLD_SIZE", "1")))
+    check_bcr(FLAGS.bcr_real, FLAGS.bcr_fake, FLAGS.bcr_policy, int(os.environ.get("WORLD_SIZE", "1")))
     logging.basicConfig(filename=FLAGS.log_file, level=logging.DEBUG if FLAGS.log_level == 'debug' else logging.INFO,
                         format='%(asctime)s %(levelname)-8s %(message)s')
     ALGORITHM, ALPHA = FLAGS.algorithm, FLAGS.alpha
@@ -162,6 +169,8 @@ def main(argv=None):
     logging.info('ada_target = {}'.format(FLAGS.ada_target or 'off'))
     logging.info('lecam = {}'.format(FLAGS.lecam or 'off'))
     logging.info('diversity = {}'.format('{} (tau {})'.format(FLAGS.diversity, FLAGS.diversity_tau) if FLAGS.diversity else 'off'))
+    logging.info('bcr = {}'.format('real {} fake {} ({})'.format(FLAGS.bcr_real, FLAGS.bcr_fake, FLAGS.bcr_policy)
+                                   if (FLAGS.bcr_real or FLAGS.bcr_fake) else 'off'))
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -210,7 +219,8 @@ def main(argv=None):
                    device=local, world_size=world, rank=rank, f32_matmul_precision=FLAGS.f32_matmul_precision,
                    n_classes=N_CLASSES, diffaugment=FLAGS.diffaugment, ada_target=FLAGS.ada_target, ada_images=FLAGS.ada_images,
                    ada_interval=FLAGS.ada_interval, ada_p_init=FLAGS.ada_p_init, lecam=FLAGS.lecam, lecam_decay=FLAGS.lecam_decay,
-                   diversity=FLAGS.diversity, diversity_tau=FLAGS.diversity_tau)
+                   diversity=FLAGS.diversity, diversity_tau=FLAGS.diversity_tau, bcr_real=FLAGS.bcr_real, bcr_fake=FLAGS.bcr_fake,
+                   bcr_policy=FLAGS.bcr_policy)
 
     # data: label noise drawn from the global numpy stream exactly as the reference does (unseeded there)
     clean_train = None                 # (images, clean labels) of the training set: the real side of the sample-quality metrics
@@ -358,6 +368,10 @@ def main(argv=None):
                 plot.plot('lecam_a_real', lecam["a_real"])
                 plot.plot('lecam_a_fake', lecam["a_fake"])
                 plot.plot('lecam_reg', lecam["reg"])
+            if m.bcr:                  # the unweighted consistency means of the last critic step (scalars of the step, as lecam_reg)
+                bcr = m.bcr_report()
+                plot.plot('bcr_real', bcr["real"])
+                plot.plot('bcr_fake', bcr["fake"])
             if m.diversity and iteration > 0:      # the last generator step's pairs (iteration 0 has no generator step)
                 div = m.diversity_report()
                 if div["ratio_mean"] is not None:
